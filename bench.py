@@ -29,6 +29,8 @@ files, index loaded from the cache files, next to `ngm-core -t <cores>` on a sli
 
   --stub-mapper: no GPU, no library -- the mapping call is replaced by a deterministic fake so that the N > 1 control path
   (sharding, cache hand-over between ranks, stats all-reduce, the JSON line) runs under gloo on CPU (tests/test_sharding_gloo.py).
+  --dump-outputs DIR: after the timed steps, what the last one handed its caller (hit records, CIGAR / MD buffers of a fixed,
+  seeded sample of rank 0's reads) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -791,6 +793,35 @@ def cpu_baseline_port(rows_qry, budget_s=8.0):
             "sample": "%d pairs, oracle C restatement of BatchScore only, OpenMP %d threads (no candidate search)" % (len(idx), cores)}
 
 
+DUMP_ROWS = 65536          # --dump-outputs: reads sampled from a step's outputs (whole pairs for paired reads)
+DUMP_STRING_BYTES = 40 << 20   # ... and the budget of the CIGAR + MD rows among them (float32, 4 bytes per buffer byte)
+
+
+def sample_outputs(out, paired):
+    """--dump-outputs: what the timed path hands its caller after a step -- the hit records and the CIGAR / MD buffers
+    of map_{pe,se}_raw -- on a fixed, seeded sample of the reads, as float64 / float32 arrays (under 64 MB in all).
+    `rows` holds the sampled read indices; cigar / md cover the first of them, as many as DUMP_STRING_BYTES allows."""
+    hits, cig, md = out
+    n = len(hits)
+    if n <= DUMP_ROWS:
+        rows = np.arange(n)
+    else:
+        rng = np.random.default_rng(20240604)
+        if paired:
+            frag = np.sort(rng.choice(n // 2, DUMP_ROWS // 2, replace=False))
+            rows = np.stack([2 * frag, 2 * frag + 1], axis=1).ravel()
+        else:
+            rows = np.sort(rng.choice(n, DUMP_ROWS, replace=False))
+    d = {"rows": rows.astype(np.float64)}
+    h = hits[rows]
+    for f in hits.dtype.names:
+        d["hits_" + f] = h[f].astype(np.float64)
+    s = rows[:min(len(rows), DUMP_STRING_BYTES // (2 * 4 * cig.shape[1]) & ~1)]
+    d["cigar"] = cig[s].astype(np.float32)
+    d["md"] = md[s].astype(np.float32)
+    return d
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -823,7 +854,12 @@ def main():
     ap.add_argument("--heavy-tail-cpu-reads", type=int, default=50_000, help="reads of a heavy-tail sub-leg's cpu_baseline sample (the reference maps 350-800 of them per second; 0: none)")
     ap.add_argument("--heavy-tail-e2e-reads", type=int, default=10_000_000, help="reads of the ngm-hip run on the GRCh38-like genome, FASTQ -> closed SAM (BASELINE config #3; 0: skip)")
     ap.add_argument("--heavy-tail-repeat-share", type=float, default=0.5)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's reads: hit records, CIGAR / MD buffers; a fixed, "
+                         "seeded sample) as DIR/<name>.npy in float32 / float64")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     global Q, C, READ_LEN
     READ_LEN = args.read_len
     Q = (READ_LEN | 1) + 1                                   # ReadProvider.cpp:288
@@ -987,6 +1023,11 @@ def main():
     kms = run(args.steps)
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # before the isolated extra pass below writes into instance 0's slice again
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in sample_outputs(out, paired).items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
     kms /= max(1, args.steps)  # GPU time per step (R reads), summed over the W streams' launches
     hits = out[0]
     if world > 1:

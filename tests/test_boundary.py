@@ -73,6 +73,19 @@ def test_vtable_and_struct_abi_match_reference_headers(tmp_path):
     assert out.returncode == 0, out.stdout + out.stderr
 
 
+def test_vtable_and_struct_abi_match_reference_golden(tmp_path):
+    """The same agreement without the reference tree: every vtable slot, destructor slot, struct size and field offset
+    and cCookie that tests/cpp/abi_probe.cpp reads from include/ngm_ialignment.h equals what it read from the reference's
+    headers (tests/golden/ialignment_abi.json, written by oracle/make_abi_golden.py)."""
+    import json
+    exe = str(tmp_path / "abi_probe")
+    subprocess.check_call(["g++", "-std=gnu++11", "-w", os.path.join(CPP, "abi_probe.cpp"), "-I", INC, "-o", exe])
+    mine = json.loads(subprocess.check_output([exe]).decode())
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "ialignment_abi.json")))
+    assert len(want) >= 40
+    assert mine == want, {k: (want.get(k), mine.get(k)) for k in set(want) | set(mine) if want.get(k) != mine.get(k)}
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode", [0, 1])
 def test_cpp_host_drives_plugin_like_ngm(tmp_path, mode):
