@@ -323,6 +323,35 @@ int ngm_mapper_last_kernel_ms(ngm_mapper *m, float ms[8]);
 /* ... and of the candidate-order replays of that call (cs_order_kernel: runs on a stream of its own beside the stages above) */
 float ngm_mapper_last_order_replay_ms(ngm_mapper *m);
 
+/* ---- `--argos` (src/writer/ScoreWriter.cpp, src/ScoreBuffer.cpp:150-183): every scored candidate of a read, ordered by score --------------
+ * ngm_mapper_set_argos: min_score >= 0 turns the mode on for this mapper (Config ARGOS_MINSCORE, `--argos-min-score`: > 0 keeps the
+ * candidates with score >= min, min = read length * match_bonus * min_score when min_score <= 1, else min_score itself); < 0 turns it off.
+ * Single-end only; not with bs_mapping / slam_seq.  The search parameters the mode implies (sensitivity 0, kmer_min 2 unless given:
+ * src/config/Config.cpp:384-388, :517-520) are the caller's, in ngm_mapper_params. */
+int ngm_mapper_set_argos(ngm_mapper *m, float min_score);
+/* Candidate search and BatchScore of n reads (rows as for ngm_mapper_map_se), then per read ScoreWriter's line
+ * "name(\t<contig>:<pos>:<reverse>:<|score difference to the previous entry|>)*\n" over the candidates with a positive score in the order of
+ * the reference's std::sort, positions converted with the --argos clamp (src/SequenceProvider.cpp:111-142).  A read without candidates (or
+ * without survivors of the filter) writes nothing.  names / meta as for ngm_mapper_map_sam (qual_len is not used).  Returns the length of
+ * the text (> out_cap: nothing was copied -- ngm_mapper_sam_fetch with a larger buffer copies it), or < 0.  stats: reads counted, reads
+ * with a line (the reference's "mapped"), 0 (ScoreWriter counts no written lines).  kernel_ms (optional): GPU time of the ordering and
+ * text kernels. */
+long long ngm_mapper_map_argos(ngm_mapper *m, int n, const char *reads, const char *names, size_t names_bytes, const ngm_sam_read *meta,
+		char *out, size_t out_cap, uint64_t stats[3], float *kernel_ms);
+/* ScoreWriter::DoWriteProlog: "#<total_reads>\n#0:<name>\t1:<name>\t...\n".  Writes it when it fits in cap; returns its length, or < 0. */
+int ngm_argos_prolog(const ngm_ref *ref, uint64_t total_reads, char *out, size_t cap);
+/* summed over this mapper's ngm_mapper_map_argos calls: [0] reads (with a line) whose positive scores are all distinct (class U: any
+ * order prints the same), [1] reads of at most 16 survivors with a tie (class S: ordered on the GPU by score and the reference's candidate
+ * order), [2] more than 16 survivors with a tie (class H: libstdc++'s std::sort on the host), [3] entries written */
+int ngm_mapper_argos_counters(ngm_mapper *m, uint64_t out[4]);
+/* ... [0] reads ordered by the long-list path (more candidates than the LDS holds: a workgroup per read over global memory),
+ * [1] reads of class S / H ordered by position because the reference's candidate order could not be determined */
+int ngm_mapper_argos_path_counters(ngm_mapper *m, uint64_t out[2]);
+/* Host-only test entry: what the --argos ordering does with one read of n candidates (scores, and the reference's candidate order `rank`,
+ * may be NULL) under min_score for a read of read_len bases.  order: the survivors (indices into the list) in the order they are printed
+ * (the first out[1] of them are); out = {survivors, survivors with a positive score, class 0 U / 1 S / 2 H}. */
+int ngm_debug_argos_order(uint32_t n, const float *score, const uint32_t *rank, float min_score, int read_len, int match_bonus, uint32_t *order, uint32_t out[3]);
+
 #ifdef __cplusplus
 }
 #endif

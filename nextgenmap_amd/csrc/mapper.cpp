@@ -73,6 +73,27 @@ void host_window(const ngm_ref *r, uint64_t offset, int buffer_len, int want, ch
 
 }  // namespace
 
+namespace ngm {
+// window gather + BatchScore of all np candidates of the batch (ScoreBuffer::DoRun, src/ScoreBuffer.cpp:80-130): d_scores[c] for every
+// candidate; events ev[2] (behind the gather) and ev[3] (behind the score kernels).  The caller has reserved d_pair_read / d_scores and the
+// engine's buffers for np candidates.
+int score_candidates(ngm_mapper *m, int n, uint64_t np, int alt_dir) {
+	const ngm_ref *r = m->ref;
+	ngm_hip_ctx *eng = m->eng;
+	const int q = m->prm.qry_max_len, c = m->prm.corridor;
+	hipLaunchKernelGGL(ngm::expand_pairs_kernel, dim3(n), dim3(64), 0, m->st, n, m->d_cand_base.p, m->d_cand_count.p, m->d_pair_read.p);
+	const int nb = (int) ((np + ngm::kSlots - 1) / ngm::kSlots);
+	ngm::WindowGeom Gs{r->n_bases - 1, ((q + c) | 1) + 1, c >> 1};  // refMaxLen of ScoreBuffer.h:112
+	hipLaunchKernelGGL(ngm::gather_pairs_kernel, dim3(nb), dim3(256), 0, m->st, m->d_reads.p, m->d_read_len.p, q, r->d_genome, Gs,
+			m->d_pair_read.p, m->d_out_loc.p, m->d_out_sv.p, (int) np, eng->RW, eng->FW, eng->packed.p, eng->lens.p, eng->blk_rows.p, alt_dir);
+	MAP_HIP_TRY(hipGetLastError());
+	MAP_HIP_TRY(hipEventRecord(m->ev[2], m->st));
+	if (int rc = ngm::engine_score_packed(eng, m->prm.mode, (int) np, m->d_scores.p, m->st)) { ngm::pipeline_set_error("%s", ngm_hip_last_error(eng)); return rc; }
+	MAP_HIP_TRY(hipEventRecord(m->ev[3], m->st));
+	return 0;
+}
+}  // namespace ngm
+
 extern "C" {
 
 int ngm_ref_decode(const ngm_ref *r, uint64_t offset, int buffer_len, char *out) {
@@ -156,6 +177,7 @@ void ngm_mapper_destroy(ngm_mapper *m) {
 	ngm_bgzf_destroy(m->bz);
 	if (m->st_hi) { (void) hipStreamSynchronize(m->st_hi); (void) hipStreamDestroy(m->st_hi); }
 	ngm::cs_release(m);
+	ngm::argos_release(m);
 	m->d_reads.release(); m->d_scores.release(); m->d_best.release(); m->d_pair_read.release();
 	m->d_winner.release(); m->d_a_read.release(); m->d_a_loc.release(); m->d_a_sv.release(); m->d_mapq.release(); m->d_nbest.release();
 	m->d_records.release(); m->d_runs.release(); m->d_runs_c.release();
@@ -259,6 +281,7 @@ long long ngm_mapper_map_sam(ngm_mapper *m, int n, const char *reads, const char
 		char *out, size_t out_cap, uint64_t stats[3], float *kernel_ms) {
 	if (!m || n < 0 || (n > 0 && (!reads || !quals || !meta))) return -22;
 	SamCall sc{quals, names, names_bytes, reinterpret_cast<const ngm::SamMeta *>(meta), out, out_cap, stats, 0, 0.f};
+	m->argos_text = false;
 	const int rc = map_impl(m, n, reads, nullptr, nullptr, nullptr, nullptr, m->sam_opt.paired != 0, &sc);
 	if (rc < 0) return rc;
 	if (kernel_ms) *kernel_ms = sc.kernel_ms;
@@ -269,7 +292,7 @@ long long ngm_mapper_map_sam(ngm_mapper *m, int n, const char *reads, const char
 int ngm_mapper_sam_fetch(ngm_mapper *m, char *out, size_t out_cap) {
 	if (!m || !out || out_cap < m->sam_text_bytes) return -22;
 	DevGuard g(m->ref->device);
-	if (m->sam_opt.bam) {   // the last call's records are still in HBM: their BGZF blocks into the larger buffer; returns their length
+	if (m->sam_opt.bam && !m->argos_text) {   // the last call's records are still in HBM: their BGZF blocks into the larger buffer; returns their length
 		if (!m->sam_text_bytes) return 0;
 		const long long zlen = ngm_bgzf_compress_device(m->bz, m->d_sam_text.p, (size_t) m->sam_text_bytes, out, out_cap);
 		if (zlen < 0 || zlen > 0x7fffffffll) return zlen < 0 ? (int) zlen : -75;
@@ -690,15 +713,7 @@ static int map_impl(ngm_mapper *m, int n, const char *reads, const void *d_reads
 				m->d_best.reserve(n)) { ngm::pipeline_set_error("out of device memory (score stage)"); return -12; }
 		if (int rc = ngm::engine_reserve(eng, (int) np)) { ngm::pipeline_set_error("%s", ngm_hip_last_error(eng)); return rc; }
 		stage_cs.acquire();
-		hipLaunchKernelGGL(ngm::expand_pairs_kernel, dim3(n), dim3(64), 0, m->st, n, m->d_cand_base.p, m->d_cand_count.p, m->d_pair_read.p);
-		const int nb = (int) ((np + ngm::kSlots - 1) / ngm::kSlots);
-		ngm::WindowGeom Gs{r->n_bases - 1, ((q + c) | 1) + 1, c >> 1};  // refMaxLen of ScoreBuffer.h:112
-		hipLaunchKernelGGL(ngm::gather_pairs_kernel, dim3(nb), dim3(256), 0, m->st, m->d_reads.p, m->d_read_len.p, q, r->d_genome, Gs,
-				m->d_pair_read.p, m->d_out_loc.p, m->d_out_sv.p, (int) np, eng->RW, eng->FW, eng->packed.p, eng->lens.p, eng->blk_rows.p, alt_dir);
-		MAP_HIP_TRY(hipGetLastError());
-		MAP_HIP_TRY(hipEventRecord(m->ev[2], m->st));
-		if (int rc = ngm::engine_score_packed(eng, mode, (int) np, m->d_scores.p, m->st)) { ngm::pipeline_set_error("%s", ngm_hip_last_error(eng)); return rc; }
-		MAP_HIP_TRY(hipEventRecord(m->ev[3], m->st));
+		if (int rc = ngm::score_candidates(m, n, np, alt_dir)) return rc;
 		hipLaunchKernelGGL(ngm::select_top1_kernel, dim3((n + 255) / 256), dim3(256), 0, m->st, n, m->d_cand_base.p, m->d_cand_count.p,
 				m->d_scores.p, m->d_out_loc.p, m->d_out_sv.p, m->d_winner.p, m->d_mapq.p, m->d_nbest.p, m->d_best.p);
 		MAP_HIP_TRY(hipGetLastError());

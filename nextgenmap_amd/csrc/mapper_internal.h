@@ -141,6 +141,20 @@ struct ngm_mapper {
 	ngm::PinnedBuf<ngm::SamRef> p_sam_refs;
 	ngm::PinnedBuf<char> p_sam_extra;
 	uint64_t sam_text_bytes = 0;      // of the last batch (still in d_sam_text)
+	// --argos (ngm_mapper_set_argos / ngm_mapper_map_argos, mapper_argos.cpp): ScoreWriter's lines instead of SAM records
+	bool argos_on = false;
+	bool argos_text = false;          // d_sam_text holds the last ngm_mapper_map_argos call's text (ngm_mapper_sam_fetch copies it as it is)
+	float argos_min = 0.f;            // --argos-min-score
+	int argos_n_starts = 0;
+	ngm::DevBuf<uint64_t> d_argos_starts, d_argos_loff, d_argos_gkeys;
+	ngm::DevBuf<uint32_t> d_argos_ord, d_argos_nsurv, d_argos_npos, d_argos_list, d_argos_llist, d_argos_gvals, d_argos_hord, d_argos_hoff;
+	ngm::DevBuf<uint8_t> d_argos_cls;
+	ngm::DevBuf<unsigned long long> d_argos_ctr;
+	ngm::PinnedBuf<uint8_t> p_argos_cls;
+	ngm::PinnedBuf<uint32_t> p_argos_nsurv;
+	uint64_t argos_ctr[4] = {0, 0, 0, 0};   // reads ordered in class U, S, H; entries written
+	uint64_t argos_long = 0, argos_unknown = 0;   // reads ordered by the long-list path; S / H reads whose ranks were unknown (ordered by position)
+	hipEvent_t aev[4] = {};            // around the first order pass and around the text kernels
 	uint64_t pair_stats[3] = {0, 0, 0};   // ngm_mapper_last_pair_stats
 	// last CS result on the host
 	int n_reads = 0;
@@ -221,5 +235,10 @@ int cs_host_arrays(ngm_mapper *m);
 int candidate_order(ngm_mapper *m, const std::vector<uint32_t> &list, uint64_t np, uint32_t **h_rank, bool wait = true);
 int candidate_order_wait(ngm_mapper *m, uint32_t **h_rank);
 void cs_release(ngm_mapper *m);   // the search side's buffers (ngm_mapper_destroy)
+long test_limit(const char *key, long dflt);   // NGM_HIP_TEST_LIMITS (mapper_search.cpp)
+
+// ---- mapper.cpp / mapper_argos.cpp ---------------------------------------------------------------------------------------------------
+int score_candidates(ngm_mapper *m, int n, uint64_t np, int alt_dir);   // window gather + BatchScore of the batch's candidates into d_scores
+void argos_release(ngm_mapper *m);   // the --argos buffers (ngm_mapper_destroy)
 
 }  // namespace ngm

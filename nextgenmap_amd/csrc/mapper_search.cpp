@@ -51,6 +51,8 @@ size_t cs_lds_bytes(const CsArgs &A, int mode) {
 constexpr size_t kLdsLimit = 160 * 1024;      // of a CU (gfx950)
 constexpr int kLdsAttr = 150 * 1024;          // what hipFuncAttributeMaxDynamicSharedMemorySize is set to for the kernels sized at run time
 
+}  // namespace
+
 // NGM_HIP_TEST_LIMITS="key=value,key=value": small tables / pools so that the paths a GRCh38-sized genome takes -- table passes that
 // start over, reads that reach cs_global_kernel, crowded buckets in the order replay, a pool too small for a read -- run on a test
 // genome (tests/test_gpu_humanlike.py).  Never set in production; every key only makes a limit smaller.
@@ -66,6 +68,8 @@ long test_limit(const char *key, long dflt) {
 	}
 	return dflt;
 }
+
+namespace {
 
 // the classes of cs_heavy2_kernel: reads of up to max_hits index hits start in the class; counters, table slots, threads, survivors
 // the scratch slice holds, table passes a read may take (the largest class)

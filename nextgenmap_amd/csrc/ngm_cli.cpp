@@ -10,7 +10,8 @@
 //   buffered, ordered output         src/writer/GenericReadWriter.h:190-304 (20 MB buffer, flushed under the output lock)
 // Everything heavy (index, candidate search, score, align) happens on the GPU behind ngm_mapper_*.
 // Single-end and paired-end (-p -q interleaved, --qry1/--qry2), --affine, -n/--strata, SAM and BAM (--bam) output, one or
-// several GPUs (-g 0,1,...).  Not supported (rejected loudly): bisulfite / SLAM-seq, --argos, --vcf, SAM/BAM *input*.
+// several GPUs (-g 0,1,...), and --argos (ScoreWriter's lines, src/writer/ScoreWriter.cpp: every scored candidate of a read, ordered on the
+// GPU -- single-end only, see ngm_mapper_map_argos).  Not supported (rejected loudly): bisulfite / SLAM-seq, --vcf, SAM/BAM *input*.
 //
 // Pass 2 is a pipeline, not a loop:
 //   splitter (1 thread)   cuts the input into batches: for plain 4-line FASTQ it only counts line ends in the mapped file
@@ -124,6 +125,8 @@ struct Opts {
 	int device = 0, kmer = 13, kmer_skip = 2, bin_size = 2, mode = 0, corridor = -1, max_read_length = 0, min_mq = 0, max_kfreq = 0;
 	int match = 10, mismatch = 15, gap_read = -1, gap_ref = -1, gap_extend = -1, affine = 0, hard_clip = 0, silent_clip = 0, no_unal = 0, fast_pairing = 0, broken_pairs = 0, max_cmrs = 2147483647;
 	int skip_save = 0, bam = 0, workers = 2, serial_reader = 0;
+	int argos = 0, kmer_min_set = 0;
+	float argos_min = 0.f;   // --argos-min-score (Default(ARGOS_MINSCORE, 0), Config.cpp:505)
 	int bs_mapping = 0, bs_cutoff = 6, match_tt = -1, match_tc = -1, match_set = 0, mismatch_set = 0, slam_seq = 0;
 	std::vector<int> devices;
 	int shard_i = 0, shard_n = 1, shard_output = 0, keep_shards = 0;
@@ -144,7 +147,7 @@ Opts parse(int argc, char **argv) {
 	Opts o;
 	for (int i = 1; i < argc; ++i) { if (i > 1) o.cmdline += " "; o.cmdline += argv[i]; }  // Config.cpp:565-574
 	enum { KSKIP = 1000, HARD, SILENT, KMIN, MB, MMP, GRP, GFP, MAXCMRS, NOUNAL, NOPROG, MAXRL, BINSZ, MAXKF, VFAST, FAST, SENS, VSENS, DEVICE,
-		SKIPSAVE, BATCH, VARIANT, SHARD, SHARDOUT, KEEPSHARDS, BAMOUT, WORKERS, SERIAL, AFFINE, GEP, PEDELIM, STRATA, BSMAP, BSCUT, MBTT, MBTC, SLAM, FASTPAIR, BROKENPAIRS, REFSCOREBUF, STATSFD, RG0, RG_LAST = RG0 + 11, UNSUPPORTED };
+		SKIPSAVE, BATCH, VARIANT, SHARD, SHARDOUT, KEEPSHARDS, BAMOUT, WORKERS, SERIAL, AFFINE, GEP, PEDELIM, STRATA, BSMAP, BSCUT, MBTT, MBTC, SLAM, FASTPAIR, BROKENPAIRS, REFSCOREBUF, STATSFD, RG0, RG_LAST = RG0 + 11, ARGOS, ARGOSMIN, UNSUPPORTED };
 	static const option lo[] = {
 		{"ref", required_argument, 0, 'r'}, {"qry", required_argument, 0, 'q'}, {"output", required_argument, 0, 'o'},
 		{"cpu-threads", required_argument, 0, 't'}, {"gpu", no_argument, 0, 'g'}, {"sensitivity", required_argument, 0, 's'},
@@ -169,7 +172,7 @@ Opts parse(int argc, char **argv) {
 		{"affine", no_argument, 0, AFFINE}, {"gap-extend-penalty", required_argument, 0, GEP}, {"bam", no_argument, 0, BAMOUT}, {"workers", required_argument, 0, WORKERS}, {"serial-reader", no_argument, 0, SERIAL}, {"bs-mapping", no_argument, 0, BSMAP},
 		{"bs-cutoff", required_argument, 0, BSCUT}, {"match-bonus-tt", required_argument, 0, MBTT}, {"match-bonus-tc", required_argument, 0, MBTC},
 		{"slam-seq", required_argument, 0, SLAM}, {"topn", required_argument, 0, 'n'}, {"strata", no_argument, 0, STRATA},
-		{"argos", no_argument, 0, UNSUPPORTED}, {"vcf", required_argument, 0, UNSUPPORTED}, {"config", required_argument, 0, UNSUPPORTED},
+		{"argos", no_argument, 0, ARGOS}, {"argos-min-score", required_argument, 0, ARGOSMIN}, {"vcf", required_argument, 0, UNSUPPORTED}, {"config", required_argument, 0, UNSUPPORTED},
 		{0, 0, 0, 0}};
 	int c, idx = 0;
 	while ((c = getopt_long(argc, argv, "o:q:r:t:gs:k:lei:R:C:Q:p1:2:I:X:n:", lo, &idx)) != -1) {
@@ -204,7 +207,7 @@ Opts parse(int argc, char **argv) {
 		case 'Q': o.min_mq = atoi(optarg); break;
 		case HARD: o.hard_clip = 1; break;
 		case SILENT: o.silent_clip = 1; break;
-		case KMIN: o.kmer_min = (float) atof(optarg); break;
+		case KMIN: o.kmer_min = (float) atof(optarg); o.kmer_min_set = 1; break;
 		case MB: o.match = atoi(optarg); o.match_set = 1; break;
 		case MMP: o.mismatch = atoi(optarg); o.mismatch_set = 1; break;
 		case BSMAP: o.bs_mapping = 1; break;
@@ -247,11 +250,28 @@ Opts parse(int argc, char **argv) {
 		case REFSCOREBUF: o.ref_score_buffer = std::max(0, atoi(optarg)); break;
 		case STATSFD: o.stats_fd = atoi(optarg); break;
 		case BROKENPAIRS: o.broken_pairs = 1; break;
+		case ARGOS: o.argos = 1; break;
+		case ARGOSMIN: o.argos_min = (float) atof(optarg); break;
 		case UNSUPPORTED: die(std::string("option --") + lo[idx].name + " is not supported by the HIP backend yet");
 		default: die("unknown option (see src/config/Options.h of NextGenMap for the option set)");
 		}
 	}
 	if (o.ref.empty()) die("no reference given (-r/--ref)");
+	if (o.argos) {
+		// ScoreWriter has no paired or binary form (DoWritePair throws, src/writer/ScoreWriter.cpp:75-77); refused before any GPU work
+		if (!o.qry1.empty() || !o.qry2.empty()) die("--argos cannot be combined with --qry1/--qry2: the argos writer is single-end only (ScoreWriter::DoWritePair is not implemented)");
+		if (o.paired) die("--argos cannot be combined with -p/--paired: the argos writer is single-end only (ScoreWriter::DoWritePair is not implemented)");
+		if (o.bam) die("--argos cannot be combined with --bam: argos output is text lines, not SAM records");
+		if (o.shard_n > 1) die("--argos cannot be combined with --shard: the prolog's read count and the single output file belong to the whole input");
+		if (o.shard_output) die("--argos cannot be combined with --shard-output: the argos lines are written by one process in input order");
+		if (o.bs_mapping) die("--argos cannot be combined with --bs-mapping: that combination is not supported by the HIP backend");
+		if (o.slam_seq) die("--argos cannot be combined with --slam-seq: that combination is not supported by the HIP backend");
+		// Config.cpp:384-388, :517-520: kmer_min 2 and sensitivity 0 unless given; no selection, so -n / --strata / -Q / the identity and
+		// residue filters have no effect (ScoreBuffer.cpp:150-183 hands every scored read to the writer)
+		if (!o.kmer_min_set) o.kmer_min = 2.f;
+		if (o.sensitivity < 0) o.sensitivity = 0.f;
+		o.topn = 1; o.strata = 0; o.min_mq = 0;
+	}
 	if (!o.qry1.empty() && !o.qry2.empty()) o.paired = 1;  // Config.cpp:395-399
 	else if (!o.qry1.empty() || !o.qry2.empty()) die("--qry1 and --qry2 must be given together");
 	if (o.paired && o.topn > 1) die("Paired end mode with topn > 1 not yet supported.");  // ScoreBuffer::topNPE
@@ -822,7 +842,7 @@ int main(int argc, char **argv) {
 	{
 		const int early_topn = o.paired ? 1 : o.topn;
 		const bool early_gpu_bam = o.bam && !o.slam_seq && !getenv("NGM_HIP_BAM_ZLIB") && !getenv("NGM_HIP_BAM_HOST_RECORDS");
-		const bool early_gpu_sam = (!o.bam || early_gpu_bam) && early_topn == 1 && !o.broken_pairs && !getenv("NGM_HIP_HOST_SAM");
+		const bool early_gpu_sam = o.argos || ((!o.bam || early_gpu_bam) && early_topn == 1 && !o.broken_pairs && !getenv("NGM_HIP_HOST_SAM"));
 		const bool early_gpu_bgzf = o.bam && !early_gpu_sam && !getenv("NGM_HIP_BAM_ZLIB");
 		if ((early_gpu_sam || early_gpu_bgzf) && !(o.qry.empty() && o.qry1.empty()) && !o.out.empty()) {
 			size_t peek_max = 0;
@@ -908,6 +928,7 @@ int main(int argc, char **argv) {
 	FastqIndex ix0, ix1;
 	size_t max_len = 0, min_len = 9999999, sum_len = 0, count = 0;
 	std::vector<Read> sample;
+	size_t total_seqs = 0;
 	{
 		// reads without a sequence are not counted (parseRead returns 0 for them: the `if (l > 0)` of ReadProvider.cpp:236)
 		bool finish = false;
@@ -917,10 +938,11 @@ int main(int argc, char **argv) {
 			max_len = std::max(max_len, len); min_len = std::min(min_len, len); sum_len += len;
 			++count;
 			if (count % 1000 == 0 && count < 10000000) return true;
-			if (count == 10000001) { if (max_len - min_len >= 10) max_len = (size_t) (max_len * 1.1f); finish = true; }
+			if (count == 10000001) { if (o.argos || max_len - min_len >= 10) max_len = (size_t) (max_len * 1.1f); finish = true; }
 			return false;
 		};
 		bool plain_ok = plain;
+		bool scan_finished = false;
 		if (plain_ok) {
 			// both passes over a plain input are one parallel scan: record offsets for the splitter, lengths and the sample for the estimates
 			mf0.prefault(); mf1.prefault();
@@ -935,7 +957,8 @@ int main(int argc, char **argv) {
 				const std::string &le = !ix0.length_error.empty() ? ix0.length_error : ix1.length_error;
 				if (!le.empty()) die("Error while parsing read: sequence and quality lengths differ (" + le + ")");
 				max_len = ix0.max_len; min_len = ix0.min_len; sum_len = ix0.sum_len; count = ix0.count;
-				if (ix0.n_nonempty >= 10000001 && max_len - min_len >= 10) max_len = (size_t) (max_len * 1.1f);
+				if (ix0.n_nonempty >= 10000001 && (o.argos || max_len - min_len >= 10)) max_len = (size_t) (max_len * 1.1f);
+				scan_finished = ix0.n_nonempty >= 10000001;
 				sample = std::move(ix0.sample);
 			}
 		}
@@ -944,7 +967,10 @@ int main(int argc, char **argv) {
 			if (!in.ok()) die("cannot open " + first_input);
 			Read r;
 			while (!finish && in.next(r)) if (account(r.seq.size())) sample.push_back(r);
+			scan_finished = finish;
 		}
+		// NGM.Stats->TotalSeqs (the --argos prolog): the reads the scan counted, 0 when it stopped at the 10 000 001st (ReadProvider.cpp:252-279)
+		total_seqs = scan_finished ? 0 : count;
 	}
 	if (count == 0) die("No reads found in input file.");
 	if (o.max_read_length > 0) max_len = (size_t) o.max_read_length;
@@ -1079,7 +1105,15 @@ int main(int argc, char **argv) {
 			for (int t = 1; t < 12; ++t) if (!o.rg[t].empty()) { rg += "\t"; rg += tag[t]; rg += ":" + o.rg[t]; }
 			rg += "\n";
 		}
-		if (!o.bam) {
+		if (o.argos) {
+			// ScoreWriter::DoWriteProlog (ScoreWriter.cpp:19-35)
+			const int plen = ngm_argos_prolog(ref, total_seqs, nullptr, 0);
+			if (plen < 0) die(ngm_pipeline_last_error());
+			std::string pro((size_t) plen, '\0');
+			if (ngm_argos_prolog(ref, total_seqs, &pro[0], pro.size()) != plen) die(ngm_pipeline_last_error());
+			if (!put_all(pro.data(), pro.size(), out_off)) die("write error on " + o.out);
+			out_off += pro.size();
+		} else if (!o.bam) {
 			for (size_t i = 0; i < contig_names.size(); ++i) { h += "@SQ\tSN:" + contig_names[i] + "\tLN:"; put_u64(h, contig_lens[i]); h += "\n"; }
 			h += "@PG\tID:ngm\tPN:ngm\tVN:0.5.5-hip\tCL:\"" + o.cmdline + "\"\n";
 			h += rg;
@@ -1120,7 +1154,7 @@ int main(int argc, char **argv) {
 	// --broken-pairs or SLAM-seq tags the records are formatted here and only the blocks come from the GPU
 	// (NGM_HIP_BAM_HOST_RECORDS=1 forces that; NGM_HIP_BAM_ZLIB=1: records here, zlib level 6 on the pool -- the round-3 path)
 	const bool gpu_bam = o.bam && !o.slam_seq && !getenv("NGM_HIP_BAM_ZLIB") && !getenv("NGM_HIP_BAM_HOST_RECORDS");
-	const bool gpu_sam = (!o.bam || gpu_bam) && topn == 1 && !o.broken_pairs && !getenv("NGM_HIP_HOST_SAM");
+	const bool gpu_sam = o.argos || ((!o.bam || gpu_bam) && topn == 1 && !o.broken_pairs && !getenv("NGM_HIP_HOST_SAM"));   // (--argos: its lines only come from the GPU)
 	const bool gpu_bgzf = o.bam && !gpu_sam && !getenv("NGM_HIP_BAM_ZLIB");
 	std::atomic<long long> t_bgzf_gpu_us{0}, t_bgzf_call_us{0};
 	std::atomic<unsigned long long> bgzf_in_bytes{0}, bgzf_out_bytes{0};
@@ -1133,7 +1167,9 @@ int main(int argc, char **argv) {
 		if (!workers[w].m) die(ngm_pipeline_last_error());
 		ngm_mapper_set_pair_state(workers[w].m, pair_state);
 		ngm_mapper_set_fast_pairing(workers[w].m, o.fast_pairing);
-		if (gpu_sam) {
+		if (o.argos) {
+			if (ngm_mapper_set_argos(workers[w].m, o.argos_min) < 0) die(ngm_pipeline_last_error());
+		} else if (gpu_sam) {
 			ngm_sam_options so{};
 			so.paired = o.paired; so.min_insert_size = o.min_insert; so.max_insert_size = o.max_insert; so.min_mq = o.min_mq;
 			so.min_identity = o.min_identity; so.min_residues = o.min_residues; so.no_unal = o.no_unal; so.rg_id = o.rg[0].empty() ? nullptr : o.rg[0].c_str(); so.bs_mapping = o.bs_mapping; so.slam_seq = o.slam_seq; so.bam = o.bam ? 1 : 0;
@@ -1694,7 +1730,8 @@ int main(int argc, char **argv) {
 				}
 				uint64_t st[3] = {0, 0, 0};
 				float sam_ms = 0.f;
-				long long len = ngm_mapper_map_sam(w.m, n, w.rows, w.qrows, w.names, total, w.meta, tb.p, tb.cap, st, &sam_ms);
+				long long len = o.argos ? ngm_mapper_map_argos(w.m, n, w.rows, w.names, total, w.meta, tb.p, tb.cap, st, &sam_ms)
+				                        : ngm_mapper_map_sam(w.m, n, w.rows, w.qrows, w.names, total, w.meta, tb.p, tb.cap, st, &sam_ms);
 				if (len > (long long) tb.cap) {  // (long CIGAR / MD strings: a larger buffer for this batch)
 					ngm_host_free(tb.p);
 					tb.cap = (size_t) len + (1u << 20);
@@ -1939,6 +1976,19 @@ int main(int argc, char **argv) {
 		}
 		snprintf(msg, sizeof(msg), "Pool thread time inside the stages, s: parse + pack %.3f | format %.3f | output copies %.3f (writer wall %.3f)",
 				t_parse_cpu_us / 1e6, t_format_cpu_us / 1e6, t_write_cpu_us / 1e6, t_write_us / 1e6);
+		info("MAIN", msg);
+	}
+	if (o.argos) {
+		uint64_t ac[4] = {0, 0, 0, 0}, ap[2] = {0, 0};
+		for (Worker &w : workers) {
+			uint64_t c4[4], c2[2];
+			if (ngm_mapper_argos_counters(w.m, c4) == 0) for (int x = 0; x < 4; ++x) ac[x] += c4[x];
+			if (ngm_mapper_argos_path_counters(w.m, c2) == 0) for (int x = 0; x < 2; ++x) ap[x] += c2[x];
+		}
+		const double nl = (double) std::max<uint64_t>(1, ac[0] + ac[1] + ac[2]);
+		snprintf(msg, sizeof(msg), "Argos order classes: U %llu (%.3f %%), S %llu (%.3f %%), H %llu (%.3f %%); %llu entries written; long-list path %llu reads; order by position (candidate order unknown) %llu reads",
+				(unsigned long long) ac[0], 100.0 * ac[0] / nl, (unsigned long long) ac[1], 100.0 * ac[1] / nl, (unsigned long long) ac[2], 100.0 * ac[2] / nl,
+				(unsigned long long) ac[3], (unsigned long long) ap[0], (unsigned long long) ap[1]);
 		info("MAIN", msg);
 	}
 	{

@@ -71,6 +71,15 @@ def _lib():
         lib.ngm_mapper_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         lib.ngm_mapper_last_order_replay_ms.restype = C.c_float
         lib.ngm_mapper_last_order_replay_ms.argtypes = [C.c_void_p]
+        lib.ngm_mapper_set_argos.argtypes = [C.c_void_p, C.c_float]
+        lib.ngm_mapper_map_argos.restype = C.c_longlong
+        lib.ngm_mapper_map_argos.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
+                                             C.c_void_p, C.POINTER(C.c_float)]
+        lib.ngm_mapper_sam_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.ngm_argos_prolog.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t]
+        lib.ngm_mapper_argos_counters.argtypes = [C.c_void_p, C.c_void_p]
+        lib.ngm_mapper_argos_path_counters.argtypes = [C.c_void_p, C.c_void_p]
+        lib.ngm_debug_argos_order.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         lib.ngm_bgzf_create.restype = C.c_void_p
         lib.ngm_bgzf_create.argtypes = [C.c_int]
         lib.ngm_bgzf_destroy.argtypes = [C.c_void_p]
@@ -213,6 +222,16 @@ class Reference:
             raise _err()
         return bool(r), bytes(out)
 
+    def argos_prolog(self, total_reads):
+        """ScoreWriter::DoWriteProlog for this reference (ngm_argos_prolog)"""
+        lib = _lib()
+        n = lib.ngm_argos_prolog(self.h, total_reads, None, 0)
+        if n < 0:
+            raise _err()
+        buf = C.create_string_buffer(n + 1)
+        lib.ngm_argos_prolog(self.h, total_reads, buf, n + 1)
+        return buf.raw[:n]
+
     def convert(self, pos):
         c, p = C.c_int(0), C.c_uint64(0)
         ok = self.lib.ngm_ref_convert(self.h, pos, C.byref(c), C.byref(p))
@@ -333,6 +352,47 @@ class Mapper:
         out = np.zeros(1, np.uint64)
         self.lib.ngm_mapper_order_table_reads(self.h, out.ctypes.data)
         return int(out[0])
+
+    def map_argos(self, reads, names, min_score=0.0):
+        """`--argos` for one batch (ngm_mapper_map_argos): reads -- rows as from reads_to_rows, or a list of sequences --, names -- one
+        per read (bytes or str) --, min_score: --argos-min-score (< 0: the mode off again).  Returns ScoreWriter's text for these reads
+        (bytes: one line per read with candidates) and the stats (reads, reads with a line, 0)."""
+        rows = reads if isinstance(reads, np.ndarray) else self.reads_to_rows(reads, self.q)
+        rows = np.ascontiguousarray(rows, dtype=np.uint8)
+        n = rows.shape[0]
+        if len(names) != n:
+            raise ValueError("one name per read")
+        if self.lib.ngm_mapper_set_argos(self.h, float(min_score)) < 0:
+            raise _err()
+        nb = [x.encode() if isinstance(x, str) else bytes(x) for x in names]
+        meta = np.zeros((n, 2), np.uint32)   # ngm_sam_read: name_off, name_len (qual_len unused)
+        off = 0
+        for i, b in enumerate(nb):
+            meta[i, 0], meta[i, 1] = off, min(len(b), 0xFFFF)
+            off += len(b)
+        blob = np.frombuffer(b"".join(nb) + b"\0", np.uint8)
+        stats = np.zeros(3, np.uint64)
+        kms = C.c_float(0)
+        cap = max(1 << 16, n * 64)
+        out = np.zeros(cap, np.uint8)
+        total = self.lib.ngm_mapper_map_argos(self.h, n, rows.ctypes.data, blob.ctypes.data, off, meta.ctypes.data, out.ctypes.data, cap,
+                                              stats.ctypes.data, C.byref(kms))
+        if total < 0:
+            raise _err()
+        if total > cap:
+            out = np.zeros(total, np.uint8)
+            if self.lib.ngm_mapper_sam_fetch(self.h, out.ctypes.data, total) < 0:
+                raise _err()
+        return out[:total].tobytes(), [int(x) for x in stats]
+
+    def argos_counters(self):
+        """summed over the map_argos calls: reads ordered in class U / S / H, entries written, reads of the long-list path, reads of class
+        S / H ordered by position (candidate order unknown)"""
+        out = np.zeros(4, np.uint64)
+        self.lib.ngm_mapper_argos_counters(self.h, out.ctypes.data)
+        p = np.zeros(2, np.uint64)
+        self.lib.ngm_mapper_argos_path_counters(self.h, p.ctypes.data)
+        return dict(zip(("U", "S", "H", "entries", "long_list", "unknown_order"), [int(x) for x in out] + [int(x) for x in p]))
 
     def cs_counters(self):
         """(k-mers looked up, index hits voted, candidates) of the last candidate search."""
