@@ -48,6 +48,17 @@ ngm_ref *ngm_ref_create_from_fasta(int device, const ngm_ref_params *p, const ch
 ngm_ref *ngm_ref_create_from_cache(int device, const ngm_ref_params *params, const char *fasta_path);
 /* 1 when the reference came from those cache files (a corrupt / mismatching cache falls back to a build: the caller rewrites it) */
 int ngm_ref_loaded_from_cache(const ngm_ref *r);
+/* --vcf FILE (PrefixTable.cpp:223-228, :500-574): the index also holds the k-mers of the VCF's variants, built like the reference
+ * builds them -- lists in genome order then VCF order, and the zero slots the reference leaves where its fill pass stores less than
+ * its count pass reserved.  Plain or gzip VCF.  An existing cache is loaded as it is and the VCF is not read (like the reference);
+ * an unreadable VCF, or a variant whose region would start before position 0 or past the end of the genome, is an error (the
+ * reference goes on without variants, or reads outside its buffers). */
+ngm_ref *ngm_ref_create_from_fasta_vcf(int device, const ngm_ref_params *params, const char *fasta_path, const char *vcf_path);
+/* out: variations loaded, SNPs, indels, ignored (the `Loaded VCF` / `Built SNP region table` lines), region entries stored, zero
+ * slots.  Returns 1 when the index was built with a VCF, 0 when not (no VCF, or loaded from a cache), < 0 on a bad argument. */
+int ngm_ref_vcf_summary(const ngm_ref *r, uint64_t out[6]);
+/* the reference's skipCount and skipBuild of a build with a VCF (they differ where the zero slots come from); return as above */
+int ngm_ref_vcf_skip_counts(const ngm_ref *r, uint64_t out[2]);
 void ngm_ref_destroy(ngm_ref *r);
 
 int ngm_ref_contig_count(const ngm_ref *r);

@@ -11,7 +11,7 @@
 // Everything heavy (index, candidate search, score, align) happens on the GPU behind ngm_mapper_*.
 // Single-end and paired-end (-p -q interleaved, --qry1/--qry2), --affine, -n/--strata, SAM and BAM (--bam) output, one or
 // several GPUs (-g 0,1,...), and --argos (ScoreWriter's lines, src/writer/ScoreWriter.cpp: every scored candidate of a read, ordered on the
-// GPU -- single-end only, see ngm_mapper_map_argos).  Not supported (rejected loudly): bisulfite / SLAM-seq, --vcf, SAM/BAM *input*.
+// GPU -- single-end only, see ngm_mapper_map_argos).  Not supported (rejected loudly): bisulfite / SLAM-seq, --vcf with --bs-mapping, SAM/BAM *input*.
 //
 // Pass 2 is a pipeline, not a loop:
 //   splitter (1 thread)   cuts the input into batches: for plain 4-line FASTQ it only counts line ends in the mapped file
@@ -119,7 +119,7 @@ private:
 };
 
 struct Opts {
-	std::string ref, qry, qry1, qry2, out;
+	std::string ref, qry, qry1, qry2, out, vcf;
 	int paired = 0, min_insert = 0, max_insert = 1000, topn = 1, strata = 0;
 	char pe_delimiter = '/';
 	int device = 0, kmer = 13, kmer_skip = 2, bin_size = 2, mode = 0, corridor = -1, max_read_length = 0, min_mq = 0, max_kfreq = 0;
@@ -147,7 +147,7 @@ Opts parse(int argc, char **argv) {
 	Opts o;
 	for (int i = 1; i < argc; ++i) { if (i > 1) o.cmdline += " "; o.cmdline += argv[i]; }  // Config.cpp:565-574
 	enum { KSKIP = 1000, HARD, SILENT, KMIN, MB, MMP, GRP, GFP, MAXCMRS, NOUNAL, NOPROG, MAXRL, BINSZ, MAXKF, VFAST, FAST, SENS, VSENS, DEVICE,
-		SKIPSAVE, BATCH, VARIANT, SHARD, SHARDOUT, KEEPSHARDS, BAMOUT, WORKERS, SERIAL, AFFINE, GEP, PEDELIM, STRATA, BSMAP, BSCUT, MBTT, MBTC, SLAM, FASTPAIR, BROKENPAIRS, REFSCOREBUF, STATSFD, RG0, RG_LAST = RG0 + 11, ARGOS, ARGOSMIN, UNSUPPORTED };
+		SKIPSAVE, BATCH, VARIANT, SHARD, SHARDOUT, KEEPSHARDS, BAMOUT, WORKERS, SERIAL, AFFINE, GEP, PEDELIM, STRATA, BSMAP, BSCUT, MBTT, MBTC, SLAM, FASTPAIR, BROKENPAIRS, REFSCOREBUF, STATSFD, RG0, RG_LAST = RG0 + 11, ARGOS, ARGOSMIN, VCF, UNSUPPORTED };
 	static const option lo[] = {
 		{"ref", required_argument, 0, 'r'}, {"qry", required_argument, 0, 'q'}, {"output", required_argument, 0, 'o'},
 		{"cpu-threads", required_argument, 0, 't'}, {"gpu", no_argument, 0, 'g'}, {"sensitivity", required_argument, 0, 's'},
@@ -172,7 +172,7 @@ Opts parse(int argc, char **argv) {
 		{"affine", no_argument, 0, AFFINE}, {"gap-extend-penalty", required_argument, 0, GEP}, {"bam", no_argument, 0, BAMOUT}, {"workers", required_argument, 0, WORKERS}, {"serial-reader", no_argument, 0, SERIAL}, {"bs-mapping", no_argument, 0, BSMAP},
 		{"bs-cutoff", required_argument, 0, BSCUT}, {"match-bonus-tt", required_argument, 0, MBTT}, {"match-bonus-tc", required_argument, 0, MBTC},
 		{"slam-seq", required_argument, 0, SLAM}, {"topn", required_argument, 0, 'n'}, {"strata", no_argument, 0, STRATA},
-		{"argos", no_argument, 0, ARGOS}, {"argos-min-score", required_argument, 0, ARGOSMIN}, {"vcf", required_argument, 0, UNSUPPORTED}, {"config", required_argument, 0, UNSUPPORTED},
+		{"argos", no_argument, 0, ARGOS}, {"argos-min-score", required_argument, 0, ARGOSMIN}, {"vcf", required_argument, 0, VCF}, {"config", required_argument, 0, UNSUPPORTED},
 		{0, 0, 0, 0}};
 	int c, idx = 0;
 	while ((c = getopt_long(argc, argv, "o:q:r:t:gs:k:lei:R:C:Q:p1:2:I:X:n:", lo, &idx)) != -1) {
@@ -251,6 +251,7 @@ Opts parse(int argc, char **argv) {
 		case STATSFD: o.stats_fd = atoi(optarg); break;
 		case BROKENPAIRS: o.broken_pairs = 1; break;
 		case ARGOS: o.argos = 1; break;
+		case VCF: o.vcf = optarg; break;
 		case ARGOSMIN: o.argos_min = (float) atof(optarg); break;
 		case UNSUPPORTED: die(std::string("option --") + lo[idx].name + " is not supported by the HIP backend yet");
 		default: die("unknown option (see src/config/Options.h of NextGenMap for the option set)");
@@ -276,6 +277,19 @@ Opts parse(int argc, char **argv) {
 	else if (!o.qry1.empty() || !o.qry2.empty()) die("--qry1 and --qry2 must be given together");
 	if (o.paired && o.topn > 1) die("Paired end mode with topn > 1 not yet supported.");  // ScoreBuffer::topNPE
 	if (o.paired && o.qry.empty() && o.qry1.empty()) die("-p/--paired needs -q (interleaved mates) or --qry1/--qry2");
+	if (!o.vcf.empty()) {
+		// (the reference builds a bisulfite index with the VCF's k-mers unconverted; that combination is not restated here)
+		if (o.bs_mapping) die("--vcf cannot be combined with --bs-mapping: that combination is not supported by the HIP backend");
+		// an index built with a VCF holds lists out of genome order, repeated positions and zero slots (refindex.h); the modes below are
+		// not yet checked against the reference with such an index and are refused rather than run unchecked.  --argos would print
+		// the candidates of the zero slots, where the reference's convert() reads past its contig table (SequenceProvider.cpp:115-119)
+		const char *why = o.argos ? "--argos" : o.bam ? "--bam" : o.topn > 1 ? "-n/--topn above 1" : o.mode == 1 ? "-e/--end-to-end" :
+				o.devices.size() > 1 ? "several GPUs (-g a,b,..)" : o.shard_output ? "--shard-output" : o.shard_n > 1 ? "--shard" : o.bin_size < 2 ? "--bin-size below 2" : nullptr;
+		if (why) die(std::string("--vcf cannot be combined with ") + why + ": that combination is not supported by the HIP backend yet");
+		gzFile vf = gzopen(o.vcf.c_str(), "rb");  // before any GPU work (the reference logs an unreadable VCF and goes on without it)
+		if (!vf) die("Failed to open VCF file " + o.vcf);
+		gzclose(vf);
+	}
 	// scoring defaults depend on the personality (Config.cpp:433-470)
 	if (o.bs_mapping) {
 		info("MAIN", "Using bs-mapping scoring scheme");
@@ -883,13 +897,28 @@ int main(int argc, char **argv) {
 	// an index cache next to the FASTA is loaded instead of rebuilding; a fresh build is saved for the next run unless
 	// --skip-save (src/PrefixTable.cpp:232-262, SequenceProvider.cpp:264-330)
 	const std::string ht_cache = o.ref + "-ht-" + std::to_string(o.kmer) + "-" + std::to_string(rp.kmer_skip) + ".3.ngm";
-	ngm_ref *ref = ngm_ref_create_from_fasta(o.device, &rp, o.ref.c_str());
+	ngm_ref *ref = o.vcf.empty() ? ngm_ref_create_from_fasta(o.device, &rp, o.ref.c_str()) : ngm_ref_create_from_fasta_vcf(o.device, &rp, o.ref.c_str(), o.vcf.c_str());
 	if (!ref) die(ngm_pipeline_last_error());
 	const bool had_cache = ngm_ref_loaded_from_cache(ref) != 0;  // (an unreadable or corrupt cache was rebuilt and is rewritten below)
 	if (had_cache) info("PREPROCESS", "Reading reference index from " + ht_cache);
 	else if (!o.skip_save) {
 		if (ngm_ref_write_ngm_cache(ref, o.ref.c_str()) < 0) info("PREPROCESS", std::string("could not save the index: ") + ngm_pipeline_last_error());
 		else info("PREPROCESS", "Writing reference index to " + ht_cache);
+	}
+	if (!o.vcf.empty()) {
+		uint64_t vs[6] = {0, 0, 0, 0, 0, 0}, sk[2] = {0, 0};
+		if (ngm_ref_vcf_summary(ref, vs) == 1) {
+			char m[200];
+			snprintf(m, sizeof(m), "Loaded VCF (%llu variations)", (unsigned long long) vs[0]); info("PREPROCESS", m);
+			snprintf(m, sizeof(m), "Built SNP region table (%llu SNPs, %llu indels, %llu ignored)", (unsigned long long) vs[1], (unsigned long long) vs[2], (unsigned long long) vs[3]);
+			info("PREPROCESS", m);
+			// PrefixTable.cpp:439-443, its two arguments swapped as there
+			if (ngm_ref_vcf_skip_counts(ref, sk) == 1 && sk[0] != sk[1]) {
+				snprintf(m, sizeof(m), "\tSkipBuild (%llu) != SkipCount (%llu)", (unsigned long long) sk[0], (unsigned long long) sk[1]); info("PREPROCESS", m);
+			}
+		} else if (had_cache) {
+			info("PREPROCESS", "--vcf " + o.vcf + " not applied: the index is loaded from the existing cache " + ht_cache + " as it is (delete it to rebuild with the VCF)");
+		}
 	}
 	// the layout the candidate search gathers from (canonical pair buckets) belongs to the preparation of the reference, not to the first batch
 	if (ngm_ref_prepare_search(ref, o.bs_mapping) < 0) die(ngm_pipeline_last_error());

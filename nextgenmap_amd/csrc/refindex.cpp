@@ -22,6 +22,8 @@
 #include <rocprim/rocprim.hpp>
 #include <zlib.h>
 
+namespace ngm { long test_limit(const char *key, long dflt); }  // NGM_HIP_TEST_LIMITS (mapper_search.cpp)
+
 namespace {
 thread_local std::string g_pipeline_error;
 
@@ -54,8 +56,10 @@ struct KmerWalker {
 	uint32_t last_prefix;
 	int64_t last_bin;
 	std::vector<uint32_t> *keys, *vals;
+	uint64_t visited = 0;
 
 	void fire(uint32_t prefix, uint64_t pos) {
+		++visited;
 		// same k-mer as the previous indexed one AND same bin as the previous same-k-mer hit -> dropped
 		if (prefix == last_prefix) {
 			const int64_t bin = (int64_t) (pos >> bin_shift);
@@ -216,7 +220,10 @@ __global__ void walk_store_flags_kernel(const uint32_t *__restrict__ pos, const 
 }
 
 // -> d_keys / d_vals (device, n entries, genome order).  Returns 0 or a negative error.
-int gpu_kmer_walk(ngm_ref *r, uint32_t **d_keys_out, uint32_t **d_vals_out, uint64_t *n_out) {
+// carried walk state (CompactPrefixTable::lastPrefix / lastBin) after the last contig, and the visited k-mer count: --vcf needs both
+struct WalkEnd { uint64_t visited = 0; uint32_t last_prefix = 111111u; int64_t last_bin = -1; };
+
+int gpu_kmer_walk(ngm_ref *r, uint32_t **d_keys_out, uint32_t **d_vals_out, uint64_t *n_out, WalkEnd *end) {
 	const uint64_t n = r->n_bases;
 	const int k = r->prm.kmer, nc = (int) r->contigs.size();
 	std::vector<uint64_t> hs(nc), he(nc);
@@ -265,11 +272,337 @@ int gpu_kmer_walk(ngm_ref *r, uint32_t **d_keys_out, uint32_t **d_vals_out, uint
 		REF_HIP_TRY(rocprim::select(d_tmp, tb, d_keys, d_flag, d_keys2, d_count, (size_t) m));
 		REF_HIP_TRY(rocprim::select(d_tmp, tb, d_pos, d_flag, d_pos2, d_count, (size_t) m));
 		REF_HIP_TRY(hipMemcpy(&kept, d_count, 8, hipMemcpyDeviceToHost));
+		if (end && nc > 0) {  // the state the last contig's walk leaves behind: from its last two visited k-mers
+			uint32_t lk[2] = {0, 0}, lp[2] = {0, 0};
+			const uint64_t t = m >= 2 ? m - 2 : 0, cnt = m - t;
+			REF_HIP_TRY(hipMemcpy(lk, d_keys + t, cnt * 4, hipMemcpyDeviceToHost));
+			REF_HIP_TRY(hipMemcpy(lp, d_pos + t, cnt * 4, hipMemcpyDeviceToHost));
+			const uint64_t last_start = hs[nc - 1];
+			const int in_last = (cnt >= 1 && lp[cnt - 1] >= last_start) + (cnt >= 2 && lp[0] >= last_start);
+			if (in_last >= 1) {
+				const uint32_t k1 = lk[cnt - 1], k0 = in_last == 2 ? lk[0] : 111111u;
+				end->last_prefix = k1;
+				end->last_bin = k1 == k0 ? (int64_t) (lp[cnt - 1] >> r->prm.bin_size) : -1;
+			}
+		}
 	}
+	if (end) end->visited = m;
 	cleanup();
 	(void) hipFree(d_pos); (void) hipFree(d_keys);
 	done = true;
 	*d_keys_out = d_keys2; *d_vals_out = d_pos2; *n_out = kept;
+	return 0;
+}
+
+
+// ---- --vcf: the k-mers of known variants (PrefixTable.cpp:500-574 BuildSNPTable, counted at :360-374, filled at :411-422) -------
+// Every kept variant gives a region: the reference around it with the ALT spliced in, walked like a contig at positions
+// ref_offset + i.  The count pass resets the walk state per region, the fill pass does not (its state comes from the last contig
+// and from the region before): a k-mer list gets the count pass's number of slots, the fill pass's entries first (genome order,
+// then VCF order) and zeros in the rest.  The first contig starts at 1000 and a region reaches at most k + |REF| + |ALT| - 2 bases
+// to the left, which build_vcf_entries checks (the reference's unsigned underflow is not restated).
+enum : uint8_t { kVarIgnored = 0, kVarSnp = 1, kVarIndel = 2, kVarBad = 3 };
+constexpr uint32_t kVarX = 8;  // DecodeRefSequence's 'x' filler (never equal to a VCF base; encode('x') == 0 in the walk)
+
+__host__ __device__ __forceinline__ uint32_t vcf_class_of(char c) {
+	return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 5u;  // (the reader keeps ACGTN only)
+}
+// DecodeRefSequence(buffer, 0, off, region_len) (SequenceProvider.cpp:382-441): region_len - 2 bases from off, a last odd one and
+// everything past the concatenated genome's end read as 'x'; an odd offset brings one base more
+struct VcfGeom {
+	uint64_t off; uint32_t d, dlen, b; bool x_last;
+	__device__ VcfGeom(uint64_t pos, uint32_t half, uint64_t concat) {
+		off = pos - half;
+		uint64_t len = 2ull * half - 2, end = 0;
+		if (off + len > concat) { end = off + len - concat; len -= end; }
+		d = (uint32_t) ((off & 1) + 2 * ((len + 1) / 2));
+		x_last = (len & 1) != 0;
+		dlen = d + (uint32_t) end;
+		b = half - 1;  // buffer_snp_pos
+	}
+	__device__ uint32_t cls(const uint32_t *g, uint32_t t) const { return (t >= d || (x_last && t == d - 1)) ? kVarX : d_class_at(g, off + t); }
+};
+__device__ __forceinline__ uint32_t vcf_half(const NgmVariant &v, int k) { return (uint32_t) k + v.ref_len + v.alt_len - 2; }
+
+// one thread per variant: what BuildSNPTable does with it, and the length of its region; the first indel whose REF does not match
+// the genome ends the table (the `break` at PrefixTable.cpp:553-554)
+__global__ void vcf_classify_kernel(const NgmVariant *__restrict__ var, uint64_t n, const char *__restrict__ seq, const uint32_t *__restrict__ genome,
+		uint64_t concat, int k, uint8_t *__restrict__ status, uint64_t *__restrict__ len, unsigned long long *__restrict__ first_bad) {
+	const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	const NgmVariant v = var[i];
+	const VcfGeom g(v.pos, vcf_half(v, k), concat);
+	uint8_t st;
+	uint64_t l = 0;
+	if (v.ref_len == 1 && v.alt_len == 1) {  // a SNP's REF is never looked at
+		st = g.cls(genome, g.b) == vcf_class_of(seq[v.alt_off]) ? kVarIgnored : kVarSnp;
+		if (st == kVarSnp) l = g.dlen;
+	} else {
+		st = (uint64_t) g.b + v.ref_len <= g.dlen ? kVarIndel : kVarBad;
+		for (uint32_t t = 0; t < v.ref_len && st == kVarIndel; ++t)
+			if (g.cls(genome, g.b + t) != vcf_class_of(seq[v.ref_off + t])) st = kVarBad;
+		if (st == kVarIndel) l = (uint64_t) g.dlen - v.ref_len + v.alt_len;
+		else atomicMin(first_bad, (unsigned long long) i);
+	}
+	status[i] = st;
+	len[i] = l;
+}
+// regions after the first bad indel are dropped; counts for `Built SNP region table`: SNPs, indels, ignored
+__global__ void vcf_cut_kernel(uint64_t n, const unsigned long long *__restrict__ first_bad, const uint8_t *__restrict__ status, uint64_t *__restrict__ len,
+		unsigned long long *__restrict__ counts) {
+	const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	if (i >= *first_bad) { len[i] = 0; return; }
+	atomicAdd(&counts[status[i] == kVarSnp ? 0 : status[i] == kVarIndel ? 1 : 2], 1ull);
+}
+// region bytes (classes, 'x' as A) at the exclusive scan of the lengths
+__global__ void vcf_fill_kernel(const NgmVariant *__restrict__ var, uint64_t n, const char *__restrict__ seq, const uint32_t *__restrict__ genome,
+		uint64_t concat, int k, const uint64_t *__restrict__ len, const uint64_t *__restrict__ roff, uint8_t *__restrict__ out) {
+	const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n || len[i] == 0) return;
+	const NgmVariant v = var[i];
+	const VcfGeom g(v.pos, vcf_half(v, k), concat);
+	uint8_t *o = out + roff[i];
+	auto put = [&](uint32_t c) { *o++ = (uint8_t) (c == kVarX ? 0u : c); };
+	if (v.ref_len == 1 && v.alt_len == 1) {
+		for (uint32_t t = 0; t < g.dlen; ++t) put(t == g.b ? vcf_class_of(seq[v.alt_off]) : g.cls(genome, t));
+	} else {
+		for (uint32_t t = 0; t < g.b; ++t) put(g.cls(genome, t));
+		for (uint32_t t = 0; t < v.alt_len; ++t) put(vcf_class_of(seq[v.alt_off + t]));
+		for (uint32_t t = g.b + v.ref_len; t < g.dlen; ++t) put(g.cls(genome, t));
+	}
+}
+
+// CS::PrefixIteration (CSstatic.cpp:26-76) over one region, calling f(prefix, position) for every VISITED k-mer -- KmerWalker::iterate
+// without the store rule, for the host and the device
+template <class F>
+__host__ __device__ inline void vcf_walk_region(const uint8_t *seq, uint64_t length, uint64_t offset, int k, int skip, uint32_t mask, F &f) {
+	for (;;) {
+		if (length < (uint64_t) k) return;
+		if (seq[0] == 5) {
+			uint64_t n_skip = 1;
+			while (n_skip < length && seq[n_skip] == 5) ++n_skip;
+			seq += n_skip;
+			if (n_skip >= (length - k)) return;  // CSstatic.cpp:37
+			length -= n_skip;
+			offset += n_skip;
+		}
+		uint32_t prefix = 0;
+		bool restart = false;
+		for (uint64_t i = 0; i < (uint64_t) k - 1; ++i) {
+			if (seq[i] == 5) { seq += i + 1; length -= i + 1; offset += i + 1; restart = true; break; }
+			prefix = (prefix << 2) | (seq[i] == 2 ? 3u : seq[i] == 3 ? 2u : (uint32_t) seq[i]);
+		}
+		if (restart) continue;
+		int skipcount = skip;
+		for (uint64_t i = k - 1; i < length; ++i) {
+			if (seq[i] == 5) { seq += i + 1; length -= i + 1; offset += i + 1; restart = true; break; }
+			prefix = ((prefix << 2) | (seq[i] == 2 ? 3u : seq[i] == 3 ? 2u : (uint32_t) seq[i])) & mask;
+			if (skipcount == skip) { f(prefix, offset + i + 1 - k); skipcount = 0; }
+			else ++skipcount;
+		}
+		if (!restart) return;
+	}
+}
+// one thread per region: the number of visited k-mers (WRITE = false), or the k-mers themselves at their offset
+template <bool WRITE>
+__global__ void vcf_walk_kernel(const NgmVariant *__restrict__ var, uint64_t n, int k, int skip, const uint64_t *__restrict__ len,
+		const uint64_t *__restrict__ roff, const uint8_t *__restrict__ regions, uint64_t *__restrict__ vcount, const uint64_t *__restrict__ voff,
+		uint32_t *__restrict__ keys, uint32_t *__restrict__ pos, uint32_t *__restrict__ reg) {
+	const uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= n) return;
+	if (len[i] == 0) { if (!WRITE) vcount[i] = 0; return; }
+	const NgmVariant v = var[i];
+	const uint64_t off = v.pos - vcf_half(v, k);
+	const uint32_t mask = (1u << (2 * k)) - 1u;
+	if (!WRITE) {
+		uint64_t c = 0;
+		auto f = [&](uint32_t, uint64_t) { ++c; };
+		vcf_walk_region(regions + roff[i], len[i], off, k, skip, mask, f);
+		vcount[i] = c;
+	} else {
+		uint64_t o = voff[i];
+		auto f = [&](uint32_t p, uint64_t q) { keys[o] = p; pos[o] = (uint32_t) q; reg[o] = (uint32_t) i; ++o; };
+		vcf_walk_region(regions + roff[i], len[i], off, k, skip, mask, f);
+	}
+}
+// the store rule (CountKmer / BuildPrefixTable, PrefixTable.cpp:641-709) of visited region k-mer j under both passes: the state before
+// j follows from the two visited k-mers before it -- within its region for the count flag (bit 0), across regions and from the
+// genome's end state (cp, cb) for the fill flag (bit 1)
+__global__ void vcf_store_flags_kernel(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ pos, const uint32_t *__restrict__ reg, uint64_t m,
+		int bin_shift, uint32_t cp, long long cb, uint8_t *__restrict__ cflag, uint8_t *__restrict__ fflag) {
+	const uint64_t j = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
+	if (j >= m) return;
+	const long long bin = (long long) (pos[j] >> bin_shift);
+	auto store = [&](uint32_t lp, long long lb) { return keys[j] != lp || lb == -1 || bin != lb; };
+	const bool first = j == 0 || reg[j - 1] != reg[j];
+	{
+		uint32_t lp = 111111u; long long lb = -1;
+		if (!first) {
+			lp = keys[j - 1];
+			const bool first1 = j - 1 == 0 || reg[j - 2] != reg[j - 1];
+			lb = keys[j - 1] == (first1 ? 111111u : keys[j - 2]) ? (long long) (pos[j - 1] >> bin_shift) : -1;
+		}
+		cflag[j] = store(lp, lb) ? 1 : 0;
+	}
+	{
+		uint32_t lp = cp; long long lb = cb;
+		if (j > 0) {
+			lp = keys[j - 1];
+			lb = keys[j - 1] == (j - 1 == 0 ? cp : keys[j - 2]) ? (long long) (pos[j - 1] >> bin_shift) : -1;
+		}
+		fflag[j] = store(lp, lb) ? 1 : 0;
+	}
+}
+// merge: count-pass entries add slots, fill-pass entries (already in the sorted table) take theirs back
+__global__ void vcf_slot_delta_kernel(const uint32_t *__restrict__ keys, uint64_t n, int delta, uint32_t *__restrict__ raw) {
+	const uint64_t j = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
+	if (j < n) atomicAdd(&raw[keys[j]], (uint32_t) delta);
+}
+// sorted entry j of k-mer kj goes to the kj's new list at its rank; the slots behind the fill pass's entries stay 0
+__global__ void vcf_scatter_kernel(const uint32_t *__restrict__ keys, const uint32_t *__restrict__ vals, uint64_t n, const uint2 *__restrict__ old_index,
+		const uint32_t *__restrict__ start, const uint32_t *__restrict__ raw, uint32_t *__restrict__ out, unsigned int *__restrict__ overflow) {
+	const uint64_t j = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x;
+	if (j >= n) return;
+	const uint32_t kj = keys[j], rank = (uint32_t) j - old_index[kj].x;
+	if (rank < raw[kj]) out[(uint64_t) start[kj] + rank] = vals[j];
+	else atomicAdd(overflow, 1u);
+}
+__global__ void vcf_narrow_kernel(uint32_t n_kmers, const uint64_t *__restrict__ start64, uint32_t *__restrict__ start) {
+	const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+	if (p < n_kmers) start[p] = (uint32_t) start64[p];
+}
+__global__ void vcf_index_kernel(uint32_t n_kmers, const uint32_t *__restrict__ start, const uint32_t *__restrict__ raw, uint2 *__restrict__ index) {
+	const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+	if (p < n_kmers) index[p] = make_uint2(start[p], raw[p]);
+}
+
+// what the variants add to the table: fill-pass entries (keys + positions, VCF order) and count-pass keys
+struct VcfEntries {
+	uint32_t *d_fkeys = nullptr, *d_fvals = nullptr, *d_ckeys = nullptr;
+	uint64_t nf = 0, nc = 0, visited = 0;
+	~VcfEntries() { (void) hipFree(d_fkeys); (void) hipFree(d_fvals); (void) hipFree(d_ckeys); }
+};
+
+// regions on the GPU; their walk on the GPU, or (host_walk) on the host like KmerWalker
+int build_vcf_entries(ngm_ref *r, const WalkEnd &end, bool host_walk, VcfEntries &out) {
+	const NgmVcf &vcf = *r->vcf;
+	const int k = r->prm.kmer;
+	const uint64_t n = vcf.v.size(), concat = r->n_bases - 1;
+	r->vcf_summary[0] = n;
+	if (n == 0) return 0;
+	for (const NgmVariant &v : vcf.v) {
+		const uint64_t half = (uint64_t) k + v.ref_len + v.alt_len - 2;
+		if (v.pos < half) { ngm::pipeline_set_error("VCF variant at %llu: its region would start before the genome", (unsigned long long) v.pos); return -22; }
+		if (v.pos - half >= concat) { ngm::pipeline_set_error("VCF variant at %llu lies beyond the end of the genome", (unsigned long long) v.pos); return -22; }
+	}
+	NgmVariant *d_var = nullptr;
+	char *d_seq = nullptr;
+	uint8_t *d_status = nullptr, *d_regions = nullptr, *d_cf = nullptr, *d_ff = nullptr;
+	uint64_t *d_len = nullptr, *d_roff = nullptr, *d_vcount = nullptr, *d_voff = nullptr, *d_sel = nullptr;
+	unsigned long long *d_bad = nullptr, *d_counts = nullptr;
+	uint32_t *d_vk = nullptr, *d_vp = nullptr, *d_vr = nullptr;
+	void *d_tmp = nullptr;
+	struct Free { std::function<void()> f; ~Free() { f(); } } free_all{[&] {
+		(void) hipFree(d_var); (void) hipFree(d_seq); (void) hipFree(d_status); (void) hipFree(d_regions); (void) hipFree(d_cf); (void) hipFree(d_ff);
+		(void) hipFree(d_len); (void) hipFree(d_roff); (void) hipFree(d_vcount); (void) hipFree(d_voff); (void) hipFree(d_sel); (void) hipFree(d_bad);
+		(void) hipFree(d_counts); (void) hipFree(d_vk); (void) hipFree(d_vp); (void) hipFree(d_vr); (void) hipFree(d_tmp); }};
+	REF_HIP_TRY(hipMalloc(&d_var, n * sizeof(NgmVariant)));
+	REF_HIP_TRY(hipMalloc(&d_seq, std::max<size_t>(vcf.seq.size(), 1)));
+	REF_HIP_TRY(hipMemcpy(d_var, vcf.v.data(), n * sizeof(NgmVariant), hipMemcpyHostToDevice));
+	REF_HIP_TRY(hipMemcpy(d_seq, vcf.seq.data(), vcf.seq.size(), hipMemcpyHostToDevice));
+	REF_HIP_TRY(hipMalloc(&d_status, n)); REF_HIP_TRY(hipMalloc(&d_len, n * 8)); REF_HIP_TRY(hipMalloc(&d_roff, n * 8));
+	REF_HIP_TRY(hipMalloc(&d_bad, 8)); REF_HIP_TRY(hipMalloc(&d_counts, 3 * 8)); REF_HIP_TRY(hipMalloc(&d_sel, 8));
+	const unsigned long long none = ~0ull;
+	REF_HIP_TRY(hipMemcpy(d_bad, &none, 8, hipMemcpyHostToDevice));
+	REF_HIP_TRY(hipMemset(d_counts, 0, 3 * 8));
+	const unsigned nb = (unsigned) ((n + 255) / 256);
+	hipLaunchKernelGGL(vcf_classify_kernel, dim3(nb), dim3(256), 0, 0, d_var, n, d_seq, r->d_genome, concat, k, d_status, d_len, d_bad);
+	hipLaunchKernelGGL(vcf_cut_kernel, dim3(nb), dim3(256), 0, 0, n, d_bad, d_status, d_len, d_counts);
+	REF_HIP_TRY(hipGetLastError());
+	unsigned long long counts[3], bad = 0;
+	REF_HIP_TRY(hipMemcpy(counts, d_counts, 3 * 8, hipMemcpyDeviceToHost));
+	REF_HIP_TRY(hipMemcpy(&bad, d_bad, 8, hipMemcpyDeviceToHost));
+	if (bad != none) fprintf(stderr, "[PREPROCESS] SNP ref does not match reference at SNP %llu\n", (unsigned long long) vcf.v[bad].pos);
+	r->vcf_summary[1] = counts[0]; r->vcf_summary[2] = counts[1]; r->vcf_summary[3] = counts[2] + (bad != none ? 1 : 0);
+	size_t tb = 0;
+	REF_HIP_TRY(rocprim::exclusive_scan(nullptr, tb, d_len, d_roff, (uint64_t) 0, (size_t) n, rocprim::plus<uint64_t>()));
+	tb += 256;
+	REF_HIP_TRY(hipMalloc(&d_tmp, tb));
+	REF_HIP_TRY(rocprim::exclusive_scan(d_tmp, tb, d_len, d_roff, (uint64_t) 0, (size_t) n, rocprim::plus<uint64_t>()));
+	uint64_t last_off = 0, last_len = 0;
+	REF_HIP_TRY(hipMemcpy(&last_off, d_roff + n - 1, 8, hipMemcpyDeviceToHost));
+	REF_HIP_TRY(hipMemcpy(&last_len, d_len + n - 1, 8, hipMemcpyDeviceToHost));
+	const uint64_t total = last_off + last_len;
+	REF_HIP_TRY(hipMalloc(&d_regions, std::max<uint64_t>(total, 1)));
+	hipLaunchKernelGGL(vcf_fill_kernel, dim3(nb), dim3(256), 0, 0, d_var, n, d_seq, r->d_genome, concat, k, d_len, d_roff, d_regions);
+	REF_HIP_TRY(hipGetLastError());
+	const uint32_t mask = (1u << (2 * k)) - 1u;
+	const int bin_shift = r->prm.bin_size, skip = r->prm.kmer_skip;
+	if (host_walk) {
+		// the two walkers of the reference: the count pass restarts its state per region, the fill pass carries it on
+		std::vector<uint8_t> reg(total);
+		std::vector<uint64_t> len(n), roff(n);
+		REF_HIP_TRY(hipMemcpy(reg.data(), d_regions, total, hipMemcpyDeviceToHost));
+		REF_HIP_TRY(hipMemcpy(len.data(), d_len, n * 8, hipMemcpyDeviceToHost));
+		REF_HIP_TRY(hipMemcpy(roff.data(), d_roff, n * 8, hipMemcpyDeviceToHost));
+		std::vector<uint32_t> fk, fv, ck;
+		uint32_t fp = end.last_prefix, cpfx = 111111u;
+		int64_t fb = end.last_bin, cbin = -1;
+		uint64_t visited = 0;
+		auto f = [&](uint32_t prefix, uint64_t pos) {
+			const int64_t bin = (int64_t) (pos >> bin_shift);
+			++visited;
+			auto step = [&](uint32_t &lp, int64_t &lb) {
+				bool st = true;
+				if (prefix == lp) { if (!(bin != lb || lb == -1)) st = false; lb = bin; }
+				else lb = -1;
+				lp = prefix;
+				return st;
+			};
+			if (step(cpfx, cbin)) ck.push_back(prefix);
+			if (step(fp, fb)) { fk.push_back(prefix); fv.push_back((uint32_t) pos); }
+		};
+		for (uint64_t i = 0; i < n; ++i) {
+			if (!len[i]) continue;
+			cpfx = 111111u; cbin = -1;
+			const NgmVariant &v = vcf.v[i];
+			vcf_walk_region(reg.data() + roff[i], len[i], v.pos - ((uint64_t) k + v.ref_len + v.alt_len - 2), k, skip, mask, f);
+		}
+		out.visited = visited; out.nf = fk.size(); out.nc = ck.size();
+		REF_HIP_TRY(hipMalloc(&out.d_fkeys, std::max<uint64_t>(out.nf, 1) * 4)); REF_HIP_TRY(hipMalloc(&out.d_fvals, std::max<uint64_t>(out.nf, 1) * 4));
+		REF_HIP_TRY(hipMalloc(&out.d_ckeys, std::max<uint64_t>(out.nc, 1) * 4));
+		REF_HIP_TRY(hipMemcpy(out.d_fkeys, fk.data(), out.nf * 4, hipMemcpyHostToDevice));
+		REF_HIP_TRY(hipMemcpy(out.d_fvals, fv.data(), out.nf * 4, hipMemcpyHostToDevice));
+		REF_HIP_TRY(hipMemcpy(out.d_ckeys, ck.data(), out.nc * 4, hipMemcpyHostToDevice));
+		return 0;
+	}
+	REF_HIP_TRY(hipMalloc(&d_vcount, n * 8)); REF_HIP_TRY(hipMalloc(&d_voff, n * 8));
+	hipLaunchKernelGGL(vcf_walk_kernel<false>, dim3(nb), dim3(256), 0, 0, d_var, n, k, skip, d_len, d_roff, d_regions, d_vcount, nullptr, nullptr, nullptr, nullptr);
+	REF_HIP_TRY(hipGetLastError());
+	REF_HIP_TRY(rocprim::exclusive_scan(d_tmp, tb, d_vcount, d_voff, (uint64_t) 0, (size_t) n, rocprim::plus<uint64_t>()));
+	REF_HIP_TRY(hipMemcpy(&last_off, d_voff + n - 1, 8, hipMemcpyDeviceToHost));
+	REF_HIP_TRY(hipMemcpy(&last_len, d_vcount + n - 1, 8, hipMemcpyDeviceToHost));
+	const uint64_t m = last_off + last_len;
+	out.visited = m;
+	if (m == 0) return 0;
+	REF_HIP_TRY(hipMalloc(&d_vk, m * 4)); REF_HIP_TRY(hipMalloc(&d_vp, m * 4)); REF_HIP_TRY(hipMalloc(&d_vr, m * 4));
+	hipLaunchKernelGGL(vcf_walk_kernel<true>, dim3(nb), dim3(256), 0, 0, d_var, n, k, skip, d_len, d_roff, d_regions, nullptr, d_voff, d_vk, d_vp, d_vr);
+	REF_HIP_TRY(hipMalloc(&d_cf, m)); REF_HIP_TRY(hipMalloc(&d_ff, m));
+	const unsigned mb = (unsigned) ((m + 255) / 256);
+	hipLaunchKernelGGL(vcf_store_flags_kernel, dim3(mb), dim3(256), 0, 0, d_vk, d_vp, d_vr, m, bin_shift, end.last_prefix, (long long) end.last_bin, d_cf, d_ff);
+	REF_HIP_TRY(hipGetLastError());
+	(void) hipFree(d_tmp); d_tmp = nullptr;
+	tb = 0;
+	REF_HIP_TRY(rocprim::select(nullptr, tb, d_vk, d_ff, (uint32_t *) nullptr, d_sel, (size_t) m));
+	tb += 256;
+	REF_HIP_TRY(hipMalloc(&d_tmp, tb));
+	REF_HIP_TRY(hipMalloc(&out.d_fkeys, m * 4)); REF_HIP_TRY(hipMalloc(&out.d_fvals, m * 4)); REF_HIP_TRY(hipMalloc(&out.d_ckeys, m * 4));
+	REF_HIP_TRY(rocprim::select(d_tmp, tb, d_vk, d_ff, out.d_fkeys, d_sel, (size_t) m));
+	REF_HIP_TRY(rocprim::select(d_tmp, tb, d_vp, d_ff, out.d_fvals, d_sel, (size_t) m));
+	REF_HIP_TRY(hipMemcpy(&out.nf, d_sel, 8, hipMemcpyDeviceToHost));
+	REF_HIP_TRY(rocprim::select(d_tmp, tb, d_vk, d_cf, out.d_ckeys, d_sel, (size_t) m));
+	REF_HIP_TRY(hipMemcpy(&out.nc, d_sel, 8, hipMemcpyDeviceToHost));
 	return 0;
 }
 
@@ -361,11 +694,15 @@ int build_index(ngm_ref *r) {
 	const uint32_t n_kmers = 1u << (2 * k);
 	uint32_t *d_keys = nullptr, *d_vals = nullptr, *d_keys2 = nullptr, *d_starts = nullptr;
 	uint64_t n = 0;
-	{
+	WalkEnd end;
+	// NGM_HIP_TEST_LIMITS=host_walk=1: the host walk below, as taken when the GPU walk runs out of memory
+	const bool host_walk = ngm::test_limit("host_walk", 0) != 0;
+	if (!host_walk) {
 		// the walk on the GPU (CountKmerFreq decodes a contig with bufferLength = len and DecodeRefSequence emits len - 2 bases,
 		// 'x' / NUL after that, which encode() maps to 0: the last two bases of a contig act as 'A' -- handled in the kernels)
-		if (gpu_kmer_walk(r, &d_keys, &d_vals, &n) != 0) { d_keys = d_vals = nullptr; n = 0; (void) hipGetLastError(); }  // e.g. out of memory on a shared GPU: the host walk needs no scratch
+		if (gpu_kmer_walk(r, &d_keys, &d_vals, &n, &end) != 0) { d_keys = d_vals = nullptr; n = 0; end = WalkEnd(); (void) hipGetLastError(); }  // e.g. out of memory on a shared GPU: the host walk needs no scratch
 	}
+	const bool walked_on_host = !d_keys;
 	if (!d_keys) {
 		std::vector<uint32_t> keys, vals;
 		keys.reserve(r->n_bases / (r->prm.kmer_skip + 1) + 16);
@@ -382,11 +719,34 @@ int build_index(ngm_ref *r) {
 			if (c.len >= 2) { tmp[c.len - 2] = 0; tmp[c.len - 1] = 0; }
 			w.iterate(tmp.data(), c.len, c.start);
 		}
+		end.visited = w.visited; end.last_prefix = w.last_prefix; end.last_bin = w.last_bin;
 		n = keys.size();
 		REF_HIP_TRY(hipMalloc(&d_keys, std::max<uint64_t>(n, 1) * 4));
 		REF_HIP_TRY(hipMalloc(&d_vals, std::max<uint64_t>(n, 1) * 4));
 		REF_HIP_TRY(hipMemcpy(d_keys, keys.data(), n * 4, hipMemcpyHostToDevice));
 		REF_HIP_TRY(hipMemcpy(d_vals, vals.data(), n * 4, hipMemcpyHostToDevice));
+	}
+	VcfEntries ve;
+	if (r->vcf) {
+		// the variants' fill-pass entries go behind the genome's, so the stable sort keeps each list in the reference's order
+		if (int rc = build_vcf_entries(r, end, walked_on_host, ve)) { (void) hipFree(d_keys); (void) hipFree(d_vals); return rc; }
+		uint32_t *k2 = nullptr, *v2 = nullptr;
+		if (hipMalloc(&k2, std::max<uint64_t>(n + ve.nf, 1) * 4) != hipSuccess || hipMalloc(&v2, std::max<uint64_t>(n + ve.nf, 1) * 4) != hipSuccess) {
+			(void) hipFree(k2); (void) hipFree(d_keys); (void) hipFree(d_vals);
+			ngm::pipeline_set_error("out of device memory adding the VCF's k-mers");
+			return -12;
+		}
+		REF_HIP_TRY(hipMemcpy(k2, d_keys, n * 4, hipMemcpyDeviceToDevice)); REF_HIP_TRY(hipMemcpy(v2, d_vals, n * 4, hipMemcpyDeviceToDevice));
+		REF_HIP_TRY(hipMemcpy(k2 + n, ve.d_fkeys, ve.nf * 4, hipMemcpyDeviceToDevice)); REF_HIP_TRY(hipMemcpy(v2 + n, ve.d_fvals, ve.nf * 4, hipMemcpyDeviceToDevice));
+		(void) hipFree(d_keys); (void) hipFree(d_vals);
+		d_keys = k2; d_vals = v2;
+		const uint64_t genome_skips = end.visited - n;
+		r->vcf_skip_count = genome_skips + ve.visited - ve.nc;
+		r->vcf_skip_build = genome_skips + ve.visited - ve.nf;
+		r->vcf_summary[4] = ve.nf;
+		r->vcf_summary[5] = ve.nc - ve.nf;
+		r->vcf_applied = true;
+		n += ve.nf;
 	}
 	r->n_entries = n;
 	REF_HIP_TRY(hipMalloc(&d_keys2, std::max<uint64_t>(n, 1) * 4));
@@ -398,8 +758,9 @@ int build_index(ngm_ref *r) {
 	REF_HIP_TRY(hipMemset(d_starts, 0, (size_t) n_kmers * 4));
 	REF_HIP_TRY(hipMemset(r->d_raw_counts, 0, (size_t) n_kmers * 4));
 	if (n > 0) {
-		// stable LSD radix sort on the 2k key bits: positions stay ascending inside each k-mer group,
-		// which is the order BuildPrefixTable appends them in (PrefixTable.cpp:729-748)
+		// stable LSD radix sort on the 2k key bits: inside each k-mer group the entries keep their input order -- ascending genome
+		// positions, which is the order BuildPrefixTable appends them in (PrefixTable.cpp:729-748), followed with --vcf by the
+		// variant regions' entries in VCF order (not ascending, and a position may repeat: refindex.h)
 		size_t tmp_bytes = 0;
 		REF_HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_keys, d_keys2, d_vals, r->d_positions, n, 0, 2 * k));
 		void *d_tmp = nullptr;
@@ -411,6 +772,54 @@ int build_index(ngm_ref *r) {
 		(void) hipFree(d_tmp);
 	}
 	hipLaunchKernelGGL(finish_index_kernel, dim3((n_kmers + 255) / 256), dim3(256), 0, 0, n_kmers, k, d_starts, r->d_raw_counts, r->d_index);
+	if (r->vcf) {
+		// every list gets the count pass's number of slots (PrefixTable.cpp:360-374): its entries so far, then zeros
+		if (ve.nc) hipLaunchKernelGGL(vcf_slot_delta_kernel, dim3((unsigned) ((ve.nc + 255) / 256)), dim3(256), 0, 0, ve.d_ckeys, ve.nc, 1, r->d_raw_counts);
+		if (ve.nf) hipLaunchKernelGGL(vcf_slot_delta_kernel, dim3((unsigned) ((ve.nf + 255) / 256)), dim3(256), 0, 0, ve.d_fkeys, ve.nf, -1, r->d_raw_counts);
+		REF_HIP_TRY(hipGetLastError());
+		// new list starts: exclusive scan of the new lengths (in 64 bits, so that a table beyond 2^32 entries is caught)
+		uint64_t total = 0;
+		{
+			uint64_t *d_start64 = nullptr;
+			void *d_scan = nullptr;
+			size_t sb = 0;
+			auto widen = rocprim::make_transform_iterator(r->d_raw_counts, [] __host__ __device__ (uint32_t x) { return (uint64_t) x; });
+			REF_HIP_TRY(rocprim::exclusive_scan(nullptr, sb, widen, d_start64, (uint64_t) 0, (size_t) n_kmers, rocprim::plus<uint64_t>()));
+			REF_HIP_TRY(hipMalloc(&d_start64, (size_t) n_kmers * 8));
+			if (hipMalloc(&d_scan, sb + 256) != hipSuccess) { (void) hipFree(d_start64); ngm::pipeline_set_error("out of device memory (VCF list starts)"); return -12; }
+			const hipError_t e1 = rocprim::exclusive_scan(d_scan, sb, widen, d_start64, (uint64_t) 0, (size_t) n_kmers, rocprim::plus<uint64_t>());
+			uint64_t last_start = 0;
+			uint32_t last_raw = 0;
+			const hipError_t e2 = hipMemcpy(&last_start, d_start64 + n_kmers - 1, 8, hipMemcpyDeviceToHost);
+			const hipError_t e3 = hipMemcpy(&last_raw, r->d_raw_counts + n_kmers - 1, 4, hipMemcpyDeviceToHost);
+			total = last_start + last_raw;
+			if (e1 == hipSuccess && e2 == hipSuccess && e3 == hipSuccess && total + 16 < 0xFFFFFFFFull)
+				hipLaunchKernelGGL(vcf_narrow_kernel, dim3((n_kmers + 255) / 256), dim3(256), 0, 0, n_kmers, d_start64, d_starts);
+			(void) hipFree(d_scan);
+			const hipError_t e4 = hipDeviceSynchronize();
+			(void) hipFree(d_start64);
+			if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess) { ngm::pipeline_set_error("scanning the VCF list lengths failed"); return -5; }
+			if (total + 16 >= 0xFFFFFFFFull) { ngm::pipeline_set_error("k-mer table with the VCF's k-mers exceeds 2^32 entries"); return -27; }
+		}
+		uint32_t *d_final = nullptr;
+		unsigned int *d_over = nullptr;
+		REF_HIP_TRY(hipMalloc(&d_final, (total + 16) * 4));
+		REF_HIP_TRY(hipMemset(d_final, 0, (total + 16) * 4));
+		REF_HIP_TRY(hipMalloc(&d_over, 4));
+		REF_HIP_TRY(hipMemset(d_over, 0, 4));
+		if (n) hipLaunchKernelGGL(vcf_scatter_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, 0, d_keys2, r->d_positions, n, r->d_index, d_starts, r->d_raw_counts, d_final, d_over);
+		hipLaunchKernelGGL(vcf_index_kernel, dim3((n_kmers + 255) / 256), dim3(256), 0, 0, n_kmers, d_starts, r->d_raw_counts, r->d_index);
+		REF_HIP_TRY(hipGetLastError());
+		unsigned int over = 0;
+		REF_HIP_TRY(hipMemcpy(&over, d_over, 4, hipMemcpyDeviceToHost));
+		(void) hipFree(d_over);
+		(void) hipFree(r->d_positions);
+		r->d_positions = d_final;
+		r->n_entries = n = total;
+		// (the fill pass never stores more into a list than the count pass reserved: the two differ in the first two visited
+		// k-mers of a region only, where the count pass stores and the fill pass may skip)
+		if (over) { ngm::pipeline_set_error("VCF k-mers: the fill pass stored more entries than the count pass reserved (%u)", over); return -75; }
+	}
 	hipLaunchKernelGGL(apply_usage_rule_kernel, dim3((n_kmers + 255) / 256), dim3(256), 0, 0, n_kmers, k, r->d_raw_counts, r->d_index);
 	REF_HIP_TRY(hipGetLastError());
 	REF_HIP_TRY(hipDeviceSynchronize());
@@ -724,10 +1133,16 @@ ngm_ref *ngm_ref_create_from_cache(int device, const ngm_ref_params *p, const ch
 	return r;
 }
 
-ngm_ref *ngm_ref_create_from_fasta(int device, const ngm_ref_params *p, const char *path) {
-	// like the reference, an index cache next to the FASTA is used instead of rebuilding (NGM_HIP_NO_CACHE=1: always rebuild)
+static ngm_ref *create_from_fasta(int device, const ngm_ref_params *p, const char *path, const char *vcf_path) {
+	// like the reference, an index cache next to the FASTA is used instead of rebuilding (NGM_HIP_NO_CACHE=1: always rebuild); the
+	// VCF is then not read at all (PrefixTable.cpp:223-228 only reads it when the table is built)
 	if (!getenv("NGM_HIP_NO_CACHE")) {
 		if (ngm_ref *cached = ngm_ref_create_from_cache(device, p, path)) return cached;
+	}
+	if (vcf_path) {  // an unreadable VCF is an error before any GPU work (the reference logs it and goes on without variants)
+		gzFile v = gzopen(vcf_path, "rb");
+		if (!v) { ngm::pipeline_set_error("Failed to open VCF file %s", vcf_path); return nullptr; }
+		gzclose(v);
 	}
 	gzFile f = gzopen(path, "rb");
 	if (!f) { ngm::pipeline_set_error("cannot open reference %s", path); return nullptr; }
@@ -765,7 +1180,33 @@ ngm_ref *ngm_ref_create_from_fasta(int device, const ngm_ref_params *p, const ch
 	if (!carry.empty()) handle_line(carry.data(), carry.size());
 	flush();
 	gzclose(f);
-	return seal(r);
+	NgmVcf vcf;
+	if (vcf_path) {
+		if (ngm_vcf_read(vcf_path, r->contigs, vcf) != 0) { ngm_ref_destroy(r); return nullptr; }
+		r->vcf = &vcf;
+	}
+	ngm_ref *out = seal(r);
+	if (out) out->vcf = nullptr;  // (the variants live in the index now)
+	return out;
+}
+
+ngm_ref *ngm_ref_create_from_fasta(int device, const ngm_ref_params *p, const char *path) { return create_from_fasta(device, p, path, nullptr); }
+
+ngm_ref *ngm_ref_create_from_fasta_vcf(int device, const ngm_ref_params *p, const char *fasta_path, const char *vcf_path) {
+	if (!vcf_path) { ngm::pipeline_set_error("ngm_ref_create_from_fasta_vcf: no VCF file given"); return nullptr; }
+	return create_from_fasta(device, p, fasta_path, vcf_path);
+}
+
+int ngm_ref_vcf_summary(const ngm_ref *r, uint64_t out[6]) {
+	if (!r || !out) return -22;
+	for (int i = 0; i < 6; ++i) out[i] = r->vcf_summary[i];
+	return r->vcf_applied ? 1 : 0;
+}
+
+int ngm_ref_vcf_skip_counts(const ngm_ref *r, uint64_t out[2]) {
+	if (!r || !out) return -22;
+	out[0] = r->vcf_skip_count; out[1] = r->vcf_skip_build;
+	return r->vcf_applied ? 1 : 0;
 }
 
 void ngm_ref_destroy(ngm_ref *r) {

@@ -11,6 +11,21 @@
 //                 5-byte packed entries, PrefixTable.h:27-61); count is already 0 for k-mers that the reference
 //                 treats as unused (>= 9901 occurrences fwd+revcomp, PrefixTable.cpp:468-478)  -- 537 MB
 //   d_positions : one uint32 per indexed k-mer occurrence, grouped by k-mer, ascending        -- ~4.1 GB
+//                 ... unless the index was built with --vcf (or loaded from a cache `ngm --vcf` wrote): then a list holds its genome
+//                 positions in ascending order, then the positions of the variant regions in VCF order (not ascending, a position may
+//                 repeat -- regions overlap), then zero slots where the reference's fill pass stored fewer entries than its count pass
+//                 reserved (PrefixTable.cpp:360-374 against :411-422; see build_vcf_entries).  What the search makes of them:
+//                 * order and repeats: the search kernels and the order replay take a list's entries in index order (the reference's
+//                   vote order, CS.cpp:116-160) and identify a bin by its value only; no kernel assumes ascending or distinct positions.
+//                 * a zero slot is position 0: `pos - corr` wraps at 2^32 on the GPU where the reference's wraps at 2^64.  With bins of
+//                   >= 4 bases (bin_size >= 2) the wrapped bin (2^32 - corr) >> bin_size fits in the kernels' 30 bits and, like the
+//                   reference's (2^64 - corr) >> bin_size, lies beyond every genome bin (corr < 1024, the genome below 2^32 - 1024);
+//                   bins group the corrections alike in both (2^32 is a multiple of the bin width), so the vote counts, thresholds and
+//                   candidate order (rList: first arrival, not hash slot) are the same; such a candidate's window starts past the
+//                   genome's end, so both score it against a row of 'N' (ScoreBuffer.cpp:113-118, gather_device.h), which scores at most
+//                   0 in local mode: it is never the top score of a mapped read (ScoreBuffer.cpp:418).  Not covered by that argument
+//                   and refused with --vcf by ngm-hip: --argos (prints every candidate: the reference converts these positions past its
+//                   contig table), -e (negative scores), -n > 1, --bam, several GPUs and shards (not yet tested).
 //   d_buckets   : the layout the candidate search actually gathers from: one aligned bucket of W = 4..32 dwords per
 //                 k-mer, {count, position 0 .. W-2}, so that a lookup is ONE memory request instead of index entry ->
 //                 position list (measured on MI355X, profiles/r02_gather_calibration.txt: random gathers are bound by
@@ -79,7 +94,25 @@ struct ngm_ref {
 	uint32_t *d_cbuckets = nullptr;
 	int cbucket_log2_words = 2;
 	uint32_t cbucket_pos_base = 0;
+	// --vcf (PrefixTable.cpp:223-228, :500-574): the variants of the VCF in file order, applied by build_index; and what came of them
+	const struct NgmVcf *vcf = nullptr;
+	bool vcf_applied = false;
+	uint64_t vcf_summary[6] = {0, 0, 0, 0, 0, 0};  // variations loaded, SNPs, indels, ignored, region entries stored, zero slots
+	uint64_t vcf_skip_count = 0, vcf_skip_build = 0; // the reference's skipCount / skipBuild (PrefixTable.cpp:439-443)
 };
+
+// one variant of a VCF, as VcfParser::add_line keeps it (src/parser/VcfParser.cpp): REF and ALT are ranges of NgmVcf::seq
+struct NgmVariant {
+	uint64_t pos;  // contig start + POS
+	uint32_t ref_off, ref_len, alt_off, alt_len;
+};
+struct NgmVcf {
+	std::vector<NgmVariant> v;
+	std::string seq;
+};
+// reads a plain or gzip VCF against the contig table (0, or a negative error with the reason as the last error); the messages the
+// reference logs for odd lines go to stderr, in file order
+int ngm_vcf_read(const char *path, const std::vector<NgmContig> &contigs, NgmVcf &out);
 
 // builds the bucket layout `kind` (0: one bucket per k-mer, 1: canonical pairs; odd k only) if it does not exist yet; 0 or -errno
 int ngm_ref_ensure_buckets(const ngm_ref *r, int kind);

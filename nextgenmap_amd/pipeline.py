@@ -37,6 +37,11 @@ def _lib():
         lib.ngm_ref_create.argtypes = [C.c_int, C.POINTER(RefParams), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.ngm_ref_create_from_fasta.restype = C.c_void_p
         lib.ngm_ref_create_from_fasta.argtypes = [C.c_int, C.POINTER(RefParams), C.c_char_p]
+        lib.ngm_ref_create_from_fasta_vcf.restype = C.c_void_p
+        lib.ngm_ref_create_from_fasta_vcf.argtypes = [C.c_int, C.POINTER(RefParams), C.c_char_p, C.c_char_p]
+        lib.ngm_ref_vcf_summary.argtypes = [C.c_void_p, C.c_void_p]
+        lib.ngm_vcf_parse_text.restype = C.c_longlong
+        lib.ngm_vcf_parse_text.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         lib.ngm_ref_create_from_cache.restype = C.c_void_p
         lib.ngm_ref_create_from_cache.argtypes = [C.c_int, C.POINTER(RefParams), C.c_char_p]
         lib.ngm_ref_destroy.argtypes = [C.c_void_p]
@@ -154,10 +159,14 @@ class Reference:
         return cls(h, kmer)
 
     @classmethod
-    def from_fasta(cls, path, device=0, kmer=13, kmer_skip=2, bin_size=2):
+    def from_fasta(cls, path, device=0, kmer=13, kmer_skip=2, bin_size=2, vcf=None):
+        """vcf: a plain or gzip VCF whose variants' k-mers go into the index (ngm --vcf); not read when a cache is loaded"""
         lib = _lib()
         p = RefParams(kmer, kmer_skip, bin_size)
-        h = lib.ngm_ref_create_from_fasta(device, C.byref(p), path.encode())
+        if vcf is not None:
+            h = lib.ngm_ref_create_from_fasta_vcf(device, C.byref(p), path.encode(), vcf.encode())
+        else:
+            h = lib.ngm_ref_create_from_fasta(device, C.byref(p), path.encode())
         if not h:
             raise _err()
         return cls(h, kmer)
@@ -182,6 +191,14 @@ class Reference:
             self.close()
         except Exception:
             pass
+
+    def vcf_summary(self):
+        """dict of what the VCF added (None when the index was not built with one): the reference's `Loaded VCF` /
+        `Built SNP region table` counts, the region entries stored and the zero slots"""
+        out = (C.c_uint64 * 6)()
+        if self.lib.ngm_ref_vcf_summary(self.h, out) != 1:
+            return None
+        return dict(zip(("variations", "snps", "indels", "ignored", "entries", "zero_slots"), [int(x) for x in out]))
 
     @property
     def contigs(self):
