@@ -18,12 +18,19 @@ bench cross-checks its SAM records against ours) or linear (NGM's default OpenCL
           Rank 0 builds the genome + index once and writes NextGenMap's cache files; the other ranks load those
           (nextgenmap_amd.sharding: shard_range / reduce_stats are the same two functions `ngm-hip` semantics follow).
 
+A plain run does what the headline figure needs and nothing else: genome, index and read sets, the warm-up, the timed steps,
+--dump-outputs, the JSON line (`value`, `ms_per_step`, and what the timed steps' own HIP events and counters give: `kernel_ms`,
+`roofline`, `per_read`, accuracy, the statistics all-reduce).  --full adds every other leg, each a run of its own: the isolated
+pass of one mapper instance (`roofline.candidate_search.isolated`), `end_to_end`, `cpu_baseline`, `heavy_tailed_genome`, and for
+N > 1 the sharded `end_to_end`; without it those fields are null or absent.  The options that size or skip a leg
+(--no-end-to-end, --no-cpu-baseline, --heavy-tail-mbp 0, --e2e-reads, ...) act under --full only.
+
 Prints ONE JSON line (rank 0): `roofline` describes the dominant kernel (candidate search) from HIP events
-recorded on the launch stream; `cpu_baseline` is the REAL reference program (NextGenMap's ngm-core built from
+recorded on the launch stream; `cpu_baseline` (--full) is the REAL reference program (NextGenMap's ngm-core built from
 its sources by oracle/ngm_ref.mk, --affine because the default backend needs an OpenCL CPU device) run on this
 host on a bounded sample of the same reads against the same genome (it loads the index cache files this
 library writes), or, when that binary is absent, the oracle's C restatement of the score stage only.
-`end_to_end` (N = 1, unless --no-end-to-end) is the DROP-IN measured: the `ngm-hip` program from the first input byte to
+`end_to_end` (--full, N = 1, unless --no-end-to-end) is the DROP-IN measured: the `ngm-hip` program from the first input byte to
 the closed SAM file -- FASTQ parsing, H2D copies, mapping, SAM text -- on --e2e-reads reads written as two plain FASTQ
 files, index loaded from the cache files, next to `ngm-core -t <cores>` on a slice of the same files.
 
@@ -139,6 +146,50 @@ def make_reads(contigs, n, seed, paired=False, subs=0.01, indel_bases=0.0, start
         rev = rng.random(n) < 0.5
         rows[rev, :READ_LEN] = COMP[rows[rev, :READ_LEN][:, ::-1]]
     return rows, ci, pos
+
+
+def fork_read_sets(contigs, n, seeds, paired, **kw):
+    """make_reads(contigs, n, seed, paired, **kw) per seed, every set in a child process of its own (the sets differ by the seed alone,
+    and one of 1 M reads is seconds of Python) that fills arrays in shared anonymous memory.  Only for a process that has not opened the
+    GPU yet (the children never do), so they are forked now and wait.  Returns collect(): it lets them start, waits for them and copies
+    their arrays into ordinary ones, so the caller holds what [make_reads(...) for seed in seeds] gives."""
+    import mmap
+    import traceback
+
+    def shared(count, dtype):
+        return np.frombuffer(mmap.mmap(-1, max(1, count * np.dtype(dtype).itemsize)), dtype=dtype, count=count)
+    bufs = [(shared(n * Q, np.uint8).reshape(n, Q), shared(2 * (n // 2) if paired else n, np.int64), shared(n, np.int64)) for _ in seeds]
+    sys.stdout.flush()
+    sys.stderr.flush()
+    gate_r, gate_w = os.pipe()
+    pids = []
+    for s_, b in zip(seeds, bufs):
+        pid = os.fork()
+        if pid == 0:
+            code = 1
+            try:
+                os.close(gate_w)
+                if os.read(gate_r, 1) != b"g":   # (end of file: the parent is gone without collect())
+                    os._exit(2)
+                for dst, src in zip(b, make_reads(contigs, n, seed=s_, paired=paired, **kw)):
+                    assert dst.shape == src.shape and dst.dtype == src.dtype, (dst.shape, dst.dtype, src.shape, src.dtype)
+                    dst[...] = src
+                code = 0
+            except BaseException:
+                traceback.print_exc()
+            finally:
+                os._exit(code)
+        pids.append(pid)
+    os.close(gate_r)
+
+    def collect():
+        os.write(gate_w, b"g" * len(pids))
+        os.close(gate_w)
+        status = [os.waitpid(pid, 0)[1] for pid in pids]
+        if any(status):
+            raise RuntimeError("read set generation failed in a child process: wait status %r" % (status,))
+        return [tuple(np.array(a) for a in b) for b in bufs]
+    return collect
 
 
 def _sam_records(path, paired=False):
@@ -829,6 +880,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--genome-mbp", type=float, default=3100.0, help="synthetic genome size (GRCh38 = 3100)")
     ap.add_argument("--reads-per-step", type=int, default=1 << 20, help="reads per GPU per step")
+    ap.add_argument("--full", action="store_true",
+                    help="also every leg beyond the headline figure, each a run of its own: the isolated pass of one mapper instance, end_to_end, "
+                         "cpu_baseline, heavy_tailed_genome, the sharded end_to_end of N > 1 (the options that size or skip a leg act under --full only)")
     ap.add_argument("--cpu-sample-reads", type=int, default=2_000_000)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--personality", choices=["affine", "linear"], default="affine")
@@ -865,10 +919,35 @@ def main():
     Q = (READ_LEN | 1) + 1                                   # ReadProvider.cpp:288
     C = args.corridor if args.corridor > 0 else int(5 + 0.15 * READ_LEN)  # ReadProvider.cpp:304
 
+    stub = args.stub_mapper
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = int(os.environ.get("RANK", "0"))
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    if args.gpus > 1 and world != args.gpus:
+        raise SystemExit("--gpus %d needs torch.distributed.run with --nproc-per-node %d" % (args.gpus, args.gpus))
+    R = args.reads_per_step
+    paired = args.layout == "pe"
+    affine = args.personality == "affine"
+    band = C + 1 if affine else C  # SeqAn's band has diagonals 0..corridor
+    # S distinct read sets, all resident in HBM; step i maps set i mod S (the steps do not map the same reads over and over)
+    S = max(1, min(args.read_sets, args.steps if args.steps > 0 else 1))
+    set_seeds = [20240602 + 2 + 1000 * rank + 7919 * s_ for s_ in range(S)]  # (set 0: config #2's seed, one shard per rank)
+    t_gen = t_index = 0.0
+    contigs = collect_sets = None
+    if world == 1:
+        t0 = time.perf_counter()
+        # one process: the genome first, then one child process per read set, forked before this process loads torch and opens the GPU.
+        # They start after the index build, where the read sets have always been made, not under it: measured on one box, alternating
+        # runs, 10 steps: read sets made under the index build 46.9-49.9 M reads/s, after it (serially or by the children) 50.5-53.2 M.
+        # The index build keeps 64 host threads busy under a CPU quota of 16, and the host stages of steps that follow it at once
+        # take 2 ms per step longer
+        contigs = make_genome(int(args.genome_mbp * 1e6), seed=20240601)
+        t_gen = time.perf_counter() - t0
+        collect_sets = fork_read_sets(contigs, R, set_seeds, paired, subs=args.subs, indel_bases=args.indel_bases)
+
     import torch
     import torch.distributed as dist
     from nextgenmap_amd import sharding
-    stub = args.stub_mapper
     if not stub:
         from nextgenmap_amd.pipeline import HIT_DTYPE, Mapper, Reference
     else:
@@ -876,11 +955,6 @@ def main():
                               ("identity", np.float32), ("nm", np.int32), ("qstart", np.int32), ("qend", np.int32), ("n_candidates", np.int32),
                               ("n_best", np.int32), ("max_votes", np.float32), ("pair_flags", np.int32)])
 
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    if args.gpus > 1 and world != args.gpus:
-        raise SystemExit("--gpus %d needs torch.distributed.run with --nproc-per-node %d" % (args.gpus, args.gpus))
     pinned_cpus = 0
     if stub:
         dev = torch.device("cpu")
@@ -907,11 +981,6 @@ def main():
             dist.barrier()
         sync()
 
-    R = args.reads_per_step
-    paired = args.layout == "pe"
-    affine = args.personality == "affine"
-    band = C + 1 if affine else C  # SeqAn's band has diagonals 0..corridor
-
     # ---- genome + index: rank 0 builds them once; the other ranks of the node load NextGenMap's cache files it writes ----
     wd = [tempfile.mkdtemp(prefix="ngm_bench_") if rank == 0 else None]
     if world > 1:
@@ -919,12 +988,12 @@ def main():
     workdir = wd[0]
     fa = os.path.join(workdir, "bench_ref.fa")
     gen_file = os.path.join(workdir, "genome.u8")
-    t_gen = t_index = 0.0
     ref = None
     if rank == 0:
-        t0 = time.perf_counter()
-        contigs = make_genome(int(args.genome_mbp * 1e6), seed=20240601)
-        t_gen = time.perf_counter() - t0
+        if contigs is None:
+            t0 = time.perf_counter()
+            contigs = make_genome(int(args.genome_mbp * 1e6), seed=20240601)
+            t_gen = time.perf_counter() - t0
         t0 = time.perf_counter()
         if not stub:
             ref = Reference.from_contigs(contigs, device=local_rank, kmer=KMER, kmer_skip=2, bin_size=2)
@@ -952,10 +1021,9 @@ def main():
     # ---- this rank's shard of the job's reads (weak scaling: R reads per rank per step) ----------------------------------
     lo_g, hi_g = sharding.shard_range(R * world, rank, world, paired=paired)
     assert hi_g - lo_g == R
-    # S distinct read sets, all resident in HBM; step i maps set i mod S (the steps do not map the same reads over and over)
-    S = max(1, min(args.read_sets, args.steps if args.steps > 0 else 1))
-    sets = [make_reads(contigs, R, seed=20240602 + 2 + 1000 * rank + 7919 * s_, paired=paired, subs=args.subs, indel_bases=args.indel_bases)
-            for s_ in range(S)]  # (set 0: config #2's seed, one shard per rank)
+    t0 = time.perf_counter()
+    sets = collect_sets() if collect_sets else [make_reads(contigs, R, seed=s_, paired=paired, subs=args.subs, indel_bases=args.indel_bases) for s_ in set_seeds]
+    t_reads = time.perf_counter() - t0
     sens = 0.5 - 0.35 * 0.5 if args.sensitive else 0.5
     d_sets = [None if stub else torch.from_numpy(t_[0]).to(dev) for t_ in sets]
     last_set = (max(1, args.steps) - 1) % S
@@ -1035,10 +1103,15 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # one extra, untimed pass of instance 0 alone: kernel durations without the other streams' kernels sharing the GPU
-    worker(0, 1, iso := [None] * W, first=last_set)
-    iso_ms = iso[0]
-    iso_ctr = mps[0].cs_counters()
+    # --full: one extra, untimed pass of instance 0 alone: kernel durations without the other streams' kernels sharing the GPU
+    isolated = None
+    if args.full:
+        worker(0, 1, iso := [None] * W, first=last_set)
+        iso_ms = iso[0]
+        iso_ctr = mps[0].cs_counters()
+        isolated = {"achieved": (20 * iso_ctr[0] + 4 * iso_ctr[1] + 16 * iso_ctr[2]) / (iso_ms[0] * 1e-3) / 1e9 if iso_ms[0] > 0 else 0.0, "ms": float(iso_ms[0]),
+                    "reads": int(bounds[1] - bounds[0]),
+                    "note": "one launch of one mapper instance with nothing else on the GPU (untimed extra pass)"}
     ctr = np.sum([m_.cs_counters() for m_ in mps], axis=0)
     kmers, hits_voted, n_cand = int(ctr[0]), int(ctr[1]), int(ctr[2])
     mapped = hits["mapped"] == 1
@@ -1083,7 +1156,7 @@ def main():
                     traffic, traffic_source = v, "profiles/" + fn + " [" + k + "]"
         line = {
             "metric": "mapped reads/sec + SW Gcells/sec, 150bp vs GRCh38, at 1/2/4/8 MI355X",
-            "value": value, "unit": "reads/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "value": value, "unit": "reads/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "int32", "data": "synthetic",
             "config": {"workload": ("%d x %dbp %s synthetic reads per GPU per step (%.1f %% substitutions%s) vs a synthetic %.0f Mbp genome (24 contigs, repeat "
@@ -1101,14 +1174,13 @@ def main():
                           "candidate_search_stage_incl_host_sync": kms[7]},
             "per_read": {"candidates": n_cand / R, "index_hits": hits_voted / R, "kmers": kmers / R},
             "accuracy_rank0_shard": {"mapped": float(mapped.mean()), "within_band_of_truth": float(correct.mean()), "mapq_gt0": float((hits["mapq"] > 0).mean())},
-            "setup_s": {"genome_generation": t_gen, "encode+index_build": t_index, "index_entries": ref.index_entries if ref else 0},
+            "setup_s": {"genome_generation": t_gen, "encode+index_build": t_index, "index_entries": ref.index_entries if ref else 0,
+                        "read_sets_after_the_index": t_reads},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                          "traffic": traffic, "traffic_source": traffic_source, "kernel": dom, "kernel_note": dom_note, "kernel_ms_per_step": float(dom_ms),
                          "candidate_search": {"achieved": b_cs / (kms[0] * 1e-3) / 1e9 if kms[0] > 0 else 0.0, "frac": (b_cs / (kms[0] * 1e-3) / 1e9 / HBM_PEAK_GBS) if kms[0] > 0 else 0.0,
                                               "bytes_per_launch": b_cs / W, "launches_per_step": W, "ms_per_launch": float(kms[0] / W),
-                                              "isolated": {"achieved": (20 * iso_ctr[0] + 4 * iso_ctr[1] + 16 * iso_ctr[2]) / (iso_ms[0] * 1e-3) / 1e9 if iso_ms[0] > 0 else 0.0, "ms": float(iso_ms[0]),
-                                                           "reads": int(bounds[1] - bounds[0]),
-                                                           "note": "one launch of one mapper instance with nothing else on the GPU (untimed extra pass)"}},
+                                              "isolated": isolated},
                          "note": "`kernel` = the kernel with the largest GPU time per step of this workload; achieved = its algorithmic bytes (SURVEY.md 8d) / its "
                                  "HIP-event time on the launch stream.  Candidate search gathers from the canonical pair buckets (one 128-byte line per k-mer pair + "
                                  "16-byte chunks beyond 31 positions); random gathers on MI355X are bound by ~50 G requests/s "
@@ -1122,10 +1194,10 @@ def main():
                                     / (elapsed / args.steps) / 1e9,
             "stats_allreduce": stats,
         }
-        if world > 1 or stub:
+        if world > 1 or stub or not args.full:
             line["cpu_baseline"] = None  # the host baseline is timed on rank 0 of a 1-GPU run only
             line["end_to_end"] = None
-            if world > 1 and not args.no_end_to_end and (not stub or args.ngm_hip_exe):
+            if args.full and world > 1 and not args.no_end_to_end and (not stub or args.ngm_hip_exe):
                 # the real config 4: one 10 M-read input through the product, one process per GPU (the other ranks wait at the barrier below)
                 try:
                     if args.ngm_hip_exe:
@@ -1156,7 +1228,7 @@ def main():
     if ref is not None:
         ref.close()
     if rank == 0:
-        if world == 1 and not stub and args.heavy_tail_mbp > 0 and READ_LEN == 150:
+        if args.full and world == 1 and not stub and args.heavy_tail_mbp > 0 and READ_LEN == 150:
             del contigs, rows, sets, d_sets, views
             try:
                 line["heavy_tailed_genome"] = heavy_tail_leg(args, dev, local_rank, paired, affine, sens, workdir)

@@ -110,7 +110,7 @@ FAKE_NGM_HIP = textwrap.dedent('''\
 
 
 def test_bench_config4_leg_two_ranks(tmp_path):
-    """bench.py --gpus 2: after the weak-scaling loop rank 0 runs the product once over ONE input, sharded over both 'GPUs'
+    """bench.py --gpus 2 --full: after the weak-scaling loop rank 0 runs the product once over ONE input, sharded over both 'GPUs'
     (`ngm-hip -g 0,1 --shard-output`, here a stand-in program: no GPU), and reports it as `end_to_end` with "scaling": "strong"."""
     import json
     fake = tmp_path / "fake-ngm-hip"
@@ -120,7 +120,7 @@ def test_bench_config4_leg_two_ranks(tmp_path):
     env["MASTER_ADDR"] = "127.0.0.1"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
-           "--stub-mapper", "--genome-mbp", "2", "--reads-per-step", "4096", "--e2e-reads", "10000", "--ngm-hip-exe", str(fake)]
+           "--stub-mapper", "--genome-mbp", "2", "--reads-per-step", "4096", "--e2e-reads", "10000", "--ngm-hip-exe", str(fake), "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600, cwd=str(tmp_path))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
