@@ -299,6 +299,17 @@ int ngm_debug_pair_eval(uint64_t n, const float *pair_score, const int *dist, co
 int ngm_debug_select_top1(int device, int n_reads, const uint32_t *base, const uint32_t *count, uint64_t n_cand, const float *scores, const uint32_t *loc,
 		const uint32_t *strand_votes, uint32_t *winner, int32_t *mapq, int32_t *n_best, float *best_score);
 
+/* test hook: ngm_hip_batch_align (include/ngm_hip.h) of an AFFINE engine the way the mapper's align stage runs it: the DP, then the one
+ * finishing kernel from the trace matrix to CIGAR / NM / identity (affine_finish_kernel, csrc/cigar_device.h).  *n_fallback: the alignments
+ * whose CIGAR did not fit the kernel's row -- those are served by the old traceback kernel on the same batch and the host's string builder,
+ * like in the mapper.  The engine and the output records are those of include/ngm_hip.h.  Returns n, or a negative error code.  tests/test_gpu_align_finish.py compares it with the CPU oracle. */
+int ngm_debug_align_finish(void *engine /* ngm_hip_ctx * */, int mode, int n, const char *const *ref, const char *const *qry, void *out /* ngm_hip_align_out[n] */,
+		uint64_t *n_fallback);
+
+/* test hook: expand_pairs_kernel (csrc/gather_device.h) over host arrays: out[base[i] + k] = i for k < count[i]; out has n_cand entries, the
+ * ones no read owns are left as 0xFFFFFFFF. */
+int ngm_debug_expand_pairs(int device, int n_reads, const uint32_t *base, const uint32_t *count, uint64_t n_cand, uint32_t *out);
+
 /* of path counter [7] (reads searched by the heavy-read kernel, csrc/cs_heavy_device.h), summed over all batches: [0] reads given a second
  * pass (T from the first pass's maximum), [1] table passes started over with twice the parts, [2] reads a class could not certify and
  * queued again, [3] times the pool of global-memory vote tables had to grow (one more synchronisation in that batch) */

@@ -12,6 +12,7 @@
 #include "../../include/ngm_hip.h"
 #include "sw_device.h"
 #include "affine_device.h"
+#include "cigar_device.h"
 #include "jit.h"
 
 namespace ngm {
@@ -82,6 +83,7 @@ struct ngm_hip_ctx {
 	bool profiling = false;
 	hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
 	bool ev_valid[3] = {false, false, false};
+	bool trace_nibbles = false;   // the affine trace matrix in `dirs` holds the 4-bit trace of the packed DP kernel
 	std::string error;
 };
 
@@ -90,5 +92,15 @@ namespace ngm {
 int engine_reserve(ngm_hip_ctx *ctx, int n);
 // DP over ctx->packed / ctx->lens / ctx->blk_rows (filled by pack_pairs_kernel or gather_pairs_kernel)
 int engine_score_packed(ngm_hip_ctx *ctx, int mode, int n, float *d_scores, hipStream_t st);
-int engine_align_packed(ngm_hip_ctx *ctx, int mode, int n, int32_t *d_records, uint16_t *d_runs, int run_stride, hipStream_t st);
+// fin (affine personality only): behind the DP, affine_finish_kernel builds the strings from the trace matrix in one launch instead of the
+// traceback into d_runs; d_records keeps the DP's end cells, so engine_affine_traceback_packed can still be run on the batch
+struct AlignFinish {
+	CigarDevOut *out;                // n entries
+	char *bytes;                     // the compact byte stream and its capacity
+	unsigned long long capacity;
+	unsigned long long *counters;    // [0] stream cursor, [1] alignments left to the host; zeroed by the caller
+};
+int engine_align_packed(ngm_hip_ctx *ctx, int mode, int n, int32_t *d_records, uint16_t *d_runs, int run_stride, hipStream_t st, const AlignFinish *fin = nullptr);
+// the runs of the batch engine_align_packed(..., fin) has just run the DP on (trace matrix and end cells still in place)
+int engine_affine_traceback_packed(ngm_hip_ctx *ctx, int n, int32_t *d_records, uint16_t *d_runs, int run_stride, hipStream_t st);
 }  // namespace ngm

@@ -279,12 +279,29 @@ __global__ void pair_simple_kernel(int n_pairs, const uint32_t *__restrict__ can
 	info[pi] = found ? ((cur << 1) | 1) : 0;
 }
 
-// expands per-read candidate lists into pair arrays: pair j of read r gets pair_read[j] = r
-__global__ void expand_pairs_kernel(int n_reads, const uint32_t *__restrict__ cand_base, const uint32_t *__restrict__ cand_count,
+// expands per-read candidate lists into pair arrays: pair j of read r gets pair_read[j] = r.
+// The split of select_top1_kernel: a workgroup owns 256 consecutive reads, a thread writes the entries of its own read when it has at most
+// kSelectSmall candidates (on a genome without a heavy tail: all of them, 1.15 on average), the reads with more go to a list in LDS and are
+// taken a wave at a time.  (A workgroup per read was one 64-lane workgroup per 1.15 words: the launch, not the stores, set its time.)
+__global__ __launch_bounds__(256) void expand_pairs_kernel(int n_reads, const uint32_t *__restrict__ cand_base, const uint32_t *__restrict__ cand_count,
 		uint32_t *__restrict__ pair_read) {
-	const int r = blockIdx.x;
-	const uint32_t b = cand_base[r], n = cand_count[r];
-	for (uint32_t j = threadIdx.x; j < n; j += blockDim.x) pair_read[b + j] = (uint32_t) r;
+	__shared__ uint32_t s_big[256], s_nbig;
+	const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+	if (tid == 0) s_nbig = 0;
+	__syncthreads();
+	const int r = blockIdx.x * 256 + tid;
+	if (r < n_reads) {
+		const uint32_t b = cand_base[r], n = cand_count[r];
+		if (n <= kSelectSmall) { for (uint32_t j = 0; j < n; ++j) pair_read[b + j] = (uint32_t) r; }
+		else s_big[atomicAdd(&s_nbig, 1u)] = (uint32_t) tid;
+	}
+	__syncthreads();
+	const uint32_t nbig = s_nbig;
+	for (uint32_t i = (uint32_t) wv; i < nbig; i += 4u) {
+		const int rr = blockIdx.x * 256 + (int) s_big[i];
+		const uint32_t b = cand_base[rr], n = cand_count[rr];
+		for (uint32_t j = (uint32_t) lane; j < n; j += 64u) pair_read[b + j] = (uint32_t) rr;
+	}
 }
 
 // winners -> compact alignment batch

@@ -81,7 +81,7 @@ int score_candidates(ngm_mapper *m, int n, uint64_t np, int alt_dir) {
 	const ngm_ref *r = m->ref;
 	ngm_hip_ctx *eng = m->eng;
 	const int q = m->prm.qry_max_len, c = m->prm.corridor;
-	hipLaunchKernelGGL(ngm::expand_pairs_kernel, dim3(n), dim3(64), 0, m->st, n, m->d_cand_base.p, m->d_cand_count.p, m->d_pair_read.p);
+	hipLaunchKernelGGL(ngm::expand_pairs_kernel, dim3((n + 255) / 256), dim3(256), 0, m->st, n, m->d_cand_base.p, m->d_cand_count.p, m->d_pair_read.p);
 	const int nb = (int) ((np + ngm::kSlots - 1) / ngm::kSlots);
 	ngm::WindowGeom Gs{r->n_bases - 1, ((q + c) | 1) + 1, c >> 1};  // refMaxLen of ScoreBuffer.h:112
 	hipLaunchKernelGGL(ngm::gather_pairs_kernel, dim3(nb), dim3(256), 0, m->st, m->d_reads.p, m->d_read_len.p, q, r->d_genome, Gs,
@@ -1184,6 +1184,49 @@ static int map_impl(ngm_mapper *m, int n, const char *reads, const void *d_reads
 		MAP_HIP_TRY(hipGetLastError());
 		MAP_HIP_TRY(hipEventRecord(m->ev[6], m->st));
 		const bool was_prof = eng->profiling;
+		const bool affine = m->prm.personality == NGM_PERSONALITY_AFFINE;
+		// affine, strings on the GPU, one alignment per read: DP, then ONE finishing kernel from the trace matrix to the strings
+		// (affine_finish_kernel, cigar_device.h).  NGM_HIP_ALIGN_TAIL_SPLIT=1 keeps the three kernels traceback / compact_runs / cigar_strings
+		// and their downloads (tests); they also serve every other mode, and the alignments the finishing kernel leaves to the host.
+		static const bool tail_split = getenv("NGM_HIP_ALIGN_TAIL_SPLIT") != nullptr;
+		const bool finish = affine && dev_strings && topn == 1 && !tail_split;
+		const unsigned long long scap = (unsigned long long) na * 96ull + 4096ull;
+		unsigned long long n_runs_total = 0, n_str_total = 0;
+		if (dev_strings && (m->d_cigout.reserve(na) || m->d_str.reserve(scap) || m->p_cigout.reserve(na))) { ngm::pipeline_set_error("out of memory (CIGAR strings)"); return -12; }
+		if (finish) {
+			unsigned long long ctr[2] = {0, 0};   // [0] bytes of the string stream, [1] alignments left to the host
+			MAP_HIP_TRY(hipMemsetAsync(m->d_total.p + 8, 0, 16, m->st));   // the stage's one memset: stream cursor + fall-back counter
+			const ngm::AlignFinish fin{m->d_cigout.p, m->d_str.p, scap, m->d_total.p + 8};
+			eng->profiling = true;  // brackets DP vs finishing kernel with eng->ev[2]
+			if (int rc = ngm::engine_align_packed(eng, mode, na, m->d_records.p, m->d_runs.p, rs, m->st, &fin)) { eng->profiling = was_prof; ngm::pipeline_set_error("%s", ngm_hip_last_error(eng)); return rc; }
+			eng->profiling = was_prof;
+			MAP_HIP_TRY(hipEventRecord(m->ev[7], m->st));
+			MAP_HIP_TRY(hipEventRecord(m->ev[8], m->st));
+			MAP_HIP_TRY(hipMemcpyAsync(m->p_cigout.p, m->d_cigout.p, (size_t) na * sizeof(ngm::CigarDevOut), hipMemcpyDeviceToHost, m->st));
+			MAP_HIP_TRY(hipMemcpyAsync(ctr, m->d_total.p + 8, 16, hipMemcpyDeviceToHost, m->st));
+			stage_align.done_after(m->ev[8]);
+			MAP_HIP_TRY(hipStreamSynchronize(m->st));
+			n_str_total = std::min<unsigned long long>(ctr[0], scap);
+			str_base = n_str_total;
+			if (m->p_str.reserve(n_str_total + 1)) { ngm::pipeline_set_error("out of pinned host memory"); return -12; }
+			if (n_str_total && !sam) MAP_HIP_TRY(hipMemcpy(m->p_str.p, m->d_str.p, n_str_total, hipMemcpyDeviceToHost));
+			if (ctr[1]) {
+				// strings beyond the device's rows (rare): the old traceback on the same batch -- trace matrix and end cells are still there --
+				// and the host's builder for exactly those alignments
+				if (m->d_runs_c.reserve((size_t) na * rs)) { ngm::pipeline_set_error("out of device memory (runs)"); return -12; }
+				MAP_HIP_TRY(hipMemsetAsync(m->d_total.p, 0, 8, m->st));
+				if (int rc = ngm::engine_affine_traceback_packed(eng, na, m->d_records.p, m->d_runs.p, rs, m->st)) { ngm::pipeline_set_error("%s", ngm_hip_last_error(eng)); return rc; }
+				hipLaunchKernelGGL(ngm::compact_runs_kernel, dim3((na + 255) / 256), dim3(256), 0, m->st, na, m->d_records.p, m->d_runs.p, rs,
+						m->d_runs_c.p, m->d_total.p);
+				MAP_HIP_TRY(hipGetLastError());
+				MAP_HIP_TRY(hipMemcpyAsync(h_rec, m->d_records.p, (size_t) na * 8 * 4, hipMemcpyDeviceToHost, m->st));
+				MAP_HIP_TRY(hipMemcpyAsync(&n_runs_total, m->d_total.p, 8, hipMemcpyDeviceToHost, m->st));
+				MAP_HIP_TRY(hipStreamSynchronize(m->st));
+				if (m->p_runs.reserve(n_runs_total + 1)) { ngm::pipeline_set_error("out of pinned host memory"); return -12; }
+				h_runs = m->p_runs.p;
+				MAP_HIP_TRY(hipMemcpy(h_runs, m->d_runs_c.p, n_runs_total * 2, hipMemcpyDeviceToHost));
+			}
+		} else {
 		eng->profiling = true;  // brackets DP vs traceback with eng->ev[2]
 		if (int rc = ngm::engine_align_packed(eng, mode, na, m->d_records.p, m->d_runs.p, rs, m->st)) { eng->profiling = was_prof; ngm::pipeline_set_error("%s", ngm_hip_last_error(eng)); return rc; }
 		eng->profiling = was_prof;
@@ -1193,14 +1236,10 @@ static int map_impl(ngm_mapper *m, int n, const char *reads, const void *d_reads
 		hipLaunchKernelGGL(ngm::compact_runs_kernel, dim3((na + 255) / 256), dim3(256), 0, m->st, na, m->d_records.p, m->d_runs.p, rs,
 				m->d_runs_c.p, m->d_total.p);
 		MAP_HIP_TRY(hipGetLastError());
-		unsigned long long n_runs_total = 0, n_str_total = 0;
 		if (!dev_strings) { MAP_HIP_TRY(hipEventRecord(m->ev[8], m->st)); }   // (behind the stage's last kernel)
 		// CIGAR / MD / NM / identity on the GPU (cigar_device.h); NGM_HIP_HOST_CIGAR=1 keeps the host builders (tests)
 		if (dev_strings) {
-			const unsigned long long scap = (unsigned long long) na * 96ull + 4096ull;
-			if (m->d_cigout.reserve(na) || m->d_str.reserve(scap) || m->p_cigout.reserve(na)) { ngm::pipeline_set_error("out of memory (CIGAR strings)"); return -12; }
 			MAP_HIP_TRY(hipMemsetAsync(m->d_total.p + 8, 0, 8, m->st));
-			const bool affine = m->prm.personality == NGM_PERSONALITY_AFFINE;
 			if (affine) hipLaunchKernelGGL(ngm::cigar_strings_kernel<true>, dim3((na + 255) / 256), dim3(256), 0, m->st, na, m->d_records.p, m->d_runs_c.p, eng->packed.p, eng->RW, eng->FW,
 					m->d_read_len.p, m->d_a_read.p, m->prm.variant == NGM_VARIANT_OCL_CPU ? 1 : 0, m->prm.hard_clip, m->prm.silent_clip, m->d_cigout.p, m->d_str.p, scap,
 					(unsigned long long *) (m->d_total.p + 8), 0);
@@ -1220,10 +1259,11 @@ static int map_impl(ngm_mapper *m, int n, const char *reads, const void *d_reads
 		h_runs = m->p_runs.p;
 		MAP_HIP_TRY(hipMemcpy(h_runs, m->d_runs_c.p, n_runs_total * 2, hipMemcpyDeviceToHost));
 		if (dev_strings) {
-			n_str_total = std::min<unsigned long long>(n_str_total, (unsigned long long) na * 96ull + 4096ull);
+			n_str_total = std::min<unsigned long long>(n_str_total, scap);
 			str_base = n_str_total;
 			if (m->p_str.reserve(n_str_total + 1)) { ngm::pipeline_set_error("out of pinned host memory"); return -12; }
 			if (n_str_total && !sam) MAP_HIP_TRY(hipMemcpy(m->p_str.p, m->d_str.p, n_str_total, hipMemcpyDeviceToHost));
+		}
 		}
 	}
 	stage_align.done();
@@ -1571,6 +1611,26 @@ int ngm_debug_select_top1(int device, int n_reads, const uint32_t *base, const u
 	MAP_HIP_TRY(hipMemcpy(best_score, d_best.p, (size_t) n_reads * 4, hipMemcpyDeviceToHost));
 	d_base.release(); d_count.release(); d_loc.release(); d_sv.release(); d_win.release(); d_mq.release(); d_nb.release(); d_sc.release(); d_best.release();
 	return 0;
+}
+
+int ngm_debug_expand_pairs(int device, int n_reads, const uint32_t *base, const uint32_t *count, uint64_t n_cand, uint32_t *out) {
+	if (n_reads <= 0 || !base || !count || (n_cand && !out)) return -22;
+	DevGuard g(device);
+	ngm::DevBuf<uint32_t> d_base, d_count, d_out;
+	auto run = [&]() -> int {
+		if (d_base.reserve(n_reads) || d_count.reserve(n_reads) || d_out.reserve((size_t) std::max<uint64_t>(n_cand, 1))) { ngm::pipeline_set_error("out of device memory (ngm_debug_expand_pairs)"); return -12; }
+		MAP_HIP_TRY(hipMemcpy(d_base.p, base, (size_t) n_reads * 4, hipMemcpyHostToDevice));
+		MAP_HIP_TRY(hipMemcpy(d_count.p, count, (size_t) n_reads * 4, hipMemcpyHostToDevice));
+		MAP_HIP_TRY(hipMemset(d_out.p, 0xFF, (size_t) std::max<uint64_t>(n_cand, 1) * 4));
+		hipLaunchKernelGGL(ngm::expand_pairs_kernel, dim3((n_reads + 255) / 256), dim3(256), 0, 0, n_reads, d_base.p, d_count.p, d_out.p);
+		MAP_HIP_TRY(hipGetLastError());
+		MAP_HIP_TRY(hipDeviceSynchronize());
+		if (n_cand) MAP_HIP_TRY(hipMemcpy(out, d_out.p, (size_t) n_cand * 4, hipMemcpyDeviceToHost));
+		return 0;
+	};
+	const int rc = run();
+	d_base.release(); d_count.release(); d_out.release();
+	return rc;
 }
 
 int ngm_mapper_heavy_counters(ngm_mapper *m, uint64_t out[4]) {

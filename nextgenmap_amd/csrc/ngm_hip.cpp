@@ -2,6 +2,7 @@
 // dispatch.  Compiled by hipcc for gfx950 only.  There is deliberately no CPU fallback: without a
 // HIP device every entry point fails loudly.
 #include "../../include/ngm_hip.h"
+#include "../../include/ngm_pipeline.h"
 
 #include <hip/hip_runtime.h>
 
@@ -193,7 +194,14 @@ int engine_score_packed(ngm_hip_ctx *ctx, int mode, int n, float *d_scores, hipS
 	return 0;
 }
 
-int engine_align_packed(ngm_hip_ctx *ctx, int mode, int n, int32_t *d_records, uint16_t *d_runs, int run_stride, hipStream_t st) {
+int engine_affine_traceback_packed(ngm_hip_ctx *ctx, int n, int32_t *d_records, uint16_t *d_runs, int run_stride, hipStream_t st) {
+	hipLaunchKernelGGL(ngm::affine_traceback_kernel, dim3((n + 255) / 256), dim3(256), 0, st, ctx->dirs.p, d_records, d_runs, n,
+			ctx->q, ctx->c + 1, run_stride, (const uint32_t *) ctx->packed.p, ctx->RW, ctx->FW, ctx->trace_nibbles ? 1 : 0);
+	HIP_TRY(ctx, hipGetLastError());
+	return 0;
+}
+
+int engine_align_packed(ngm_hip_ctx *ctx, int mode, int n, int32_t *d_records, uint16_t *d_runs, int run_stride, hipStream_t st, const AlignFinish *fin) {
 	const int am = mode & NGM_MODE_ALIGN_MASK;
 	const int nb = n_blocks_of(n);
 	if (ctx->prm.personality == NGM_PERSONALITY_AFFINE) {
@@ -219,11 +227,16 @@ int engine_align_packed(ngm_hip_ctx *ctx, int mode, int n, int32_t *d_records, u
 					(const uint16_t *) ctx->blk_rows.p, (float *) nullptr, ctx->dirs.p, d_records, n, nb, ctx->RW, ctx->q, ctx->KA));
 		}
 		if (ctx->profiling) HIP_TRY(ctx, hipEventRecord(ctx->ev[2], st));
-		hipLaunchKernelGGL(ngm::affine_traceback_kernel, dim3((n + 255) / 256), dim3(256), 0, st, ctx->dirs.p, d_records, d_runs, n,
-				ctx->q, CP, run_stride, (const uint32_t *) ctx->packed.p, ctx->RW, ctx->FW, pk ? 1 : 0);
+		ctx->trace_nibbles = pk != nullptr;
+		if (!fin) return engine_affine_traceback_packed(ctx, n, d_records, d_runs, run_stride, st);
+		if (pk) hipLaunchKernelGGL(ngm::affine_finish_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, st, n, (const uint32_t *) ctx->dirs.p, (const int32_t *) d_records,
+				(const uint32_t *) ctx->packed.p, (const uint16_t *) ctx->lens.p, ctx->q, CP, ctx->RW, ctx->FW, fin->out, fin->bytes, fin->capacity, fin->counters);
+		else hipLaunchKernelGGL(ngm::affine_finish_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, st, n, (const uint32_t *) ctx->dirs.p, (const int32_t *) d_records,
+				(const uint32_t *) ctx->packed.p, (const uint16_t *) ctx->lens.p, ctx->q, CP, ctx->RW, ctx->FW, fin->out, fin->bytes, fin->capacity, fin->counters);
 		HIP_TRY(ctx, hipGetLastError());
 		return 0;
 	}
+	if (fin) { set_error(ctx, "the finishing kernel serves the affine personality only"); return -22; }
 	const int DW = ngm::dir_words(ctx->c);
 	if (ctx->dirs.reserve((size_t) nb * ctx->q * DW * ngm::kSlots)) { set_error(ctx, "out of device memory for the direction matrix"); return -12; }
 	// local alignments whose re-based values fit 16 bits (the score kernel's condition): two pairs per lane, see sw_align_pk_kernel
@@ -506,6 +519,74 @@ int ngm_hip_batch_align(ngm_hip_ctx *ctx, int mode, int n, const char *const *re
 	}
 	for (int i = 0; i < n; ++i) {
 		ngm::build_cigar_md(cp, ctx->h_records.p + (size_t) i * 8, ctx->h_runs.p + (size_t) i * rs, ref[i], qry[i], &out[i], (cp.alt && dir && dir[i]) ? 1 : 0);
+	}
+	return n;
+}
+
+// test hook (include/ngm_pipeline.h): ngm_hip_batch_align of the affine personality the way the mapper's align stage runs it -- DP, then
+// affine_finish_kernel; the alignments that kernel leaves to the host (counted in *n_fallback) get the old traceback on the same batch.
+int ngm_debug_align_finish(void *engine, int mode, int n, const char *const *ref, const char *const *qry, void *out_records, uint64_t *n_fallback) {
+	ngm_hip_ctx *ctx = (ngm_hip_ctx *) engine;
+	ngm_hip_align_out *out = (ngm_hip_align_out *) out_records;
+	if (!ctx || !out || !n_fallback) return -22;
+	*n_fallback = 0;
+	if (n <= 0) return 0;
+	if (ctx->prm.personality != NGM_PERSONALITY_AFFINE) { set_error(ctx, "ngm_debug_align_finish: affine personality only"); return -22; }
+	const int am = mode & NGM_MODE_ALIGN_MASK;
+	if (am != NGM_MODE_LOCAL && am != NGM_MODE_END_TO_END) { set_error(ctx, "unsupported alignment mode %d", am); return -22; }
+	ScopedDevice sd(ctx->device);
+	const size_t rl = ctx->rl, q = ctx->q;
+	const int rs = ngm::run_stride(ctx->q, ctx->c);
+	if (ctx->h_ref.reserve((size_t) n * rl) || ctx->h_qry.reserve((size_t) n * q) || ctx->d_ref.reserve((size_t) n * rl) ||
+			ctx->d_qry.reserve((size_t) n * q) || ctx->d_records.reserve((size_t) n * 8) || ctx->d_runs.reserve((size_t) n * rs) ||
+			ctx->h_records.reserve((size_t) n * 8) || ctx->h_runs.reserve((size_t) n * rs)) {
+		set_error(ctx, "out of memory staging %d pairs", n);
+		return -12;
+	}
+	for (int i = 0; i < n; ++i) {
+		memcpy(ctx->h_ref.p + (size_t) i * rl, ref[i], rl);
+		memcpy(ctx->h_qry.p + (size_t) i * q, qry[i], q);
+	}
+	const unsigned long long scap = (unsigned long long) n * ngm::kCigarRow + 4096ull;
+	ngm::DevBuf<ngm::CigarDevOut> d_out;
+	ngm::DevBuf<char> d_str;
+	ngm::DevBuf<unsigned long long> d_ctr;
+	std::vector<ngm::CigarDevOut> h_out((size_t) n);
+	std::vector<char> h_str((size_t) scap);
+	unsigned long long ctr[2] = {0, 0};
+	auto run = [&]() -> int {
+		if (d_out.reserve(n) || d_str.reserve(scap) || d_ctr.reserve(2)) { set_error(ctx, "out of device memory (ngm_debug_align_finish)"); return -12; }
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ref.p, ctx->h_ref.p, (size_t) n * rl, hipMemcpyHostToDevice, ctx->stream));
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->d_qry.p, ctx->h_qry.p, (size_t) n * q, hipMemcpyHostToDevice, ctx->stream));
+		HIP_TRY(ctx, hipMemsetAsync(d_ctr.p, 0, 16, ctx->stream));
+		if (int r = engine_reserve(ctx, n)) return r;
+		if (int r = launch_pack(ctx, n, ctx->d_ref.p, ctx->d_qry.p, ctx->stream)) return r;
+		const ngm::AlignFinish fin{d_out.p, d_str.p, scap, d_ctr.p};
+		if (int r = ngm::engine_align_packed(ctx, mode, n, ctx->d_records.p, ctx->d_runs.p, rs, ctx->stream, &fin)) return r;
+		HIP_TRY(ctx, hipMemcpyAsync(h_out.data(), d_out.p, (size_t) n * sizeof(ngm::CigarDevOut), hipMemcpyDeviceToHost, ctx->stream));
+		HIP_TRY(ctx, hipMemcpyAsync(ctr, d_ctr.p, 16, hipMemcpyDeviceToHost, ctx->stream));
+		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+		const unsigned long long used = std::min(ctr[0], scap);
+		if (used) HIP_TRY(ctx, hipMemcpy(h_str.data(), d_str.p, (size_t) used, hipMemcpyDeviceToHost));
+		if (ctr[1]) {
+			if (int r = ngm::engine_affine_traceback_packed(ctx, n, ctx->d_records.p, ctx->d_runs.p, rs, ctx->stream)) return r;
+			HIP_TRY(ctx, hipMemcpyAsync(ctx->h_records.p, ctx->d_records.p, sizeof(int32_t) * 8 * (size_t) n, hipMemcpyDeviceToHost, ctx->stream));
+			HIP_TRY(ctx, hipMemcpyAsync(ctx->h_runs.p, ctx->d_runs.p, sizeof(uint16_t) * (size_t) rs * n, hipMemcpyDeviceToHost, ctx->stream));
+			HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+		}
+		return 0;
+	};
+	const int rc = run();
+	d_out.release(); d_str.release(); d_ctr.release();
+	if (rc) return rc;
+	*n_fallback = ctr[1];
+	for (int i = 0; i < n; ++i) {
+		const ngm::CigarDevOut &dv = h_out[(size_t) i];
+		if (!(dv.flags & 1)) { ngm::build_cigar_affine(ctx->h_records.p + (size_t) i * 8, ctx->h_runs.p + (size_t) i * rs, ref[i], qry[i], ctx->q, &out[i]); continue; }
+		memcpy(out[i].cigar, h_str.data() + dv.cig_off, dv.cig_len); out[i].cigar[dv.cig_len] = 0;
+		memcpy(out[i].md, h_str.data() + dv.md_off, dv.md_len); out[i].md[dv.md_len] = 0;
+		out[i].position_offset = dv.position_offset; out[i].qstart = dv.qstart; out[i].qend = dv.qend;
+		out[i].score_token = dv.score_token; out[i].identity = dv.identity; out[i].nm = dv.nm;
 	}
 	return n;
 }

@@ -76,6 +76,7 @@ def load_library():
                                          C.c_int, C.c_void_p]
     lib.ngm_hip_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     lib.ngm_hip_set_profiling.argtypes = [C.c_void_p, C.c_int]
+    lib.ngm_debug_align_finish.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
     _lib = lib
     return lib
 
@@ -144,8 +145,10 @@ class Engine:
         assert r == n
         return out
 
-    def BatchAlign(self, mode, ref, qry, dirs=None):
-        """-> list of dicts(cigar, md, position_offset, qstart, qend, score_token, identity, nm)."""
+    def BatchAlign(self, mode, ref, qry, dirs=None, finish=False):
+        """-> list of dicts(cigar, md, position_offset, qstart, qend, score_token, identity, nm).
+        finish (affine personality): the mapper's align stage instead of the drop-in's -- DP, then the one finishing kernel from the
+        trace matrix to the strings; self.last_fallback = the alignments that kernel left to the old traceback and the host."""
         n, ref, qry, rp, qp = self._ptr_lists(ref, qry)
         stride = 4 * max(1, self.q)  # AlignmentBuffer.cpp:106-109
         cig = np.zeros((n, stride), dtype=np.uint8)
@@ -157,7 +160,12 @@ class Engine:
             outs[i].cigar = cig.ctypes.data + i * stride
             outs[i].md = md.ctypes.data + i * stride
         d = None if dirs is None else np.ascontiguousarray(dirs, dtype=np.uint8)
-        r = self._check(self.lib.ngm_hip_batch_align(self.h, mode, n, rp, qp, outs, None if d is None else d.ctypes.data), n)
+        if finish:
+            fb = C.c_uint64(0)
+            r = self._check(self.lib.ngm_debug_align_finish(self.h, mode, n, rp, qp, outs, C.byref(fb)), n)
+            self.last_fallback = int(fb.value)
+        else:
+            r = self._check(self.lib.ngm_hip_batch_align(self.h, mode, n, rp, qp, outs, None if d is None else d.ctypes.data), n)
         assert r == n
         res = []
         for i in range(n):
