@@ -196,7 +196,8 @@ typedef struct ngm_sam_options {
 	int bs_mapping;             /* Config "bs_mapping": the ZS:Z tag (src/writer/SAMWriter.cpp:173-187) */
 	int slam_seq;               /* Config SLAM_SEQ != 0: the TC:i / RA:Z / MP:Z tags (src/writer/SAMWriter.cpp:203-221, GenericReadWriter.h:87-186) */
 	int bam;                    /* Config "bam": the records as BAM (src/writer/BAMWriter.cpp:147-375), in BGZF blocks written by the GPU -- what
-	                             * ngm_mapper_map_sam returns is then a piece of the BAM file (whole BGZF members); not with slam_seq */
+	                             * ngm_mapper_map_sam returns is then a piece of the BAM file (whole BGZF members); with slam_seq the TC:i / RA:Z /
+	                             * MP:Z tags follow RG (src/writer/BAMWriter.cpp:273-292) */
 } ngm_sam_options;
 int ngm_mapper_set_sam_options(ngm_mapper *m, const ngm_sam_options *o);
 typedef struct ngm_sam_read {   /* per read: where its name is, how long its quality string is */
@@ -211,6 +212,13 @@ typedef struct ngm_sam_read {   /* per read: where its name is, how long its qua
  * mapped, lines written.  kernel_ms (optional): GPU time of the formatting kernels. */
 long long ngm_mapper_map_sam(ngm_mapper *m, int n, const char *reads, const char *quals, const char *names, size_t names_bytes,
 		const ngm_sam_read *meta, char *out, size_t out_cap, uint64_t stats[3], float *kernel_ms);
+/* The same for reads the caller has trimmed (`ngm -5 / --max-polya`: the rows and quality rows hold the trimmed read, as for every
+ * entry point).  polya_trimmed: per read, the bases --max-polya cut off (MappedRead::polyATrimmed, src/ReadProvider.cpp:428-443);
+ * non-null: every record carries it as XA:i (src/writer/SAMWriter.cpp:192-194, :355-357; BAMWriter.cpp:258-260, :356-358), 0 included.
+ * NULL: no XA:i tag -- ngm_mapper_map_sam is this call with NULL.  A read whose row is empty (all NUL) is legal: it has no candidates
+ * and is written as an unmapped record with empty SEQ and QUAL. */
+long long ngm_mapper_map_sam_trimmed(ngm_mapper *m, int n, const char *reads, const char *quals, const char *names, size_t names_bytes,
+		const ngm_sam_read *meta, const uint16_t *polya_trimmed, char *out, size_t out_cap, uint64_t stats[3], float *kernel_ms);
 int ngm_mapper_sam_fetch(ngm_mapper *m, char *out, size_t out_cap);
 
 /* Several mappers on ONE input (ngm-hip hands batches to a mapper per worker thread / per GPU, like NextGenMap hands them to

@@ -184,7 +184,7 @@ void ngm_mapper_destroy(ngm_mapper *m) {
 	m->d_pair_info.release(); m->p_pair_info.release(); m->d_sam_contig_start.release();
 	m->d_pair_out.release(); m->d_pair_top.release(); m->d_pair_tied_n.release(); m->d_pair_list.release(); m->p_pair_out.release(); m->p_pair_top.release(); m->p_pair_tied_n.release();
 	m->d_sam_contig_names.release(); m->d_sam_rg.release(); m->d_sam_names.release(); m->d_sam_text.release(); m->d_sam_contig_off.release(); m->d_sam_len.release(); m->d_sam_off.release();
-	m->d_sam_quals.release(); m->d_sam_meta.release(); m->d_sam_refs.release(); m->d_sam_hits.release(); m->p_sam_hits.release(); m->p_sam_refs.release(); m->p_sam_extra.release();
+	m->d_sam_quals.release(); m->d_sam_polya.release(); m->d_sam_meta.release(); m->d_sam_refs.release(); m->d_sam_hits.release(); m->p_sam_hits.release(); m->p_sam_refs.release(); m->p_sam_extra.release();
 	for (auto &e : m->ev) if (e) (void) hipEventDestroy(e);
 	for (auto &e : m->cev) if (e) (void) hipEventDestroy(e);
 	for (auto &e : m->oev) if (e) (void) hipEventDestroy(e);
@@ -232,7 +232,7 @@ int ngm_mapper_cs_fetch(ngm_mapper *m, uint64_t *loc, uint8_t *strand, float *vo
 }
 
 // the SAM stage of a call (ngm_mapper_map_sam): inputs the records need beyond the reads, where the text goes
-struct SamCall { const char *quals; const char *names; size_t names_bytes; const ngm::SamMeta *meta; char *out; size_t out_cap; uint64_t *stats; long long text_bytes; float kernel_ms; };
+struct SamCall { const char *quals; const char *names; size_t names_bytes; const ngm::SamMeta *meta; const uint16_t *polya; char *out; size_t out_cap; uint64_t *stats; long long text_bytes; float kernel_ms; };
 static int map_impl(ngm_mapper *m, int n, const char *reads, const void *d_reads_ext, ngm_hit *hits, char *cigars, char *mds, bool paired, SamCall *sam = nullptr);
 
 int ngm_mapper_map_se(ngm_mapper *m, int n, const char *reads, ngm_hit *hits, char *cigars, char *mds) {
@@ -251,7 +251,6 @@ int ngm_mapper_map_pe_resident(ngm_mapper *m, int n, const char *reads, const vo
 int ngm_mapper_set_sam_options(ngm_mapper *m, const ngm_sam_options *o) {
 	if (!m || !o) return -22;
 	DevGuard g(m->ref->device);
-	if (o->bam && o->slam_seq) { ngm::pipeline_set_error("ngm_mapper_set_sam_options: BAM records with SLAM-seq tags are formatted by the caller"); return -22; }
 	m->sam_opt = *o;
 	m->sam_opt.rg_id = nullptr;
 	if (o->bam && !m->bz) { m->bz = ngm_bgzf_create(m->ref->device); if (!m->bz) return -12; }
@@ -279,8 +278,13 @@ static_assert(sizeof(ngm_sam_read) == sizeof(ngm::SamMeta) && sizeof(ngm_sam_rea
 
 long long ngm_mapper_map_sam(ngm_mapper *m, int n, const char *reads, const char *quals, const char *names, size_t names_bytes, const ngm_sam_read *meta,
 		char *out, size_t out_cap, uint64_t stats[3], float *kernel_ms) {
+	return ngm_mapper_map_sam_trimmed(m, n, reads, quals, names, names_bytes, meta, nullptr, out, out_cap, stats, kernel_ms);
+}
+
+long long ngm_mapper_map_sam_trimmed(ngm_mapper *m, int n, const char *reads, const char *quals, const char *names, size_t names_bytes, const ngm_sam_read *meta,
+		const uint16_t *polya_trimmed, char *out, size_t out_cap, uint64_t stats[3], float *kernel_ms) {
 	if (!m || n < 0 || (n > 0 && (!reads || !quals || !meta))) return -22;
-	SamCall sc{quals, names, names_bytes, reinterpret_cast<const ngm::SamMeta *>(meta), out, out_cap, stats, 0, 0.f};
+	SamCall sc{quals, names, names_bytes, reinterpret_cast<const ngm::SamMeta *>(meta), polya_trimmed, out, out_cap, stats, 0, 0.f};
 	m->argos_text = false;
 	const int rc = map_impl(m, n, reads, nullptr, nullptr, nullptr, nullptr, m->sam_opt.paired != 0, &sc);
 	if (rc < 0) return rc;
@@ -654,6 +658,10 @@ static int map_impl(ngm_mapper *m, int n, const char *reads, const void *d_reads
 		MAP_HIP_TRY(hipMemcpyAsync(m->d_sam_quals.p, sam->quals, (size_t) n * q, hipMemcpyHostToDevice, m->st));
 		if (sam->names_bytes) MAP_HIP_TRY(hipMemcpyAsync(m->d_sam_names.p, sam->names, sam->names_bytes, hipMemcpyHostToDevice, m->st));
 		MAP_HIP_TRY(hipMemcpyAsync(m->d_sam_meta.p, sam->meta, (size_t) n * sizeof(ngm::SamMeta), hipMemcpyHostToDevice, m->st));
+		if (sam->polya && n > 0) {
+			if (m->d_sam_polya.reserve((size_t) n)) { ngm::pipeline_set_error("out of memory (SAM stage)"); return -12; }
+			MAP_HIP_TRY(hipMemcpyAsync(m->d_sam_polya.p, sam->polya, (size_t) n * sizeof(uint16_t), hipMemcpyHostToDevice, m->st));
+		}
 		hits = m->p_sam_hits.p;
 	}
 	GpuStage stage_cs(m);
@@ -1394,11 +1402,14 @@ static int map_impl(ngm_mapper *m, int n, const char *reads, const void *d_reads
 		S.genome = r->d_genome; S.contig_start = m->d_sam_contig_start.p;
 		S.unit_len = m->d_sam_len.p; S.unit_off = m->d_sam_off.p; S.counters = m->d_total.p + 16;
 		S.bam = m->sam_opt.bam ? 1 : 0;
+		S.polya = sam->polya ? m->d_sam_polya.p : nullptr;
 		hipEvent_t e0 = m->cev[0], e1 = m->cev[1];
 		MAP_HIP_TRY(hipEventRecord(e0, m->st));
 		unsigned long long total = 0;
 		if (units > 0) {
-			hipLaunchKernelGGL(ngm::sam_lengths_kernel, dim3((units + 255) / 256), dim3(256), 0, m->st, S, units);
+			const bool bam_slam = S.bam && S.slam_seq;   // (BAM records with SLAM-seq tags: kernels of their own, sam_device.h)
+			if (bam_slam) hipLaunchKernelGGL(ngm::sam_lengths_kernel<true>, dim3((units + 255) / 256), dim3(256), 0, m->st, S, units);
+			else hipLaunchKernelGGL(ngm::sam_lengths_kernel<false>, dim3((units + 255) / 256), dim3(256), 0, m->st, S, units);
 			MAP_HIP_TRY(hipGetLastError());
 			size_t tmp_bytes = 0;
 			(void) rocprim::exclusive_scan(nullptr, tmp_bytes, m->d_sam_len.p, m->d_sam_off.p, 0u, (size_t) units + 1, rocprim::plus<uint32_t>(), m->st);
@@ -1418,7 +1429,8 @@ static int map_impl(ngm_mapper *m, int n, const char *reads, const void *d_reads
 			if (m->d_sam_text.reserve((size_t) total + 16)) { ngm::pipeline_set_error("out of device memory (SAM text)"); return -12; }
 			S.out = m->d_sam_text.p;
 			stage_sam.acquire();
-			hipLaunchKernelGGL(ngm::sam_write_kernel, dim3((units + 255) / 256), dim3(256), 0, m->st, S, units);
+			if (bam_slam) hipLaunchKernelGGL(ngm::sam_write_kernel<true>, dim3((units + 255) / 256), dim3(256), 0, m->st, S, units);
+			else hipLaunchKernelGGL(ngm::sam_write_kernel<false>, dim3((units + 255) / 256), dim3(256), 0, m->st, S, units);
 			MAP_HIP_TRY(hipGetLastError());
 		}
 		MAP_HIP_TRY(hipEventRecord(e1, m->st));

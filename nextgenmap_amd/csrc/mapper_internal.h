@@ -134,6 +134,7 @@ struct ngm_mapper {
 	ngm::DevBuf<uint32_t> d_sam_contig_off, d_sam_len, d_sam_off;
 	ngm::DevBuf<uint64_t> d_sam_contig_start;
 	ngm::DevBuf<uint8_t> d_sam_quals;
+	ngm::DevBuf<uint16_t> d_sam_polya;   // ngm_mapper_map_sam_trimmed: bases --max-polya cut per read (XA:i)
 	ngm::DevBuf<ngm::SamMeta> d_sam_meta;
 	ngm::DevBuf<ngm::SamRef> d_sam_refs;
 	ngm::DevBuf<ngm_hit> d_sam_hits;

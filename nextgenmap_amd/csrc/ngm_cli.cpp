@@ -11,7 +11,8 @@
 // Everything heavy (index, candidate search, score, align) happens on the GPU behind ngm_mapper_*.
 // Single-end and paired-end (-p -q interleaved, --qry1/--qry2), --affine, -n/--strata, SAM and BAM (--bam) output, one or
 // several GPUs (-g 0,1,...), and --argos (ScoreWriter's lines, src/writer/ScoreWriter.cpp: every scored candidate of a read, ordered on the
-// GPU -- single-end only, see ngm_mapper_map_argos).  Not supported (rejected loudly): bisulfite / SLAM-seq, --vcf with --bs-mapping, SAM/BAM *input*.
+// GPU -- single-end only, see ngm_mapper_map_argos), bisulfite (--bs-mapping) and SLAM-seq (--slam-seq) mapping, -5/--trim5 and --max-polya
+// (csrc/read_trim.h).  Not supported (rejected loudly): --vcf with --bs-mapping, --max-polya with --argos or --vcf, SAM/BAM *input*, --config.
 //
 // Pass 2 is a pipeline, not a loop:
 //   splitter (1 thread)   cuts the input into batches: for plain 4-line FASTQ it only counts line ends in the mapped file
@@ -63,6 +64,7 @@
 #include "../../include/ngm_pipeline.h"
 #include "bam_writer.h"
 #include "gz_inflate.h"
+#include "read_trim.h"
 #include "thread_pool.h"
 
 namespace {
@@ -126,6 +128,7 @@ struct Opts {
 	int match = 10, mismatch = 15, gap_read = -1, gap_ref = -1, gap_extend = -1, affine = 0, hard_clip = 0, silent_clip = 0, no_unal = 0, fast_pairing = 0, broken_pairs = 0, max_cmrs = 2147483647;
 	int skip_save = 0, bam = 0, workers = 2, serial_reader = 0;
 	int argos = 0, kmer_min_set = 0;
+	ngm::trim::Options trim;   // -5/--trim5, --max-polya (Options.h:103-104)
 	float argos_min = 0.f;   // --argos-min-score (Default(ARGOS_MINSCORE, 0), Config.cpp:505)
 	int bs_mapping = 0, bs_cutoff = 6, match_tt = -1, match_tc = -1, match_set = 0, mismatch_set = 0, slam_seq = 0;
 	std::vector<int> devices;
@@ -147,7 +150,7 @@ Opts parse(int argc, char **argv) {
 	Opts o;
 	for (int i = 1; i < argc; ++i) { if (i > 1) o.cmdline += " "; o.cmdline += argv[i]; }  // Config.cpp:565-574
 	enum { KSKIP = 1000, HARD, SILENT, KMIN, MB, MMP, GRP, GFP, MAXCMRS, NOUNAL, NOPROG, MAXRL, BINSZ, MAXKF, VFAST, FAST, SENS, VSENS, DEVICE,
-		SKIPSAVE, BATCH, VARIANT, SHARD, SHARDOUT, KEEPSHARDS, BAMOUT, WORKERS, SERIAL, AFFINE, GEP, PEDELIM, STRATA, BSMAP, BSCUT, MBTT, MBTC, SLAM, FASTPAIR, BROKENPAIRS, REFSCOREBUF, STATSFD, RG0, RG_LAST = RG0 + 11, ARGOS, ARGOSMIN, VCF, UNSUPPORTED };
+		SKIPSAVE, BATCH, VARIANT, SHARD, SHARDOUT, KEEPSHARDS, BAMOUT, WORKERS, SERIAL, AFFINE, GEP, PEDELIM, STRATA, BSMAP, BSCUT, MBTT, MBTC, SLAM, FASTPAIR, BROKENPAIRS, REFSCOREBUF, STATSFD, MAXPOLYA, RG0, RG_LAST = RG0 + 11, ARGOS, ARGOSMIN, VCF, UNSUPPORTED };
 	static const option lo[] = {
 		{"ref", required_argument, 0, 'r'}, {"qry", required_argument, 0, 'q'}, {"output", required_argument, 0, 'o'},
 		{"cpu-threads", required_argument, 0, 't'}, {"gpu", no_argument, 0, 'g'}, {"sensitivity", required_argument, 0, 's'},
@@ -172,10 +175,11 @@ Opts parse(int argc, char **argv) {
 		{"affine", no_argument, 0, AFFINE}, {"gap-extend-penalty", required_argument, 0, GEP}, {"bam", no_argument, 0, BAMOUT}, {"workers", required_argument, 0, WORKERS}, {"serial-reader", no_argument, 0, SERIAL}, {"bs-mapping", no_argument, 0, BSMAP},
 		{"bs-cutoff", required_argument, 0, BSCUT}, {"match-bonus-tt", required_argument, 0, MBTT}, {"match-bonus-tc", required_argument, 0, MBTC},
 		{"slam-seq", required_argument, 0, SLAM}, {"topn", required_argument, 0, 'n'}, {"strata", no_argument, 0, STRATA},
-		{"argos", no_argument, 0, ARGOS}, {"argos-min-score", required_argument, 0, ARGOSMIN}, {"vcf", required_argument, 0, VCF}, {"config", required_argument, 0, UNSUPPORTED},
+		{"argos", no_argument, 0, ARGOS}, {"argos-min-score", required_argument, 0, ARGOSMIN}, {"vcf", required_argument, 0, VCF},
+		{"trim5", required_argument, 0, '5'}, {"max-polya", required_argument, 0, MAXPOLYA}, {"config", required_argument, 0, UNSUPPORTED},
 		{0, 0, 0, 0}};
 	int c, idx = 0;
-	while ((c = getopt_long(argc, argv, "o:q:r:t:gs:k:lei:R:C:Q:p1:2:I:X:n:", lo, &idx)) != -1) {
+	while ((c = getopt_long(argc, argv, "o:q:r:t:gs:k:lei:R:C:Q:p1:2:I:X:n:bd:5:", lo, &idx)) != -1) {
 		switch (c) {
 		case 'r': o.ref = optarg; break;
 		case 'q': o.qry = optarg; break;
@@ -186,7 +190,9 @@ Opts parse(int argc, char **argv) {
 		case STRATA: o.strata = 1; break;
 		case 'I': o.min_insert = atoi(optarg); break;
 		case 'X': o.max_insert = atoi(optarg); break;
-		case PEDELIM: o.pe_delimiter = optarg[0]; break;
+		case PEDELIM: case 'd': o.pe_delimiter = optarg[0]; break;
+		case '5': o.trim.trim5 = atoi(optarg); if (o.trim.trim5 < 0) die("-5/--trim5 expects a number of bases >= 0"); break;
+		case MAXPOLYA: o.trim.max_polya = atoi(optarg); break;
 		case 'o': o.out = optarg; break;
 		case 't': break;  // host threads follow the machine (NGM_HIP_HOST_THREADS)
 		case 'g':  // "-g" or "-g 0,1,..." (optional list without '=', src/config/Config.cpp:624-647); the GPU is not optional here
@@ -233,7 +239,7 @@ Opts parse(int argc, char **argv) {
 		case SENS: o.sensitive = 1; break;
 		case VSENS: o.very_sensitive = 1; break;
 		case DEVICE: o.device = atoi(optarg); o.devices.assign(1, o.device); break;
-		case BAMOUT: o.bam = 1; break;
+		case BAMOUT: case 'b': o.bam = 1; break;
 		case WORKERS: o.workers = std::max(1, atoi(optarg)); break;
 		case SERIAL: o.serial_reader = 1; break;
 		case BATCH: o.batch = std::max(1024, atoi(optarg)); break;
@@ -267,6 +273,7 @@ Opts parse(int argc, char **argv) {
 		if (o.shard_output) die("--argos cannot be combined with --shard-output: the argos lines are written by one process in input order");
 		if (o.bs_mapping) die("--argos cannot be combined with --bs-mapping: that combination is not supported by the HIP backend");
 		if (o.slam_seq) die("--argos cannot be combined with --slam-seq: that combination is not supported by the HIP backend");
+		if (o.trim.max_polya >= 0) die("--argos cannot be combined with --max-polya: that combination is not checked against the reference and not supported by the HIP backend");
 		// Config.cpp:384-388, :517-520: kmer_min 2 and sensitivity 0 unless given; no selection, so -n / --strata / -Q / the identity and
 		// residue filters have no effect (ScoreBuffer.cpp:150-183 hands every scored read to the writer)
 		if (!o.kmer_min_set) o.kmer_min = 2.f;
@@ -284,7 +291,8 @@ Opts parse(int argc, char **argv) {
 		// not yet checked against the reference with such an index and are refused rather than run unchecked.  --argos would print
 		// the candidates of the zero slots, where the reference's convert() reads past its contig table (SequenceProvider.cpp:115-119)
 		const char *why = o.argos ? "--argos" : o.bam ? "--bam" : o.topn > 1 ? "-n/--topn above 1" : o.mode == 1 ? "-e/--end-to-end" :
-				o.devices.size() > 1 ? "several GPUs (-g a,b,..)" : o.shard_output ? "--shard-output" : o.shard_n > 1 ? "--shard" : o.bin_size < 2 ? "--bin-size below 2" : nullptr;
+				o.devices.size() > 1 ? "several GPUs (-g a,b,..)" : o.shard_output ? "--shard-output" : o.shard_n > 1 ? "--shard" : o.bin_size < 2 ? "--bin-size below 2" :
+				o.trim.max_polya >= 0 ? "--max-polya" : nullptr;
 		if (why) die(std::string("--vcf cannot be combined with ") + why + ": that combination is not supported by the HIP backend yet");
 		gzFile vf = gzopen(o.vcf.c_str(), "rb");  // before any GPU work (the reference logs an unreadable VCF and goes on without it)
 		if (!vf) die("Failed to open VCF file " + o.vcf);
@@ -334,18 +342,9 @@ Opts parse(int argc, char **argv) {
 }
 
 // ---- input: records as views into the mapped file (plain FASTQ) or into storage owned by the batch (serial reader) ----
-struct Rec { const char *name; const char *seq; const char *qual; uint32_t name_len, seq_len, qual_len; uint8_t unit; };
+struct Rec { const char *name; const char *seq; const char *qual; uint32_t name_len, seq_len, qual_len; uint8_t unit; uint16_t polya; };   // seq / qual: behind the -5 prefix; polya: bases --max-polya cut (XA:i)
 
-inline void pack_row_view(const char *seq, size_t len, int q, char *row) {  // IParser.h:59-121
-	memset(row, 0, q);
-	if (len == 0) { row[0] = 'N'; return; }
-	const int L = (int) std::min<size_t>(len, (size_t) q - 1);
-	for (int i = 0; i < L; ++i) {
-		const char c = (char) (seq[i] & 0xDF);  // toupper for letters
-		row[i] = (c == 'A' || c == 'C' || c == 'G' || c == 'T') ? c : 'N';
-	}
-}
-void pack_row(const Read &r, int q, char *row) { pack_row_view(r.seq.data(), r.seq.size(), q, row); }
+void pack_row(const Read &r, int q, char *row) { (void) ngm::trim::pack_row(r.seq.data(), r.seq.size(), q, row); }  // IParser.h:59-121
 
 // a whole file mapped read-only; plain() = not gzip and made of 4-line FASTQ records (checked on the first records)
 struct MappedFile {
@@ -495,7 +494,7 @@ struct FastqIndex {
 	std::vector<Read> sample;
 };
 
-void build_fastq_index(const MappedFile &f, int step, bool stats, FastqIndex &ix) {
+void build_fastq_index(const MappedFile &f, int step, bool stats, int trim5, FastqIndex &ix) {
 	ngm::ThreadPool &pool = ngm::ThreadPool::instance();
 	const int T = (int) std::max<size_t>(1, std::min<size_t>((size_t) pool.size() * 4, f.n >> 20));
 	struct Range { size_t start = 0, n_rec = 0, n_ne = 0, bad_at = 0, rec_base = 0, ne_base = 0, max_len = 0, min_len = 9999999, sum_len = 0; bool bad = false; std::string len_err; std::vector<Read> sample; };
@@ -540,9 +539,14 @@ void build_fastq_index(const MappedFile &f, int step, bool stats, FastqIndex &ix
 				if (stats && rec.seq_len) {   // reads without a sequence are not counted (ReadProvider.cpp:236)
 					++c;
 					if (c <= 10000001) {
-						const size_t len = std::min<size_t>(rec.seq_len, 9999);
+						const size_t len = ngm::trim::estimate_len(rec.seq_len, trim5);   // (the parser's read: behind the -5 prefix, before --max-polya)
 						R.max_len = std::max(R.max_len, len); R.min_len = std::min(R.min_len, len); R.sum_len += len;
-						if (c % 1000 == 0 && c < 10000000) R.sample.push_back(Read{std::string(rec.name, rec.name_len), std::string(rec.seq, rec.seq_len), std::string()});
+						if (c % 1000 == 0 && c < 10000000) {
+							const char *sq = rec.seq, *ql = rec.qual;
+							uint32_t sl = rec.seq_len, qn = 0;
+							ngm::trim::trim5(trim5, sq, sl, ql, qn);
+							R.sample.push_back(Read{std::string(rec.name, rec.name_len), std::string(sq, sl), std::string()});
+						}
 					}
 				}
 			}
@@ -855,7 +859,7 @@ int main(int argc, char **argv) {
 	} early;
 	{
 		const int early_topn = o.paired ? 1 : o.topn;
-		const bool early_gpu_bam = o.bam && !o.slam_seq && !getenv("NGM_HIP_BAM_ZLIB") && !getenv("NGM_HIP_BAM_HOST_RECORDS");
+		const bool early_gpu_bam = o.bam && !getenv("NGM_HIP_BAM_ZLIB") && !getenv("NGM_HIP_BAM_HOST_RECORDS");
 		const bool early_gpu_sam = o.argos || ((!o.bam || early_gpu_bam) && early_topn == 1 && !o.broken_pairs && !getenv("NGM_HIP_HOST_SAM"));
 		const bool early_gpu_bgzf = o.bam && !early_gpu_sam && !getenv("NGM_HIP_BAM_ZLIB");
 		if ((early_gpu_sam || early_gpu_bgzf) && !(o.qry.empty() && o.qry1.empty()) && !o.out.empty()) {
@@ -864,7 +868,7 @@ int main(int argc, char **argv) {
 			else {
 				SeqReader peek((o.qry1.empty() ? o.qry : o.qry1).c_str());
 				Read r;
-				for (int i = 0; i < 256 && peek.ok() && peek.next(r); ++i) peek_max = std::max(peek_max, std::min<size_t>(r.seq.size(), 9999));
+				for (int i = 0; i < 256 && peek.ok() && peek.next(r); ++i) if (!r.seq.empty()) peek_max = std::max(peek_max, ngm::trim::estimate_len(r.seq.size(), o.trim.trim5));
 			}
 			if (peek_max > 0) {
 				early.q = std::min(1000, (int) ((peek_max | 1) + 1));
@@ -963,7 +967,7 @@ int main(int argc, char **argv) {
 		bool finish = false;
 		auto account = [&](size_t seq_len) -> bool {  // true: keep this read for the sensitivity sample
 			if (seq_len == 0) return false;
-			const size_t len = std::min<size_t>(seq_len, 9999);
+			const size_t len = ngm::trim::estimate_len(seq_len, o.trim.trim5);
 			max_len = std::max(max_len, len); min_len = std::min(min_len, len); sum_len += len;
 			++count;
 			if (count % 1000 == 0 && count < 10000000) return true;
@@ -975,8 +979,8 @@ int main(int argc, char **argv) {
 		if (plain_ok) {
 			// both passes over a plain input are one parallel scan: record offsets for the splitter, lengths and the sample for the estimates
 			mf0.prefault(); mf1.prefault();
-			build_fastq_index(mf0, sub_step, true, ix0);
-			if (ix0.ok && mf1.p) build_fastq_index(mf1, sub_step, false, ix1);
+			build_fastq_index(mf0, sub_step, true, o.trim.trim5, ix0);
+			if (ix0.ok && mf1.p) build_fastq_index(mf1, sub_step, false, o.trim.trim5, ix1);
 			if (!ix0.ok || (mf1.p && !ix1.ok)) {
 				// not a strict 4-line record (multi-line sequences, stray blank lines): kseq reads those, so does the serial reader
 				info("INPUT", "Record at byte " + std::to_string(!ix0.ok ? ix0.bad_at : ix1.bad_at) + " of " + (!ix0.ok ? path0 : path1) + " is not a 4-line FASTQ record: using the serial reader");
@@ -995,7 +999,10 @@ int main(int argc, char **argv) {
 			SeqReader in(first_input.c_str());
 			if (!in.ok()) die("cannot open " + first_input);
 			Read r;
-			while (!finish && in.next(r)) if (account(r.seq.size())) sample.push_back(r);
+			while (!finish && in.next(r)) if (account(r.seq.size())) {
+				if (o.trim.trim5 > 0) r.seq.erase(0, std::min<size_t>(r.seq.size(), (size_t) o.trim.trim5));
+				sample.push_back(r);
+			}
 			scan_finished = finish;
 		}
 		// NGM.Stats->TotalSeqs (the --argos prolog): the reads the scan counted, 0 when it stopped at the 10 000 001st (ReadProvider.cpp:252-279)
@@ -1179,16 +1186,17 @@ int main(int argc, char **argv) {
 	}
 	ngm_pair_state *pair_state = ngm_pair_state_create();
 	// SAM text on the GPU (csrc/sam_device.h) for plain SAM output with one alignment per read; BAM and -n > 1 are formatted here
-	// --bam: the records and their BGZF blocks are written by the GPU as well (sam_device.h's BAM mode + bgzf_device.h); with -n > 1,
-	// --broken-pairs or SLAM-seq tags the records are formatted here and only the blocks come from the GPU
+	// --bam: the records and their BGZF blocks are written by the GPU as well (sam_device.h's BAM mode + bgzf_device.h), SLAM-seq tags
+	// included; with -n > 1 or --broken-pairs the records are formatted here and only the blocks come from the GPU
 	// (NGM_HIP_BAM_HOST_RECORDS=1 forces that; NGM_HIP_BAM_ZLIB=1: records here, zlib level 6 on the pool -- the round-3 path)
-	const bool gpu_bam = o.bam && !o.slam_seq && !getenv("NGM_HIP_BAM_ZLIB") && !getenv("NGM_HIP_BAM_HOST_RECORDS");
+	const bool gpu_bam = o.bam && !getenv("NGM_HIP_BAM_ZLIB") && !getenv("NGM_HIP_BAM_HOST_RECORDS");
 	const bool gpu_sam = o.argos || ((!o.bam || gpu_bam) && topn == 1 && !o.broken_pairs && !getenv("NGM_HIP_HOST_SAM"));   // (--argos: its lines only come from the GPU)
 	const bool gpu_bgzf = o.bam && !gpu_sam && !getenv("NGM_HIP_BAM_ZLIB");
 	std::atomic<long long> t_bgzf_gpu_us{0}, t_bgzf_call_us{0};
 	std::atomic<unsigned long long> bgzf_in_bytes{0}, bgzf_out_bytes{0};
 	struct Worker { ngm_mapper *m = nullptr; char *rows = nullptr; size_t rows_cap = 0; std::vector<ngm_hit> hits; std::vector<char> cig, md;
 		char *qrows = nullptr, *names = nullptr; size_t names_cap = 0; ngm_sam_read *meta = nullptr;
+		uint16_t *polya = nullptr; size_t polya_cap = 0;   // --max-polya: bases cut per read, for the GPU writer's XA:i (page-locked like meta; 2 bytes per read)
 		ngm_bgzf *bz = nullptr; char *bam_raw = nullptr, *bam_out = nullptr; size_t bam_raw_cap = 0, bam_out_cap = 0; };
 	std::vector<Worker> workers(o.devices.size() * (size_t) o.workers);
 	for (size_t w = 0; w < workers.size(); ++w) {
@@ -1264,6 +1272,7 @@ int main(int argc, char **argv) {
 		if (!mp.empty()) { s += "\tMP:Z:"; s += mp; }
 	};
 	struct BamMate { int ref; long long pos0; long long tlen; };  // what BAMWriter::DoWritePair passes on (0-based, -1 = none; its own TLEN rule)
+	const bool xa_tag = o.trim.max_polya >= 0;   // trimPolyA (SAMWriter.h:11): XA:i on every record, 0 when nothing was cut
 	auto write_mapped = [&](std::string &s, size_t &n_written, const View &v, int flags, const char *rnext, unsigned long long pnext, long long tlen, const BamMate &bm) {
 		const ngm_hit &h = *v.h;
 		const int L = v.L;
@@ -1287,6 +1296,7 @@ int main(int argc, char **argv) {
 			tg.add_int("AS", (int) h.score); tg.add_int("NM", h.nm); tg.add_int("NH", h.n_best);
 			if (o.bs_mapping) { const bool second = o.paired && (flags & 0x80); const char *zs = second ? (h.reverse ? "+-" : "--") : (h.reverse ? "-+" : "++"); tg.add_string("ZS", zs, 2); }  // BAMWriter.cpp:240-254
 			tg.add_float("XI", roundf(h.identity * 10000.0f) / 10000.0f);
+			if (xa_tag) tg.add_int("XA", v.r->polya);   // BAMWriter.cpp:258-260
 			tg.add_int("X0", h.n_best); tg.add_int("XE", (int) h.max_votes); tg.add_int("XR", L - h.qstart - h.qend);
 			tg.add_string("MD", v.md, strlen(v.md));
 			if (!o.rg[0].empty()) tg.add_string("RG", o.rg[0].data(), o.rg[0].size());
@@ -1334,7 +1344,9 @@ int main(int argc, char **argv) {
 			s += second ? (h.reverse ? "\tZS:Z:+-" : "\tZS:Z:--") : (h.reverse ? "\tZS:Z:-+" : "\tZS:Z:++");
 		}
 		s += "\tXI:f:"; put_identity(s, h.identity);
-		s += "\tX0:i:"; put_i64(s, h.n_best); s += "\tXE:i:"; put_i64(s, (int) h.max_votes); s += "\tXR:i:"; put_i64(s, L - h.qstart - h.qend); s += "\tMD:Z:"; s += v.md;
+		s += "\tX0:i:"; put_i64(s, h.n_best);
+		if (xa_tag) { s += "\tXA:i:"; put_i64(s, v.r->polya); }   // SAMWriter.cpp:192-194
+		s += "\tXE:i:"; put_i64(s, (int) h.max_votes); s += "\tXR:i:"; put_i64(s, L - h.qstart - h.qend); s += "\tMD:Z:"; s += v.md;
 		if (o.slam_seq) slam_tags(s, v);
 		s.push_back('\n');
 		++n_written;
@@ -1348,6 +1360,7 @@ int main(int argc, char **argv) {
 			const int n = std::min(v.L, 1000), QL = std::min<int>((int) v.r->qual_len, v.L);
 			for (int t = 0; t < n; ++t) qual[t] = t < QL ? v.r->qual[t] : ':';
 			ngm::bam::Tags tg;
+			if (xa_tag) tg.add_int("XA", v.r->polya);   // BAMWriter.cpp:356-358
 			if (!o.rg[0].empty()) tg.add_string("RG", o.rg[0].data(), o.rg[0].size());
 			const int p0 = contig >= 0 ? (int) pos1 - 1 : -1;
 			ngm::bam::put_record(s, v.r->name, v.r->name_len, (uint32_t) (flags | 0x4), contig >= 0 ? contig : -1, p0, 0, nullptr, v.row, (size_t) n,
@@ -1360,6 +1373,7 @@ int main(int argc, char **argv) {
 		s.push_back('\t'); put_u64(s, pos1); s += "\t0\t*\t"; s.push_back(rnext); s.push_back('\t'); put_u64(s, pnext1); s += "\t0\t";
 		s.append(v.row, v.L); s.push_back('\t');
 		if (noq) s.push_back('*'); else s.append(v.r->qual, std::min<int>((int) v.r->qual_len, v.L));
+		if (xa_tag) { s += "\tXA:i:"; put_i64(s, v.r->polya); }   // SAMWriter.cpp:355-357
 		s += rg_unmapped;
 		s.push_back('\n');
 		++n_written;
@@ -1669,10 +1683,11 @@ int main(int argc, char **argv) {
 				pool.parallel_for(n, [&](int lo, int hi) {
 					for (int i = lo; i < hi; ++i) {
 						const Read &r = b->owned[i];
-						b->recs[i] = Rec{r.name.data(), r.seq.data(), r.qual.data(), (uint32_t) r.name.size(), (uint32_t) r.seq.size(), (uint32_t) r.qual.size(), r.unit};
-						if (o.paired) strip_mate(b->recs[i].name, b->recs[i].name_len);
-						pack_row_view(r.seq.data(), r.seq.size(), q, w.rows + (size_t) i * q);
-						if (gpu_sam) memcpy(w.qrows + (size_t) i * q, r.qual.data(), std::min<size_t>(r.qual.size(), (size_t) q - 1));
+						Rec &rc = b->recs[i];
+						rc = Rec{r.name.data(), r.seq.data(), r.qual.data(), (uint32_t) r.name.size(), (uint32_t) r.seq.size(), (uint32_t) r.qual.size(), r.unit, 0};
+						if (o.paired) strip_mate(rc.name, rc.name_len);
+						rc.polya = (uint16_t) ngm::trim::parse_read(o.trim, q, rc.seq, rc.seq_len, rc.qual, rc.qual_len, w.rows + (size_t) i * q);
+						if (gpu_sam) memcpy(w.qrows + (size_t) i * q, rc.qual, std::min<size_t>(rc.qual_len, (size_t) q - 1));
 					}
 				}, 4096);
 			} else if (w.rows) {
@@ -1697,7 +1712,7 @@ int main(int argc, char **argv) {
 							if (r.qual_len != r.seq_len) { if (!bad.exchange(true)) bad_msg = "Error while parsing read: sequence and quality lengths differ (" + std::string(r.name, r.name_len) + ")"; return; }  // IParser.h copyToRead
 							at = nx;
 							if (o.paired) strip_mate(r.name, r.name_len);
-							pack_row_view(r.seq, r.seq_len, q, w.rows + (size_t) i * q);
+							r.polya = (uint16_t) ngm::trim::parse_read(o.trim, q, r.seq, r.seq_len, r.qual, r.qual_len, w.rows + (size_t) i * q);
 							if (gpu_sam) memcpy(w.qrows + (size_t) i * q, r.qual, std::min<size_t>(r.qual_len, (size_t) q - 1));
 						}
 					}
@@ -1739,7 +1754,16 @@ int main(int argc, char **argv) {
 					w.names = (char *) ngm_host_alloc(w.names_cap);
 					if (!w.names) { fail(ngm_pipeline_last_error()); w.names_cap = 0; if (o.paired) (void) ngm_mapper_map_pe(w.m, 0, nullptr, nullptr, nullptr, nullptr); continue; }
 				}
-				pool.parallel_for(n, [&](int lo, int hi) { for (int i = lo; i < hi; ++i) memcpy(w.names + w.meta[i].name_off, b->recs[i].name, w.meta[i].name_len); }, 8192);
+				if (xa_tag && (size_t) n > w.polya_cap) {
+					ngm_host_free(w.polya);
+					w.polya_cap = (size_t) std::max(n, batch_reads);
+					w.polya = (uint16_t *) ngm_host_alloc(w.polya_cap * sizeof(uint16_t));
+					if (!w.polya) { fail(ngm_pipeline_last_error()); w.polya_cap = 0; if (o.paired) (void) ngm_mapper_map_pe(w.m, 0, nullptr, nullptr, nullptr, nullptr); continue; }
+				}
+				uint16_t *const polya = xa_tag ? w.polya : nullptr;
+				pool.parallel_for(n, [&](int lo, int hi) {
+					for (int i = lo; i < hi; ++i) { memcpy(w.names + w.meta[i].name_off, b->recs[i].name, w.meta[i].name_len); if (polya) polya[i] = b->recs[i].polya; }
+				}, 8192);
 				t_parse_us += us_since(tp);
 				auto tm = std::chrono::steady_clock::now();
 				TextBuf tb{nullptr, 0};
@@ -1760,7 +1784,7 @@ int main(int argc, char **argv) {
 				uint64_t st[3] = {0, 0, 0};
 				float sam_ms = 0.f;
 				long long len = o.argos ? ngm_mapper_map_argos(w.m, n, w.rows, w.names, total, w.meta, tb.p, tb.cap, st, &sam_ms)
-				                        : ngm_mapper_map_sam(w.m, n, w.rows, w.qrows, w.names, total, w.meta, tb.p, tb.cap, st, &sam_ms);
+				                        : ngm_mapper_map_sam_trimmed(w.m, n, w.rows, w.qrows, w.names, total, w.meta, polya, tb.p, tb.cap, st, &sam_ms);
 				if (len > (long long) tb.cap) {  // (long CIGAR / MD strings: a larger buffer for this batch)
 					ngm_host_free(tb.p);
 					tb.cap = (size_t) len + (1u << 20);
@@ -2046,7 +2070,7 @@ int main(int argc, char **argv) {
 		info("MAIN", msg);
 	}
 	if (const char *pf = getenv("NGM_HIP_PROFILE")) prof::dump(pf);
-	for (Worker &w : workers) { ngm_mapper_destroy(w.m); ngm_host_free(w.rows); ngm_host_free(w.qrows); ngm_host_free(w.names); ngm_host_free(w.meta);
+	for (Worker &w : workers) { ngm_mapper_destroy(w.m); ngm_host_free(w.rows); ngm_host_free(w.qrows); ngm_host_free(w.names); ngm_host_free(w.meta); ngm_host_free(w.polya);
 		ngm_bgzf_destroy(w.bz); ngm_host_free(w.bam_raw); ngm_host_free(w.bam_out); }
 	for (TextBuf &t : text_free) ngm_host_free(t.p);
 	ngm_pair_state_destroy(pair_state);

@@ -8,7 +8,7 @@
 // 2.2 us of CPU time per read on 64 threads (22 of the 20 CPU-seconds of a 10 M read run); the GPU does it in two passes
 // over the batch: lengths per unit (a read, or a pair: the two records of a pair are written together, mate 2 first),
 // exclusive prefix sum, bytes.  The host only copies the finished text to the output file.
-// The host formatter in ngm_cli.cpp stays: BAM output, -n > 1, and as the twin the tests compare this one with.
+// The host formatter in ngm_cli.cpp stays: -n > 1, --broken-pairs, and as the twin the tests compare this one with.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -51,10 +51,17 @@ struct SamArgs {
 	char *out;
 	unsigned long long *counters;  // [0] reads counted [1] reads mapped [2] lines written
 	int bam;                    // the records as BAM (binary, uncompressed: BAMWriter.cpp:147-375 over bamtools' BamWriter_p.cpp) instead of SAM text
+	const uint16_t *polya;      // [n] bases --max-polya cut off the read (MappedRead::polyATrimmed), or null: no XA:i tag
 };
 
+// mark / since / set32: a 32-bit field whose value is known only after later bytes (a BAM record's block_size in front of tags of
+// data-dependent length) is put as a placeholder and set afterwards; the counting pass only counts it
 struct SamCountSink {
 	uint32_t n = 0;
+	typedef uint32_t Mark;
+	__device__ __forceinline__ Mark mark() const { return n; }
+	__device__ __forceinline__ uint32_t since(Mark m) const { return n - m; }
+	__device__ __forceinline__ void set32(Mark, uint32_t) {}
 	__device__ __forceinline__ void put(char) { ++n; }
 	__device__ __forceinline__ void put32(uint32_t) { n += 4; }
 	__device__ __forceinline__ void bytes(const char *, uint32_t len) { n += len; }
@@ -64,6 +71,10 @@ struct SamCountSink {
 };
 struct SamWriteSink {
 	char *p;
+	typedef char *Mark;
+	__device__ __forceinline__ Mark mark() const { return p; }
+	__device__ __forceinline__ uint32_t since(Mark m) const { return (uint32_t) (p - m); }
+	__device__ __forceinline__ void set32(Mark m, uint32_t v) { m[0] = (char) v; m[1] = (char) (v >> 8); m[2] = (char) (v >> 16); m[3] = (char) (v >> 24); }
 	__device__ __forceinline__ void put(char c) { *p++ = c; }
 	__device__ __forceinline__ void put32(uint32_t v) { p[0] = (char) v; p[1] = (char) (v >> 8); p[2] = (char) (v >> 16); p[3] = (char) (v >> 24); p += 4; }
 	__device__ __forceinline__ void bytes(const char *s, uint32_t len) { for (uint32_t i = 0; i < len; ++i) p[i] = s[i]; p += len; }
@@ -130,7 +141,9 @@ template <typename Sink> __device__ __forceinline__ void sam_contig(const SamArg
 // per-column records computeCigarMD leaves in Align::ExtendedData, SWOclCigar.cpp:484-540): every aligned column has a type
 // 5 * ref + read (A0 C1 G2 T3 other 4); RA = the 25 type counts, MP = "type:read position:ref position" (1-based, from the start of
 // the aligned read / of the alignment) of the columns the kernel labelled 'X', TC = the T>C columns (reverse strand: A>G).
-template <typename Sink>
+// BAM: the same three as typed BAM tags (src/writer/BAMWriter.cpp:273-292: TC 'i', RA and MP 'Z' with their NUL; RA as
+// computeSlaSeqTags leaves it, every count followed by a comma -- the SAM writer drops the last one, this one does not).
+template <bool BAM, typename Sink>
 __device__ __forceinline__ void sam_slam_tags(const SamArgs &A, Sink &s, const SamView &v, const SamRef &rf) {
 	const ngm_hit &h = *v.h;
 	const int L = v.L;
@@ -147,8 +160,15 @@ __device__ __forceinline__ void sam_slam_tags(const SamArgs &A, Sink &s, const S
 	for (int pass = 0; pass < 2; ++pass) {   // pass 0: counts (TC and RA come first in the record), pass 1: the MP list
 		if (pass == 1) {
 			const int tc = h.reverse ? rates[0 * 5 + 2] : rates[3 * 5 + 1];
-			sam_lit(s, "\tTC:i:"); sam_i64(s, tc); sam_lit(s, "\tRA:Z:");
-			for (int i = 0; i < 25; ++i) { if (i) s.put(','); sam_i64(s, rates[i]); }
+			if (BAM) {
+				s.put('T'); s.put('C'); s.put('i'); s.put32((uint32_t) tc);
+				s.put('R'); s.put('A'); s.put('Z');
+				for (int i = 0; i < 25; ++i) { sam_i64(s, rates[i]); s.put(','); }
+				s.put('\0');
+			} else {
+				sam_lit(s, "\tTC:i:"); sam_i64(s, tc); sam_lit(s, "\tRA:Z:");
+				for (int i = 0; i < 25; ++i) { if (i) s.put(','); sam_i64(s, rates[i]); }
+			}
 		}
 		int read_i = h.qstart, ref_i = 0, num = 0;
 		bool any = false;
@@ -166,7 +186,7 @@ __device__ __forceinline__ void sam_slam_tags(const SamArgs &A, Sink &s, const S
 					const char fch = fc == 0u ? 'A' : fc == 1u ? 'C' : fc == 2u ? 'G' : fc == 3u ? 'T' : fc == 4u ? 'x' : 'N';
 					const bool eq = !A.variant_cpu ? (rch == fch) : (A.alt_scoring ? rc == fc : (rc <= 3u && rc == fc));
 					if (!eq) {
-						sam_lit(s, any ? "," : "\tMP:Z:"); any = true;
+						sam_lit(s, any ? "," : BAM ? "MPZ" : "\tMP:Z:"); any = true;
 						sam_i64(s, type); s.put(':'); sam_i64(s, read_i + k2 + 1); s.put(':'); sam_i64(s, ref_i + k2 + 1);
 					}
 				}
@@ -175,6 +195,7 @@ __device__ __forceinline__ void sam_slam_tags(const SamArgs &A, Sink &s, const S
 			else if (ch == 'D') ref_i += num;
 			num = 0;   // (S / H: the clipped bases are not columns; the leading ones are h.qstart)
 		}
+		if (BAM && pass == 1 && any) s.put('\0');
 	}
 }
 
@@ -225,7 +246,8 @@ template <typename F> __device__ __forceinline__ int bam_cigar_ops(const char *c
 	}
 	return span;
 }
-template <typename Sink>
+// BAM_SLAM: the SLAM-seq tags are compiled in (kernels of their own: the other modes keep their registers)
+template <bool BAM_SLAM, typename Sink>
 __device__ __forceinline__ void bam_mapped(const SamArgs &A, Sink &s, const SamView &v, int flags, int mate_ref, long long mate_pos0, long long tlen) {
 	const ngm_hit &h = *v.h;
 	const int L = v.L;
@@ -239,8 +261,9 @@ __device__ __forceinline__ void bam_mapped(const SamArgs &A, Sink &s, const SamV
 	uint32_t n_ops = 0;
 	const int span = bam_cigar_ops(A.str + rf.cig_off, rf.cig_len, [&](uint32_t, uint32_t) { if (n_ops < 512u) ++n_ops; });
 	const uint32_t l_name = (uint32_t) v.m.name_len + 1u;
-	const uint32_t tags = 21u + (A.bs_mapping ? 6u : 0u) + 7u + 21u + (3u + rf.md_len + 1u) + (A.rg_len > 0 ? 3u + (uint32_t) A.rg_len + 1u : 0u);
-	s.put32(32u + l_name + 4u * n_ops + (uint32_t) ((n + 1) / 2) + (uint32_t) n + tags);
+	const uint32_t tags = 21u + (A.bs_mapping ? 6u : 0u) + 7u + (A.polya ? 7u : 0u) + 21u + (3u + rf.md_len + 1u) + (A.rg_len > 0 ? 3u + (uint32_t) A.rg_len + 1u : 0u);
+	const typename Sink::Mark block_at = s.mark();
+	s.put32(32u + l_name + 4u * n_ops + (uint32_t) ((n + 1) / 2) + (uint32_t) n + tags);   // (+ the SLAM-seq tags: set below)
 	s.put32((uint32_t) h.contig);
 	s.put32((uint32_t) (int) h.pos);
 	s.put32((bam_min_bin((int) h.pos, (int) h.pos + span) << 16) | ((uint32_t) h.mapq << 8) | l_name);
@@ -274,9 +297,14 @@ __device__ __forceinline__ void bam_mapped(const SamArgs &A, Sink &s, const SamV
 		bam_tag_str(s, 'Z', 'S', second ? (h.reverse ? "+-" : "--") : (h.reverse ? "-+" : "++"), 2u);
 	}
 	s.put('X'); s.put('I'); s.put('f'); s.put32(__float_as_uint(roundf(h.identity * 10000.0f) / 10000.0f));
+	if (A.polya) bam_tag_int(s, 'X', 'A', (int) A.polya[v.i]);   // BAMWriter.cpp:258-260
 	bam_tag_int(s, 'X', '0', h.n_best); bam_tag_int(s, 'X', 'E', (int) h.max_votes); bam_tag_int(s, 'X', 'R', L - h.qstart - h.qend);
 	bam_tag_str(s, 'M', 'D', A.str + rf.md_off, rf.md_len);
 	if (A.rg_len > 0) bam_tag_str(s, 'R', 'G', A.rg, (uint32_t) A.rg_len);
+	if (BAM_SLAM && A.slam_seq) {   // BAMWriter.cpp:273-292: their length depends on the alignment's columns, so block_size follows them
+		sam_slam_tags<true>(A, s, v, rf);
+		s.set32(block_at, s.since(block_at) - 4u);   // block_size: the record behind this field
+	}
 }
 template <typename Sink>
 __device__ __forceinline__ void bam_unmapped(const SamArgs &A, Sink &s, const SamView &v, int flags, int contig, unsigned long long pos1) {
@@ -284,7 +312,7 @@ __device__ __forceinline__ void bam_unmapped(const SamArgs &A, Sink &s, const Sa
 	const int n = min(v.L, 1000), QL = min(qlen, v.L);
 	const int ref = contig >= 0 ? contig : -1, p0 = contig >= 0 ? (int) pos1 - 1 : -1;
 	const uint32_t l_name = (uint32_t) v.m.name_len + 1u;
-	const uint32_t tags = A.rg_len > 0 ? 3u + (uint32_t) A.rg_len + 1u : 0u;
+	const uint32_t tags = (A.polya ? 7u : 0u) + (A.rg_len > 0 ? 3u + (uint32_t) A.rg_len + 1u : 0u);
 	s.put32(32u + l_name + (uint32_t) ((n + 1) / 2) + (uint32_t) n + tags);
 	s.put32((uint32_t) ref);
 	s.put32((uint32_t) p0);
@@ -297,17 +325,18 @@ __device__ __forceinline__ void bam_unmapped(const SamArgs &A, Sink &s, const Sa
 	s.bytes(A.names + v.m.name_off, v.m.name_len); s.put('\0');
 	for (int t = 0; t < n; t += 2) s.put((char) ((bam_base_code((char) v.row[t]) << 4) | (t + 1 < n ? bam_base_code((char) v.row[t + 1]) : 0u)));
 	for (int t = 0; t < n; ++t) s.put((char) (((qlen != 0 && t < QL) ? (char) v.qual[t] : ':') - 33));
+	if (A.polya) bam_tag_int(s, 'X', 'A', (int) A.polya[v.i]);   // BAMWriter.cpp:356-358
 	if (A.rg_len > 0) bam_tag_str(s, 'R', 'G', A.rg, (uint32_t) A.rg_len);
 }
 
 // SAMWriter::DoWriteReadGeneric (SAMWriter.cpp:98-228).  rnext: 0 '*', 1 '=', 2 the name of contig rnext_contig; bm_*: what BAMWriter::DoWritePair
 // passes on instead (mate reference, 0-based mate position, its own TLEN rule)
-template <typename Sink>
+template <bool BAM_SLAM, typename Sink>
 __device__ __forceinline__ void sam_mapped(const SamArgs &A, Sink &s, const SamView &v, int flags, int rnext, int rnext_contig, unsigned long long pnext, long long tlen,
 		int bm_ref = -1, long long bm_pos0 = -1, long long bm_tlen = 0) {
 	const ngm_hit &h = *v.h;
 	const int L = v.L;
-	if (A.bam) { bam_mapped(A, s, v, flags | (h.reverse ? 0x10 : 0), bm_ref, bm_pos0, bm_tlen); return; }
+	if (A.bam) { bam_mapped<BAM_SLAM>(A, s, v, flags | (h.reverse ? 0x10 : 0), bm_ref, bm_pos0, bm_tlen); return; }
 	const int qlen = v.m.qual_len & 0x7FFF;
 	const bool noq = qlen == 0;
 	if (h.reverse) flags |= 0x10;
@@ -336,9 +365,11 @@ __device__ __forceinline__ void sam_mapped(const SamArgs &A, Sink &s, const SamV
 		sam_lit(s, second ? (h.reverse ? "\tZS:Z:+-" : "\tZS:Z:--") : (h.reverse ? "\tZS:Z:-+" : "\tZS:Z:++"));
 	}
 	sam_lit(s, "\tXI:f:"); sam_identity(s, h.identity);
-	sam_lit(s, "\tX0:i:"); sam_i64(s, h.n_best); sam_lit(s, "\tXE:i:"); sam_i64(s, (int) h.max_votes); sam_lit(s, "\tXR:i:"); sam_i64(s, L - h.qstart - h.qend);
+	sam_lit(s, "\tX0:i:"); sam_i64(s, h.n_best);
+	if (A.polya) { sam_lit(s, "\tXA:i:"); sam_i64(s, (int) A.polya[v.i]); }   // SAMWriter.cpp:192-194
+	sam_lit(s, "\tXE:i:"); sam_i64(s, (int) h.max_votes); sam_lit(s, "\tXR:i:"); sam_i64(s, L - h.qstart - h.qend);
 	sam_lit(s, "\tMD:Z:"); s.bytes(A.str + rf.md_off, rf.md_len);
-	if (A.slam_seq) sam_slam_tags(A, s, v, rf);
+	if (A.slam_seq) sam_slam_tags<false>(A, s, v, rf);
 	s.put('\n');
 }
 // SAMWriter::DoWriteUnmappedReadGeneric (SAMWriter.cpp:311-372): contig < 0 prints '*'
@@ -351,13 +382,14 @@ __device__ __forceinline__ void sam_unmapped(const SamArgs &A, Sink &s, const Sa
 	s.put('\t'); sam_u64(s, pos1); sam_lit(s, "\t0\t*\t"); s.put(rnext); s.put('\t'); sam_u64(s, pnext1); sam_lit(s, "\t0\t");
 	s.seq_fwd(v.row, v.L); s.put('\t');
 	if (qlen == 0) s.put('*'); else s.seq_fwd(v.qual, min(qlen, v.L));
+	if (A.polya) { sam_lit(s, "\tXA:i:"); sam_i64(s, (int) A.polya[v.i]); }   // SAMWriter.cpp:355-357
 	if (A.rg_len > 0) { sam_lit(s, "\tRG:Z:"); s.bytes(A.rg, (uint32_t) A.rg_len); }
 	s.put('\n');
 }
 
 // one unit: read `unit` (single-end) or reads 2 * unit, 2 * unit + 1 (paired).  cnt: reads counted / mapped, lines written; pairs with
 // both mates mapped, of those broken, insert size of the others (AlignmentBuffer.cpp:175-199 pairInsertCount / brokenPairs / pairInsertSum)
-template <typename Sink>
+template <bool BAM_SLAM, typename Sink>
 __device__ __forceinline__ void sam_unit(const SamArgs &A, int unit, Sink &s, uint32_t (&cnt)[6]) {
 	if (!A.paired) {
 		const SamView v = sam_view(A, unit);
@@ -365,7 +397,7 @@ __device__ __forceinline__ void sam_unit(const SamArgs &A, int unit, Sink &s, ui
 		++cnt[0];
 		if (!sam_passes(A, v)) { if (!A.no_unal) { sam_unmapped(A, s, v, 0, -1, 0, '*', 0); ++cnt[2]; } return; }
 		++cnt[1];
-		sam_mapped(A, s, v, 0, 0, 0, 0, 0); ++cnt[2];
+		sam_mapped<BAM_SLAM>(A, s, v, 0, 0, 0, 0, 0); ++cnt[2];
 		return;
 	}
 	// read1 = the first mate (even ReadId), written second by AlignmentBuffer::WriteRead; read2 = its mate
@@ -391,36 +423,36 @@ __device__ __forceinline__ void sam_unit(const SamArgs &A, int unit, Sink &s, ui
 		if (unal) { sam_unmapped(A, s, v2, f2 | 0x8, -1, 0, '*', 0); sam_unmapped(A, s, v1, f1 | 0x8, -1, 0, '*', 0); }
 		cnt[2] += 2 * unal;
 	} else if (!m1) {
-		sam_mapped(A, s, v2, f2 | 0x8, 1, 0, p2, 0, h2.contig, (long long) h2.pos, 0);
+		sam_mapped<BAM_SLAM>(A, s, v2, f2 | 0x8, 1, 0, p2, 0, h2.contig, (long long) h2.pos, 0);
 		if (unal) sam_unmapped(A, s, v1, f1, h2.contig, p2, '=', p2);
 		cnt[2] += 1 + unal;
 	} else if (!m2) {
 		if (unal) sam_unmapped(A, s, v2, f2, h1.contig, p1, '=', p1);
-		sam_mapped(A, s, v1, f1 | 0x8, 1, 0, p1, 0, h1.contig, (long long) h1.pos, 0);
+		sam_mapped<BAM_SLAM>(A, s, v1, f1 | 0x8, 1, 0, p1, 0, h1.contig, (long long) h1.pos, 0);
 		cnt[2] += 1 + unal;
 	} else if (!paired_fail) {
 		if (!h1.reverse) {
 			const long long d = ((long long) h2.pos + v2.L - h2.qstart - h2.qend) - (long long) h1.pos;
 			const long long db = (long long) h2.pos + v2.L - (long long) h1.pos;   // BAMWriter.cpp:428-433: the whole read length
-			sam_mapped(A, s, v2, f2 | 0x2, 1, 0, p1, -d, h2.contig, (long long) h1.pos, -db);
-			sam_mapped(A, s, v1, f1 | 0x2 | 0x20, 1, 0, p2, d, h2.contig, (long long) h2.pos, db);
+			sam_mapped<BAM_SLAM>(A, s, v2, f2 | 0x2, 1, 0, p1, -d, h2.contig, (long long) h1.pos, -db);
+			sam_mapped<BAM_SLAM>(A, s, v1, f1 | 0x2 | 0x20, 1, 0, p2, d, h2.contig, (long long) h2.pos, db);
 			cnt[2] += 2;
 		} else if (!h2.reverse) {
 			const long long d = ((long long) h1.pos + v1.L - h1.qstart - h1.qend) - (long long) h2.pos;
 			const long long db = (long long) h1.pos + v1.L - (long long) h2.pos;
-			sam_mapped(A, s, v2, f2 | 0x2 | 0x20, 1, 0, p1, d, h2.contig, (long long) h1.pos, db);
-			sam_mapped(A, s, v1, f1 | 0x2, 1, 0, p2, -d, h2.contig, (long long) h2.pos, -db);
+			sam_mapped<BAM_SLAM>(A, s, v2, f2 | 0x2 | 0x20, 1, 0, p1, d, h2.contig, (long long) h1.pos, db);
+			sam_mapped<BAM_SLAM>(A, s, v1, f1 | 0x2, 1, 0, p2, -d, h2.contig, (long long) h2.pos, -db);
 			cnt[2] += 2;
 		}
 	} else {
-		sam_mapped(A, s, v2, f2 | (h1.reverse ? 0x20 : 0), 2, h1.contig, p1, 0, h1.contig, (long long) h1.pos, 0);
-		sam_mapped(A, s, v1, f1 | (h2.reverse ? 0x20 : 0), 2, h2.contig, p2, 0, h2.contig, (long long) h2.pos, 0);
+		sam_mapped<BAM_SLAM>(A, s, v2, f2 | (h1.reverse ? 0x20 : 0), 2, h1.contig, p1, 0, h1.contig, (long long) h1.pos, 0);
+		sam_mapped<BAM_SLAM>(A, s, v1, f1 | (h2.reverse ? 0x20 : 0), 2, h2.contig, p2, 0, h2.contig, (long long) h2.pos, 0);
 		cnt[2] += 2;
 	}
 }
 
 #ifdef NGM_SAM_KERNELS
-__global__ __launch_bounds__(256) void sam_lengths_kernel(SamArgs A, int units) {
+template <bool BAM_SLAM> __global__ __launch_bounds__(256) void sam_lengths_kernel(SamArgs A, int units) {
 	__shared__ unsigned long long s_sum;
 	if (threadIdx.x == 0) s_sum = 0;
 	__syncthreads();
@@ -429,7 +461,7 @@ __global__ __launch_bounds__(256) void sam_lengths_kernel(SamArgs A, int units) 
 	if (u < units) {
 		SamCountSink s;
 		uint32_t cnt[6] = {0, 0, 0, 0, 0, 0};
-		sam_unit(A, u, s, cnt);
+		sam_unit<BAM_SLAM>(A, u, s, cnt);
 		A.unit_len[u] = len = s.n;
 	}
 	// the batch's offsets are 32-bit prefix sums: their total is checked against this 64-bit sum of the same lengths (a wrap is
@@ -438,7 +470,7 @@ __global__ __launch_bounds__(256) void sam_lengths_kernel(SamArgs A, int units) 
 	__syncthreads();
 	if (threadIdx.x == 0 && s_sum) atomicAdd(&A.counters[3], s_sum);
 }
-__global__ __launch_bounds__(256) void sam_write_kernel(SamArgs A, int units) {
+template <bool BAM_SLAM> __global__ __launch_bounds__(256) void sam_write_kernel(SamArgs A, int units) {
 	__shared__ unsigned long long s_cnt[6];
 	if (threadIdx.x < 6) s_cnt[threadIdx.x] = 0;
 	__syncthreads();
@@ -446,7 +478,7 @@ __global__ __launch_bounds__(256) void sam_write_kernel(SamArgs A, int units) {
 	uint32_t cnt[6] = {0, 0, 0, 0, 0, 0};
 	if (u < units) {
 		SamWriteSink s{A.out + A.unit_off[u]};
-		sam_unit(A, u, s, cnt);
+		sam_unit<BAM_SLAM>(A, u, s, cnt);
 	}
 	for (int k = 0; k < 6; ++k) if (cnt[k]) atomicAdd(&s_cnt[k], (unsigned long long) cnt[k]);
 	__syncthreads();

@@ -21,6 +21,12 @@ class MapperParams(C.Structure):
                 ("match_bonus_tt", C.c_int), ("match_bonus_tc", C.c_int), ("slam_seq", C.c_int)]
 
 
+class SamOptions(C.Structure):   # ngm_sam_options
+    _fields_ = [("paired", C.c_int), ("min_insert_size", C.c_int), ("max_insert_size", C.c_int), ("min_mq", C.c_int),
+                ("min_identity", C.c_float), ("min_residues", C.c_float), ("no_unal", C.c_int), ("rg_id", C.c_char_p),
+                ("bs_mapping", C.c_int), ("slam_seq", C.c_int), ("bam", C.c_int)]
+
+
 HIT_DTYPE = np.dtype([("mapped", "i4"), ("contig", "i4"), ("pos", "u8"), ("reverse", "i4"), ("mapq", "i4"),
                       ("score", "f4"), ("identity", "f4"), ("nm", "i4"), ("qstart", "i4"), ("qend", "i4"),
                       ("n_candidates", "i4"), ("n_best", "i4"), ("max_votes", "f4"), ("pair_flags", "i4")], align=True)
@@ -81,6 +87,10 @@ def _lib():
         lib.ngm_mapper_map_argos.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
                                              C.c_void_p, C.POINTER(C.c_float)]
         lib.ngm_mapper_sam_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.ngm_mapper_set_sam_options.argtypes = [C.c_void_p, C.c_void_p]
+        lib.ngm_mapper_map_sam_trimmed.restype = C.c_longlong
+        lib.ngm_mapper_map_sam_trimmed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_float)]
         lib.ngm_argos_prolog.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t]
         lib.ngm_mapper_argos_counters.argtypes = [C.c_void_p, C.c_void_p]
         lib.ngm_mapper_argos_path_counters.argtypes = [C.c_void_p, C.c_void_p]
@@ -400,6 +410,50 @@ class Mapper:
             out = np.zeros(total, np.uint8)
             if self.lib.ngm_mapper_sam_fetch(self.h, out.ctypes.data, total) < 0:
                 raise _err()
+        return out[:total].tobytes(), [int(x) for x in stats]
+
+    def map_sam(self, reads, quals, names, polya_trimmed=None, paired=False, rg_id=None, slam_seq=0, bam=False, min_insert_size=0,
+                max_insert_size=1000, min_mq=0, min_identity=0.65, min_residues=0.5, no_unal=False):
+        """The records of one batch, written by the GPU (ngm_mapper_set_sam_options + ngm_mapper_map_sam_trimmed).  reads -- rows as from
+        reads_to_rows, or a list of sequences, already trimmed (`-5`, `--max-polya`; an empty read is legal) --, quals -- one quality
+        string per read (b"" for none) --, names -- one per read --, polya_trimmed -- per read, the bases --max-polya cut off: given, every
+        record carries it as XA:i; None, no such tag (ngm_mapper_map_sam).  Returns the SAM text (bam: a piece of the BAM file, whole
+        BGZF members) and the stats (reads counted, reads mapped, records written)."""
+        rows = reads if isinstance(reads, np.ndarray) else self.reads_to_rows(reads, self.q)
+        rows = np.ascontiguousarray(rows, dtype=np.uint8)
+        n = rows.shape[0]
+        if len(names) != n or len(quals) != n or (polya_trimmed is not None and len(polya_trimmed) != n):
+            raise ValueError("one name, one quality string and one poly-A count per read")
+        so = SamOptions(int(paired), min_insert_size, max_insert_size, min_mq, min_identity, min_residues, int(no_unal),
+                        rg_id.encode() if isinstance(rg_id, str) else rg_id, 0, int(slam_seq), int(bam))
+        if self.lib.ngm_mapper_set_sam_options(self.h, C.byref(so)) < 0:
+            raise _err()
+        nb = [x.encode() if isinstance(x, str) else bytes(x) for x in names]
+        qrows = np.zeros((n, self.q), np.uint8)
+        meta = np.zeros(n, np.dtype([("name_off", np.uint32), ("name_len", np.uint16), ("qual_len", np.uint16)]))   # ngm_sam_read
+        off = 0
+        for i, b in enumerate(nb):
+            ql = quals[i].encode() if isinstance(quals[i], str) else bytes(quals[i])
+            qrows[i, :min(len(ql), self.q - 1)] = np.frombuffer(ql[:self.q - 1], np.uint8)
+            meta[i] = (off, min(len(b), 0xFFFF), min(len(ql), 0x7FFF))
+            off += len(b)
+        blob = np.frombuffer(b"".join(nb) + b"\0", np.uint8)
+        polya = None if polya_trimmed is None else np.ascontiguousarray(polya_trimmed, dtype=np.uint16)
+        stats = np.zeros(3, np.uint64)
+        kms = C.c_float(0)
+        cap = max(1 << 16, n * (2 * self.q + 512))
+        out = np.zeros(cap, np.uint8)
+        total = self.lib.ngm_mapper_map_sam_trimmed(self.h, n, rows.ctypes.data, qrows.ctypes.data, blob.ctypes.data, off, meta.ctypes.data,
+                                                    None if polya is None else polya.ctypes.data, out.ctypes.data, cap, stats.ctypes.data, C.byref(kms))
+        if total < 0:
+            raise _err()
+        if total > cap:
+            out = np.zeros(total, np.uint8)
+            got = self.lib.ngm_mapper_sam_fetch(self.h, out.ctypes.data, total)
+            if got < 0:
+                raise _err()
+            if bam:
+                total = got
         return out[:total].tobytes(), [int(x) for x in stats]
 
     def argos_counters(self):
