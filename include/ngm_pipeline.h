@@ -248,7 +248,16 @@ void ngm_bgzf_destroy(ngm_bgzf *z);
 size_t ngm_bgzf_bound(size_t n);
 long long ngm_bgzf_compress(ngm_bgzf *z, const void *raw, size_t n, void *out, size_t out_cap);
 long long ngm_bgzf_compress_device(ngm_bgzf *z, const void *d_raw, size_t n, void *out, size_t out_cap);   /* raw bytes already in the device's memory */
-float ngm_bgzf_last_kernel_ms(const ngm_bgzf *z);   /* HIP-event time of the last call's compression kernel */
+float ngm_bgzf_last_kernel_ms(const ngm_bgzf *z);   /* HIP-event time of the last call's compression kernel (after ngm_bgzf_inflate: the time during which one of its
+                                                         inflate kernels ran -- the chunks' kernels may overlap, their intervals are united, not summed) */
+/* The other direction (csrc/bgzf_inflate_device.h): a run of whole BGZF members (a BAM, any file written by bgzip) inflated by the
+ * GPU, one workgroup per member, length and CRC-32 of every member checked there against its trailer.
+ * ngm_bgzf_inflated_size: the host's walk over the chain (BSIZE of the BC subfield, ISIZE of the trailer): the bytes of text, or
+ * (size_t)-1 if the data is not made of whole BGZF members (no BC subfield, a BSIZE past the end, an ISIZE above 65536).
+ * ngm_bgzf_inflate: the text into out (host memory, out_cap >= the inflated size).  Returns the bytes written; < 0 on error, with the
+ * index of the first member the GPU refused in ngm_pipeline_last_error ("... member <i> refused ..."). */
+size_t ngm_bgzf_inflated_size(const void *members, size_t n);
+long long ngm_bgzf_inflate(ngm_bgzf *z, const void *members, size_t n, void *out, size_t out_cap);
 
 /* page-locked host memory for read batches (the H2D copy then runs at PCIe rate without a staging copy) */
 void *ngm_host_alloc(size_t bytes);

@@ -1,6 +1,8 @@
-// bgzf.cpp -- host side of the GPU BGZF compressor (bgzf_device.h): ngm_bgzf_create / _compress / _destroy (include/ngm_pipeline.h).
+// bgzf.cpp -- host side of the GPU BGZF compressor (bgzf_device.h) and inflater (bgzf_inflate_device.h): ngm_bgzf_create / _compress /
+// _inflate / _destroy (include/ngm_pipeline.h).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -9,6 +11,7 @@
 
 #include "../../include/ngm_pipeline.h"
 #include "bgzf_device.h"
+#include "bgzf_inflate_device.h"
 #include "refindex.h"
 
 #define BGZF_HIP_TRY(expr)                                                                      \
@@ -35,6 +38,22 @@ struct ngm_bgzf {
 	size_t h_cap = 0;
 	float last_ms = 0.f;
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
+	// the inflater (set up by the first ngm_bgzf_inflate): two slots, so that one chunk's copies run under its neighbour's kernel
+	struct InflateSlot {
+		hipStream_t st = nullptr;
+		hipEvent_t ev0 = nullptr, ev1 = nullptr;
+		uint8_t *d_in = nullptr, *d_out = nullptr, *h_in = nullptr, *h_out = nullptr;   // h_*: page-locked
+		ngm::inflate::Member *d_mem = nullptr, *h_mem = nullptr;
+		uint32_t *d_status = nullptr, *h_status = nullptr;
+		size_t in_cap = 0, out_cap = 0, mem_cap = 0;
+		// the chunk in flight
+		size_t first_member = 0, n_members = 0, text_at = 0, text_bytes = 0;
+		bool busy = false;
+	} inf[2];
+	uint8_t *d_inf_tables = nullptr;   // CRC byte table [256], x^(8 m) [65537]
+	hipEvent_t inf_base = nullptr;     // recorded in front of a call's first kernel: the chunks' kernel intervals are measured from it
+	float inf_busy_until = 0.f;        // ms after inf_base up to which the intervals seen so far reach
+	bool inf_ready = false;
 };
 
 namespace {
@@ -100,6 +119,19 @@ extern "C" void ngm_bgzf_destroy(ngm_bgzf *z) {
 	if (z->ev0) (void) hipEventDestroy(z->ev0);
 	if (z->ev1) (void) hipEventDestroy(z->ev1);
 	if (z->st) (void) hipStreamDestroy(z->st);
+	for (ngm_bgzf::InflateSlot &s : z->inf) {
+		if (s.st) (void) hipStreamSynchronize(s.st);
+		(void) hipFree(s.d_in); (void) hipFree(s.d_out); (void) hipFree(s.d_mem); (void) hipFree(s.d_status);
+		if (s.h_in) (void) hipHostFree(s.h_in);
+		if (s.h_out) (void) hipHostFree(s.h_out);
+		if (s.h_mem) (void) hipHostFree(s.h_mem);
+		if (s.h_status) (void) hipHostFree(s.h_status);
+		if (s.ev0) (void) hipEventDestroy(s.ev0);
+		if (s.ev1) (void) hipEventDestroy(s.ev1);
+		if (s.st) (void) hipStreamDestroy(s.st);
+	}
+	(void) hipFree(z->d_inf_tables);
+	if (z->inf_base) (void) hipEventDestroy(z->inf_base);
 	delete z;
 }
 
@@ -192,5 +224,143 @@ static long long compress_on_device(ngm_bgzf *z, const uint8_t *d_raw, size_t n,
 	}
 	float ms = 0.f;
 	if (hipEventElapsedTime(&ms, z->ev0, z->ev1) == hipSuccess) z->last_ms = ms;
+	return (long long) total;
+}
+
+// ---- inflate ---------------------------------------------------------------------------------------------------------
+extern "C" size_t ngm_bgzf_inflated_size(const void *members, size_t n) {
+	size_t total = 0;
+	if (!members || !ngm::inflate::walk_members((const uint8_t *) members, n, nullptr, &total)) return (size_t) -1;
+	return total;
+}
+
+namespace {
+constexpr size_t kInfChunkIn = (size_t) 16 << 20, kInfChunkOut = (size_t) 64 << 20;   // a chunk ends before it would pass either
+
+int inflate_setup(ngm_bgzf *z) {
+	if (z->inf_ready) return 0;
+	const std::vector<uint32_t> t = ngm::inflate::crc_tables();
+	BGZF_HIP_TRY(hipMalloc(&z->d_inf_tables, t.size() * 4));
+	BGZF_HIP_TRY(hipMemcpy(z->d_inf_tables, t.data(), t.size() * 4, hipMemcpyHostToDevice));
+	// more than 64 KiB of LDS per workgroup: the attribute is set for this object's device, and its result counts
+	BGZF_HIP_TRY(hipFuncSetAttribute((const void *) ngm::inflate::inflate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ngm::inflate::inflate_lds_bytes()));
+	for (ngm_bgzf::InflateSlot &s : z->inf) {
+		BGZF_HIP_TRY(hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
+		BGZF_HIP_TRY(hipEventCreate(&s.ev0));
+		BGZF_HIP_TRY(hipEventCreate(&s.ev1));
+	}
+	BGZF_HIP_TRY(hipEventCreate(&z->inf_base));
+	z->inf_ready = true;
+	return 0;
+}
+
+int inflate_reserve(ngm_bgzf::InflateSlot &s, size_t in_bytes, size_t out_bytes, size_t members) {
+	if (in_bytes > s.in_cap) {
+		(void) hipFree(s.d_in); if (s.h_in) (void) hipHostFree(s.h_in);
+		s.d_in = s.h_in = nullptr; s.in_cap = 0;
+		BGZF_HIP_TRY(hipMalloc(&s.d_in, in_bytes));
+		BGZF_HIP_TRY(hipHostMalloc(&s.h_in, in_bytes, hipHostMallocDefault));
+		s.in_cap = in_bytes;
+	}
+	if (out_bytes > s.out_cap) {
+		(void) hipFree(s.d_out); if (s.h_out) (void) hipHostFree(s.h_out);
+		s.d_out = s.h_out = nullptr; s.out_cap = 0;
+		BGZF_HIP_TRY(hipMalloc(&s.d_out, out_bytes));
+		BGZF_HIP_TRY(hipHostMalloc(&s.h_out, out_bytes, hipHostMallocDefault));
+		s.out_cap = out_bytes;
+	}
+	if (members > s.mem_cap) {
+		(void) hipFree(s.d_mem); (void) hipFree(s.d_status); if (s.h_mem) (void) hipHostFree(s.h_mem); if (s.h_status) (void) hipHostFree(s.h_status);
+		s.d_mem = s.h_mem = nullptr; s.d_status = s.h_status = nullptr; s.mem_cap = 0;
+		BGZF_HIP_TRY(hipMalloc(&s.d_mem, members * sizeof(ngm::inflate::Member)));
+		BGZF_HIP_TRY(hipHostMalloc(&s.h_mem, members * sizeof(ngm::inflate::Member), hipHostMallocDefault));
+		BGZF_HIP_TRY(hipMalloc(&s.d_status, members * 4));
+		BGZF_HIP_TRY(hipHostMalloc(&s.h_status, members * 4, hipHostMallocDefault));
+		s.mem_cap = members;
+	}
+	return 0;
+}
+
+// waits for the slot's chunk, adds its kernel time, looks at its status words and moves its text to its place; *bad: the first refused member.
+// last_ms is the time during which an inflate kernel ran: the two slots' kernels are on two streams and may overlap on the device, so the
+// chunks' intervals [ev0, ev1] are united (measured from inf_base, harvested in chunk order), not summed.
+int inflate_harvest(ngm_bgzf *z, ngm_bgzf::InflateSlot &s, uint8_t *out, long long *bad, uint32_t *bad_status) {
+	if (!s.busy) return 0;
+	s.busy = false;
+	BGZF_HIP_TRY(hipStreamSynchronize(s.st));
+	float t0 = 0.f, t1 = 0.f;
+	if (hipEventElapsedTime(&t0, z->inf_base, s.ev0) == hipSuccess && hipEventElapsedTime(&t1, z->inf_base, s.ev1) == hipSuccess) {
+		if (t1 > std::max(t0, z->inf_busy_until)) z->last_ms += t1 - std::max(t0, z->inf_busy_until);
+		z->inf_busy_until = std::max(z->inf_busy_until, t1);
+	}
+	for (size_t m = 0; m < s.n_members; ++m) if (s.h_status[m] != ngm::inflate::kOk) {
+		if (*bad < 0) { *bad = (long long) (s.first_member + m); *bad_status = s.h_status[m]; }
+		return 0;
+	}
+	if (*bad < 0) memcpy(out + s.text_at, s.h_out, s.text_bytes);
+	return 0;
+}
+}  // namespace
+
+extern "C" long long ngm_bgzf_inflate(ngm_bgzf *z, const void *members, size_t n, void *out, size_t out_cap) {
+	if (!z || (!members && n) || (!out && out_cap)) { ngm::pipeline_set_error("ngm_bgzf_inflate: bad arguments"); return -22; }
+	const uint8_t *in = (const uint8_t *) members;
+	std::vector<ngm::inflate::HostMember> chain;
+	size_t total = 0;
+	if (!ngm::inflate::walk_members(in, n, &chain, &total)) { ngm::pipeline_set_error("ngm_bgzf_inflate: the data is not a run of whole BGZF members"); return -22; }
+	if (total > out_cap) { ngm::pipeline_set_error("ngm_bgzf_inflate: %zu bytes of text for a buffer of %zu", total, out_cap); return -22; }
+	z->last_ms = 0.f;
+	if (chain.empty()) return 0;
+	BGZF_HIP_TRY(hipSetDevice(z->device));
+	if (int rc = inflate_setup(z)) return rc;
+	long long bad = -1;
+	uint32_t bad_status = 0;
+	size_t m0 = 0, text_at = 0;
+	for (int c = 0; m0 < chain.size() && bad < 0; ++c) {
+		// the members of this chunk: at least one, then as many as stay inside both limits
+		size_t m1 = m0, in_bytes = 0, out_bytes = 0;
+		while (m1 < chain.size() && (m1 == m0 || (in_bytes + chain[m1].size <= kInfChunkIn && out_bytes + chain[m1].isize <= kInfChunkOut))) {
+			in_bytes += chain[m1].size; out_bytes += chain[m1].isize; ++m1;
+		}
+		ngm_bgzf::InflateSlot &s = z->inf[c & 1];
+		if (int rc = inflate_harvest(z, s, (uint8_t *) out, &bad, &bad_status)) return rc;
+		if (bad >= 0) break;
+		const bool whole = m0 == 0 && m1 == chain.size();   // (a small input takes what it needs, a large one whole chunks)
+		if (int rc = inflate_reserve(s, whole ? in_bytes + 64 : kInfChunkIn + 65536 + 64, whole ? out_bytes + 64 : kInfChunkOut + 65536 + 64, whole ? m1 - m0 : std::max<size_t>(m1 - m0, kInfChunkIn / 28 / 64))) return rc;
+		const size_t base = chain[m0].at;
+		memcpy(s.h_in, in + base, in_bytes);
+		size_t o = 0;
+		for (size_t m = m0; m < m1; ++m) {
+			const ngm::inflate::HostMember &h = chain[m];
+			s.h_mem[m - m0] = ngm::inflate::Member{(uint32_t) (h.at - base + h.payload), (uint32_t) (h.at - base + h.size - 8), (uint32_t) o, h.isize};
+			o += h.isize;
+		}
+		s.first_member = m0; s.n_members = m1 - m0; s.text_at = text_at; s.text_bytes = out_bytes;
+		BGZF_HIP_TRY(hipMemcpyAsync(s.d_in, s.h_in, in_bytes, hipMemcpyHostToDevice, s.st));
+		BGZF_HIP_TRY(hipMemcpyAsync(s.d_mem, s.h_mem, s.n_members * sizeof(ngm::inflate::Member), hipMemcpyHostToDevice, s.st));
+		ngm::inflate::Args A{};
+		A.in = s.d_in; A.members = s.d_mem; A.n_members = (int) s.n_members; A.out = s.d_out; A.status = s.d_status;
+		A.crc_table = (const uint32_t *) z->d_inf_tables; A.xpow = (const uint32_t *) z->d_inf_tables + 256;
+		if (c == 0) { BGZF_HIP_TRY(hipEventRecord(z->inf_base, s.st)); z->inf_busy_until = 0.f; }
+		BGZF_HIP_TRY(hipEventRecord(s.ev0, s.st));
+		hipLaunchKernelGGL(ngm::inflate::inflate_kernel, dim3((unsigned) std::min<size_t>(s.n_members, (size_t) z->grid * 2)), dim3(ngm::inflate::kNT), ngm::inflate::inflate_lds_bytes(), s.st, A);
+		BGZF_HIP_TRY(hipGetLastError());
+		BGZF_HIP_TRY(hipEventRecord(s.ev1, s.st));
+		BGZF_HIP_TRY(hipMemcpyAsync(s.h_status, s.d_status, s.n_members * 4, hipMemcpyDeviceToHost, s.st));
+		if (out_bytes) BGZF_HIP_TRY(hipMemcpyAsync(s.h_out, s.d_out, out_bytes, hipMemcpyDeviceToHost, s.st));
+		s.busy = true;
+		text_at += out_bytes;
+		m0 = m1;
+	}
+	// what is still in flight, in chunk order: the slot of the chunk before the last one first
+	const int chunks_done = (int) ((z->inf[0].busy ? 1 : 0) + (z->inf[1].busy ? 1 : 0));
+	if (chunks_done == 2) {
+		const int older = z->inf[0].first_member < z->inf[1].first_member ? 0 : 1;
+		if (int rc = inflate_harvest(z, z->inf[older], (uint8_t *) out, &bad, &bad_status)) return rc;
+		if (int rc = inflate_harvest(z, z->inf[older ^ 1], (uint8_t *) out, &bad, &bad_status)) return rc;
+	} else {
+		for (ngm_bgzf::InflateSlot &s : z->inf) if (int rc = inflate_harvest(z, s, (uint8_t *) out, &bad, &bad_status)) return rc;
+	}
+	if (bad >= 0) { ngm::pipeline_set_error("GPU BGZF inflate: member %lld refused (status %u)", bad, bad_status); return -74; }
 	return (long long) total;
 }

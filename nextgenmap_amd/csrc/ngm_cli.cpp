@@ -64,6 +64,8 @@
 #include "../../include/ngm_pipeline.h"
 #include "bam_writer.h"
 #include "gz_inflate.h"
+#include "bam_input.h"
+#include "bgzf_inflate_device.h"
 #include "read_trim.h"
 #include "thread_pool.h"
 
@@ -126,7 +128,7 @@ struct Opts {
 	char pe_delimiter = '/';
 	int device = 0, kmer = 13, kmer_skip = 2, bin_size = 2, mode = 0, corridor = -1, max_read_length = 0, min_mq = 0, max_kfreq = 0;
 	int match = 10, mismatch = 15, gap_read = -1, gap_ref = -1, gap_extend = -1, affine = 0, hard_clip = 0, silent_clip = 0, no_unal = 0, fast_pairing = 0, broken_pairs = 0, max_cmrs = 2147483647;
-	int skip_save = 0, bam = 0, workers = 2, serial_reader = 0;
+	int skip_save = 0, bam = 0, workers = 2, serial_reader = 0, keep_tags = 0;
 	int argos = 0, kmer_min_set = 0;
 	ngm::trim::Options trim;   // -5/--trim5, --max-polya (Options.h:103-104)
 	float argos_min = 0.f;   // --argos-min-score (Default(ARGOS_MINSCORE, 0), Config.cpp:505)
@@ -150,7 +152,7 @@ Opts parse(int argc, char **argv) {
 	Opts o;
 	for (int i = 1; i < argc; ++i) { if (i > 1) o.cmdline += " "; o.cmdline += argv[i]; }  // Config.cpp:565-574
 	enum { KSKIP = 1000, HARD, SILENT, KMIN, MB, MMP, GRP, GFP, MAXCMRS, NOUNAL, NOPROG, MAXRL, BINSZ, MAXKF, VFAST, FAST, SENS, VSENS, DEVICE,
-		SKIPSAVE, BATCH, VARIANT, SHARD, SHARDOUT, KEEPSHARDS, BAMOUT, WORKERS, SERIAL, AFFINE, GEP, PEDELIM, STRATA, BSMAP, BSCUT, MBTT, MBTC, SLAM, FASTPAIR, BROKENPAIRS, REFSCOREBUF, STATSFD, MAXPOLYA, RG0, RG_LAST = RG0 + 11, ARGOS, ARGOSMIN, VCF, UNSUPPORTED };
+		SKIPSAVE, BATCH, VARIANT, SHARD, SHARDOUT, KEEPSHARDS, BAMOUT, WORKERS, SERIAL, AFFINE, GEP, PEDELIM, STRATA, BSMAP, BSCUT, MBTT, MBTC, SLAM, FASTPAIR, BROKENPAIRS, REFSCOREBUF, STATSFD, MAXPOLYA, RG0, RG_LAST = RG0 + 11, ARGOS, ARGOSMIN, VCF, KEEPTAGS, PARSEALL, UNSUPPORTED };
 	static const option lo[] = {
 		{"ref", required_argument, 0, 'r'}, {"qry", required_argument, 0, 'q'}, {"output", required_argument, 0, 'o'},
 		{"cpu-threads", required_argument, 0, 't'}, {"gpu", no_argument, 0, 'g'}, {"sensitivity", required_argument, 0, 's'},
@@ -176,6 +178,7 @@ Opts parse(int argc, char **argv) {
 		{"bs-cutoff", required_argument, 0, BSCUT}, {"match-bonus-tt", required_argument, 0, MBTT}, {"match-bonus-tc", required_argument, 0, MBTC},
 		{"slam-seq", required_argument, 0, SLAM}, {"topn", required_argument, 0, 'n'}, {"strata", no_argument, 0, STRATA},
 		{"argos", no_argument, 0, ARGOS}, {"argos-min-score", required_argument, 0, ARGOSMIN}, {"vcf", required_argument, 0, VCF},
+		{"keep-tags", no_argument, 0, KEEPTAGS}, {"parse-all", no_argument, 0, PARSEALL},
 		{"trim5", required_argument, 0, '5'}, {"max-polya", required_argument, 0, MAXPOLYA}, {"config", required_argument, 0, UNSUPPORTED},
 		{0, 0, 0, 0}};
 	int c, idx = 0;
@@ -258,6 +261,8 @@ Opts parse(int argc, char **argv) {
 		case BROKENPAIRS: o.broken_pairs = 1; break;
 		case ARGOS: o.argos = 1; break;
 		case VCF: o.vcf = optarg; break;
+		case KEEPTAGS: o.keep_tags = 1; break;   // (FASTA / FASTQ records have no tags: refused only with SAM / BAM input, in main)
+		case PARSEALL: break;                    // every record of a SAM / BAM input is a read: the default (Config.cpp:489)
 		case ARGOSMIN: o.argos_min = (float) atof(optarg); break;
 		case UNSUPPORTED: die(std::string("option --") + lo[idx].name + " is not supported by the HIP backend yet");
 		default: die("unknown option (see src/config/Options.h of NextGenMap for the option set)");
@@ -353,6 +358,8 @@ struct MappedFile {
 	int fd = -1;
 	char *owned = nullptr;        // gzip input: the inflated text lives here instead of in a file mapping
 	size_t owned_map = 0;         // != 0: `owned` is an anonymous mapping of this many bytes (gz_inflate.h), else malloc'ed
+	int device = 0;               // BGZF input: the GPU that inflates it
+	int format = ngm::bamin::kFastx;   // of the (inflated) bytes: ngm::bamin::Format
 	bool open(const char *path) {
 		fd = ::open(path, O_RDONLY);
 		if (fd < 0) return false;
@@ -368,12 +375,62 @@ struct MappedFile {
 		trim();
 		return n > 0;
 	}
-	void trim() { while (n > 0 && (p[n - 1] == '\n' || p[n - 1] == '\r' || p[n - 1] == ' ' || p[n - 1] == '\t')) --n; }
+	// (a BAM file is binary: its last bytes belong to its last record)
+	void trim() { format = ngm::bamin::detect(p, n, true); if (format == ngm::bamin::kBam) return; while (n > 0 && (p[n - 1] == '\n' || p[n - 1] == '\r' || p[n - 1] == ' ' || p[n - 1] == '\t')) --n; }
 	// .gz input: inflated ONCE into memory (zlib, one thread per file -- the two files of a pair at the same time) and then read
 	// like a mapped plain file by all pool threads, instead of twice through a line-by-line reader (estimation pass, mapping pass).
 	// Inputs that inflate to more than 64 GB per file go through the serial reader.
+	// BGZF (every BAM, every file written by bgzip): the members are independent, the GPU inflates them (bgzf_inflate_device.h) into the
+	// one reserved range a .gz input lives in.  false: not BGZF, or a member the GPU refuses -- the file then takes the host's route
+	// below, whose message the user sees.  NGM_HIP_BGZF_INFLATE_HOST=1 forces that route.
+	bool inflate_bgzf(const char *path, size_t cap_max) {
+		if (getenv("NGM_HIP_BGZF_INFLATE_HOST")) return false;
+		struct stat st;
+		if (fstat(fd, &st) != 0 || st.st_size < 28) return false;
+		unsigned char head[4];
+		if (pread(fd, head, 4, 0) != 4 || head[2] != 8 || head[3] != 4) return false;   // (BGZF: deflate, FLG = FEXTRA alone)
+		const size_t zn = (size_t) st.st_size;
+		void *zm = mmap(nullptr, zn, PROT_READ, MAP_PRIVATE, fd, 0);
+		if (zm == MAP_FAILED) return false;
+		// the first member carries the BC subfield, wherever among its subfields: the walk over the chain below looks for it the same way
+		if (!ngm::inflate::first_member_is_bgzf((const uint8_t *) zm, zn)) { munmap(zm, zn); return false; }
+		madvise(zm, zn, MADV_SEQUENTIAL);
+		const size_t total = ngm_bgzf_inflated_size(zm, zn);
+		if (total == (size_t) -1 || total == 0 || total > cap_max) { munmap(zm, zn); return false; }
+		const size_t res = ((total + 320 + 4095) & ~(size_t) 4095) + ((size_t) 2 << 20);
+		void *om = mmap(nullptr, res, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);
+		if (om == MAP_FAILED) { munmap(zm, zn); return false; }
+		// (the first touch of the text's pages is the kernel's, on a thread of its own, as for a .gz input: gz_inflate.h)
+		std::thread toucher([om, total] {
+#ifndef MADV_POPULATE_WRITE
+#define MADV_POPULATE_WRITE 23
+#endif
+			for (size_t o = 0; o < total; o += (size_t) 4 << 20) if (madvise((char *) om + o, std::min<size_t>((size_t) 4 << 20, ((total - o) + 4095) & ~(size_t) 4095), MADV_POPULATE_WRITE) != 0) return;
+		});
+		ngm_bgzf *z = ngm_bgzf_create(device);
+		const long long got = z ? ngm_bgzf_inflate(z, zm, zn, om, total) : -1;
+		const float ms = z ? ngm_bgzf_last_kernel_ms(z) : 0.f;
+		if (z) ngm_bgzf_destroy(z);
+		toucher.join();
+		munmap(zm, zn);
+		if (got != (long long) total) {
+			info("INPUT", std::string("GPU BGZF inflate of ") + path + " failed (" + ngm_pipeline_last_error() + "): reading it on the host");
+			munmap(om, res);
+			return false;
+		}
+		static std::atomic<bool> said{false};
+		if (!said.exchange(true)) {
+			char m[200];
+			snprintf(m, sizeof(m), "BGZF blocks inflated on the GPU (%.1f MB of text, kernels %.1f ms)", total / 1e6, ms);
+			info("INPUT", m);
+		}
+		owned = (char *) om; owned_map = res; p = owned; n = total; map_len = 0;
+		trim();
+		return true;
+	}
 	bool inflate_all(const char *path) {
 		const size_t cap_max = (size_t) 64 << 30;
+		if (inflate_bgzf(path, cap_max)) return n > 0;
 		{   // (what gz_inflate.h refuses -- a damaged stream, a wrong CRC or length -- falls back to zlib's inflate below)
 			char *text = nullptr;
 			size_t len = 0, reserved = 0;
@@ -469,6 +526,7 @@ struct Batch {
 	std::vector<size_t> sub0, sub1;
 	int n0 = 0, n1 = 0;                 // records from file 0 / file 1
 	std::vector<Read> owned;            // serial reader: the records themselves
+	std::vector<std::unique_ptr<char[]>> store;   // SAM / BAM input: per sub-range, what the records' views point into where the file does not hold it (decoded bases, qualities + 33, reversed reads)
 	std::vector<Rec> recs;
 	std::vector<std::string> chunks;    // formatted output, in order
 	char *text = nullptr;               // ... or, formatted on the GPU: one piece in a page-locked buffer of the pool
@@ -568,6 +626,50 @@ void build_fastq_index(const MappedFile &f, int step, bool stats, int trim5, Fas
 		ix.max_len = std::max(ix.max_len, rg[r].max_len); ix.min_len = std::min(ix.min_len, rg[r].min_len); ix.sum_len += rg[r].sum_len;
 		for (Read &x : rg[r].sample) ix.sample.push_back(std::move(x));
 	}
+	ix.count = std::min<size_t>(ix.n_nonempty, 10000001);
+	ix.ok = true;
+}
+
+// ---- the same index for a SAM or BAM input (bam_input.h): one walk over the records.  A BAM's records are found through the chain of
+// their block_size fields, which only a serial walk can follow; it reads 36 bytes per record.  !ix.ok: ix.length_error holds the message.
+void build_record_index(const MappedFile &f, int step, int trim5, FastqIndex &ix) {
+	namespace bi = ngm::bamin;
+	ix.step = step;
+	size_t c = 0;
+	auto account = [&](size_t at, const bi::View *v, uint32_t seq_len, auto &&decode) {
+		if (ix.n_records % (size_t) step == 0) ix.sub.push_back(at);
+		++ix.n_records;
+		if (!seq_len) return;   // reads without a sequence are not counted (ReadProvider.cpp:236)
+		++ix.n_nonempty;
+		if (++c > 10000001) return;
+		const size_t len = ngm::trim::estimate_len(seq_len, trim5);
+		ix.max_len = std::max(ix.max_len, len); ix.min_len = std::min(ix.min_len, len); ix.sum_len += len;
+		if (c % 1000 == 0 && c < 10000000) {
+			bi::View w;
+			std::vector<char> store;
+			if (v) w = *v; else decode(w, store);
+			const char *sq = w.seq, *ql = w.qual;
+			uint32_t sl = w.seq_len, qn = 0;
+			ngm::trim::trim5(trim5, sq, sl, ql, qn);
+			ix.sample.push_back(Read{std::string(w.name, w.name_len), std::string(sq, sl), std::string()});
+		}
+	};
+	if (f.format == bi::kBam) {
+		const uint8_t *p = (const uint8_t *) f.p;
+		if (!bi::bam_walk(p, f.n, [&](size_t at, size_t, uint32_t ls) {
+				account(at, nullptr, ls, [&](bi::View &w, std::vector<char> &store) { store.resize(bi::bam_store_bytes(ls) + 1); bi::bam_decode(p, at, w, store.data()); });
+			}, &ix.length_error)) return;
+	} else {
+		std::vector<char> store;
+		for (size_t at = 0, next = 0; at < f.n; at = next) {
+			if (!bi::sam_is_record(f.p, f.n, at, &next)) continue;
+			store.resize(bi::sam_store_bytes(at, next) + 1);
+			bi::View v;
+			if (!bi::sam_decode(f.p, at, next, v, store.data())) { ix.length_error = "Error while parsing read: sequence and quality lengths differ (" + std::string(v.name, v.name_len) + ")"; return; }
+			account(at, &v, v.seq_len, [](bi::View &, std::vector<char> &) {});
+		}
+	}
+	ix.sub.push_back(f.n);
 	ix.count = std::min<size_t>(ix.n_nonempty, 10000001);
 	ix.ok = true;
 }
@@ -816,6 +918,19 @@ int main(int argc, char **argv) {
 	mallopt(M_TOP_PAD, 64 << 20);
 	const auto t_process = std::chrono::steady_clock::now();
 	Opts o = parse(argc, argv);
+	// SAM / BAM input (ReadProvider::DetermineParser): known from the first bytes, so that what it does not go with is refused before any GPU work
+	int in_format = ngm::bamin::kFastx;
+	for (const std::string *path : {&o.qry, &o.qry1, &o.qry2}) if (!path->empty()) in_format = std::max(in_format, (int) ngm::bamin::detect_file(path->c_str()));
+	if (in_format != ngm::bamin::kFastx) {
+		const std::string what = in_format == ngm::bamin::kBam ? "BAM" : "SAM";
+		info("INPUT", "Input is " + what);
+		if (o.keep_tags) die("option --keep-tags is not supported by the HIP backend yet (" + what + " input: the tags of the input records are not copied to the output)");
+		if (!o.qry1.empty() || !o.qry2.empty()) die(what + " input cannot be combined with --qry1/--qry2: give the interleaved mates to -p -q");
+		if (o.broken_pairs) die(what + " input cannot be combined with --broken-pairs");
+		if (o.shard_n > 1) die(what + " input cannot be combined with --shard");
+		if (o.shard_output) die(what + " input cannot be combined with --shard-output");
+		if (o.serial_reader) die(what + " input cannot be combined with --serial-reader: its records are read from the whole file in memory");
+	}
 	if (o.shard_output && (o.devices.size() > 1 || getenv("NGM_HIP_SHARD_SINGLE")) && o.shard_n == 1 && o.stats_fd < 0 && !o.out.empty() && !(o.qry.empty() && o.qry1.empty())) return run_sharded(argc, argv, o);   // (a shard process has its parent's --stats-fd)
 	// a shard process of `-g a,b,... --shard-output` on distinct GPUs: join the communicator of the one collective of the path (the final
 	// statistics all-reduce, RCCL over xGMI) NOW, on a thread of its own -- ncclCommInitRank takes about a second, the load of the index hides it
@@ -865,7 +980,7 @@ int main(int argc, char **argv) {
 		if ((early_gpu_sam || early_gpu_bgzf) && !(o.qry.empty() && o.qry1.empty()) && !o.out.empty()) {
 			size_t peek_max = 0;
 			if (o.max_read_length > 0) peek_max = (size_t) o.max_read_length;
-			else {
+			else if (in_format == ngm::bamin::kFastx) {   // (SAM / BAM: no guess, the buffers are requested once the scan knows the longest read)
 				SeqReader peek((o.qry1.empty() ? o.qry : o.qry1).c_str());
 				Read r;
 				for (int i = 0; i < 256 && peek.ok() && peek.next(r); ++i) if (!r.seq.empty()) peek_max = std::max(peek_max, ngm::trim::estimate_len(r.seq.size(), o.trim.trim5));
@@ -947,12 +1062,15 @@ int main(int argc, char **argv) {
 	if (!o.serial_reader) {
 		bool ok1 = true;
 		std::thread second;   // (a .gz pair inflates both files at the same time)
+		mf0.device = mf1.device = o.device;
 		if (!path1.empty()) second = std::thread([&] { ok1 = mf1.open(path1.c_str()) && mf1.plain_fastq(); });
-		plain = mf0.open(path0.c_str()) && mf0.plain_fastq();
+		plain = mf0.open(path0.c_str()) && (mf0.format != ngm::bamin::kFastx || mf0.plain_fastq());
+		if (mf0.p && mf0.format != in_format) die("the input is not the " + std::string(in_format == ngm::bamin::kBam ? "BAM" : in_format == ngm::bamin::kSam ? "SAM" : "FASTA / FASTQ") + " file its first bytes announce");
 		if (second.joinable()) second.join();
 		plain = plain && ok1;
 		if (!plain) { mf0.release(); mf1.release(); }   // (an inflated copy the serial reader has no use for)
 	}
+	if (in_format != ngm::bamin::kFastx && !plain) die("cannot read " + path0 + " into memory (SAM / BAM input is read from the whole file in memory)");
 	const int batch_reads = o.paired ? (o.batch & ~1) : o.batch;
 	// the splitter hands out whole sub-ranges of sub_step records (per file): the largest power of two up to kSub that divides a batch's share
 	const int per_file_reads = path1.empty() ? batch_reads : batch_reads / 2;
@@ -979,7 +1097,12 @@ int main(int argc, char **argv) {
 		if (plain_ok) {
 			// both passes over a plain input are one parallel scan: record offsets for the splitter, lengths and the sample for the estimates
 			mf0.prefault(); mf1.prefault();
-			build_fastq_index(mf0, sub_step, true, o.trim.trim5, ix0);
+			if (in_format != ngm::bamin::kFastx) {
+				build_record_index(mf0, sub_step, o.trim.trim5, ix0);
+				if (!ix0.ok) die(ix0.length_error);
+			} else {
+				build_fastq_index(mf0, sub_step, true, o.trim.trim5, ix0);
+			}
 			if (ix0.ok && mf1.p) build_fastq_index(mf1, sub_step, false, o.trim.trim5, ix1);
 			if (!ix0.ok || (mf1.p && !ix1.ok)) {
 				// not a strict 4-line record (multi-line sequences, stray blank lines): kseq reads those, so does the serial reader
@@ -1690,6 +1813,43 @@ int main(int argc, char **argv) {
 						if (gpu_sam) memcpy(w.qrows + (size_t) i * q, rc.qual, std::min<size_t>(rc.qual_len, (size_t) q - 1));
 					}
 				}, 4096);
+			} else if (w.rows && in_format != ngm::bamin::kFastx) {
+				// SAM / BAM input: the sub-ranges of the plain route; a record's views point into the file or into the sub-range's store
+				namespace bi = ngm::bamin;
+				const int nsub0 = (int) b->sub0.size() - 1;
+				b->store.clear(); b->store.resize((size_t) nsub0);
+				pool.parallel_for(nsub0, [&](int lo, int hi) {
+					for (int sl = lo; sl < hi; ++sl) {
+						const int cnt = std::min(sub_step, b->n0 - sl * sub_step);
+						size_t at = b->sub0[sl];
+						b->store[sl].reset(new char[2 * (b->sub0[sl + 1] - at) + 16]);
+						char *store = b->store[sl].get();
+						for (int j = 0; j < cnt; ++j) {
+							const int i = sl * sub_step + j;
+							bi::View v;
+							if (in_format == bi::kBam) {
+								size_t size = 0;
+								uint32_t ls = 0;
+								std::string err;
+								if (!bi::bam_check((const uint8_t *) mf0.p, mf0.n, at, &size, &ls, &err)) { if (!bad.exchange(true)) bad_msg = err; return; }
+								bi::bam_decode((const uint8_t *) mf0.p, at, v, store);
+								store += bi::bam_store_bytes(ls);
+								at += size;
+							} else {
+								size_t next = at;
+								while (at < mf0.n && !bi::sam_is_record(mf0.p, mf0.n, at, &next)) at = next;
+								if (at >= mf0.n || !bi::sam_decode(mf0.p, at, next, v, store)) { if (!bad.exchange(true)) bad_msg = "malformed SAM record at byte " + std::to_string(at); return; }
+								store += bi::sam_store_bytes(at, next);
+								at = next;
+							}
+							Rec &r = b->recs[i];
+							r = Rec{v.name, v.seq, v.qual, v.name_len, v.seq_len, v.qual_len, 0, 0};
+							if (o.paired) strip_mate(r.name, r.name_len);
+							r.polya = (uint16_t) ngm::trim::parse_read(o.trim, q, r.seq, r.seq_len, r.qual, r.qual_len, w.rows + (size_t) i * q);
+							if (gpu_sam) memcpy(w.qrows + (size_t) i * q, r.qual, std::min<size_t>(r.qual_len, (size_t) q - 1));
+						}
+					}
+				}, 1);
 			} else if (w.rows) {
 				// plain input: sub-range s of file f holds records [s sub_step, ...) of that file's share of the batch; record j of file f is batch record
 				// j (one file) or 2 j + f (two files)

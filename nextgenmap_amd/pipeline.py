@@ -102,6 +102,10 @@ def _lib():
         lib.ngm_bgzf_bound.argtypes = [C.c_size_t]
         lib.ngm_bgzf_compress.restype = C.c_longlong
         lib.ngm_bgzf_compress.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+        lib.ngm_bgzf_inflated_size.restype = C.c_size_t
+        lib.ngm_bgzf_inflated_size.argtypes = [C.c_char_p, C.c_size_t]
+        lib.ngm_bgzf_inflate.restype = C.c_longlong
+        lib.ngm_bgzf_inflate.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t]
         lib.ngm_bgzf_last_kernel_ms.restype = C.c_float
         lib.ngm_bgzf_last_kernel_ms.argtypes = [C.c_void_p]
         _bound = True
@@ -126,6 +130,20 @@ class Bgzf:
         cap = lib.ngm_bgzf_bound(len(data))
         out = C.create_string_buffer(cap)
         n = lib.ngm_bgzf_compress(self._h, data, len(data), out, cap)
+        if n < 0:
+            raise _err()
+        return out.raw[:n]
+
+    def decompress(self, data):
+        """the text of a run of whole BGZF members, inflated and CRC-checked by the GPU; raises on anything that is not one, and on the
+        first member the GPU refuses (the message names its index)"""
+        lib = _lib()
+        data = bytes(data)
+        cap = lib.ngm_bgzf_inflated_size(data, len(data))
+        if cap == C.c_size_t(-1).value:
+            raise RuntimeError("not a run of whole BGZF members")
+        out = C.create_string_buffer(max(1, cap))
+        n = lib.ngm_bgzf_inflate(self._h, data, len(data), out, cap)
         if n < 0:
             raise _err()
         return out.raw[:n]
