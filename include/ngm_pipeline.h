@@ -259,6 +259,45 @@ float ngm_bgzf_last_kernel_ms(const ngm_bgzf *z);   /* HIP-event time of the las
 size_t ngm_bgzf_inflated_size(const void *members, size_t n);
 long long ngm_bgzf_inflate(ngm_bgzf *z, const void *members, size_t n, void *out, size_t out_cap);
 
+/* ---- `ngm-hip --sort` (csrc/bam_sort.cpp): the BAM records of a whole run kept in the device's memory, sorted there into samtools'
+ * coordinate order -- key ((uint32) refID, pos + 1, flag 0x10), ascending, refID -1 last; equal keys keep input order, which is (seq,
+ * position in the run): the result depends neither on the order of the add calls nor on how the records were cut into runs -- and handed
+ * back as the BGZF members of the sorted file plus its BAI index (SAM specification 5.2).  The sorted records form one byte stream cut into
+ * members of exactly 0xFF00 input bytes (only the last one may be shorter; records straddle members), so the members do not depend on
+ * chunk_bytes.  Records live in segments, one per add; nothing is spilled: when the device's memory is full, add fails with -12.
+ * The index is canonical: per reference its bins ascending, a bin's chunks = the maximal runs of consecutive records of
+ * that reference and bin, then pseudo-bin 37450, the linear index from the records' [pos, end), n_no_coor.
+ * Errors: < 0 with ngm_pipeline_last_error(); the object stays destroyable after every error. */
+typedef struct ngm_bam_sort ngm_bam_sort;
+typedef struct ngm_bam_sort_params {
+	int device;
+	size_t chunk_bytes;  /* uncompressed bytes of sorted records compressed per ngm_bam_sort_next call; 0: 512 members (31.9 MiB);
+	                        rounded down to a multiple of 0xFF00, never below 0xFF00 */
+	size_t max_bytes;    /* cap on the record bytes held; 0: only the device's memory limits it */
+} ngm_bam_sort_params;
+ngm_bam_sort *ngm_bam_sort_create(const ngm_bam_sort_params *p);
+void ngm_bam_sort_destroy(ngm_bam_sort *s);
+/* a run of whole uncompressed BAM records (block_size chain) in host memory; seq orders the runs (any order of calls, every seq once);
+ * thread-safe against other add calls.  The chain is walked on the host before a byte reaches the device: -22 with "ngm_bam_sort_add: ...
+ * record <i> ..." for a chain that does not end exactly at n_bytes, a block_size below 32, or a record whose name, CIGAR, sequence and
+ * qualities exceed its block_size; -22 for a duplicate seq and an add after finish; -12 for a total above max_bytes. */
+int ngm_bam_sort_add(ngm_bam_sort *s, uint64_t seq, const void *records, size_t n_bytes);
+/* no add after this: validates, sorts; n_ref = entries of the BAM's reference dictionary.  -22 names seq and the index within its run of
+ * the first record with a refID at or above n_ref, with a refID >= 0 and pos < 0, or with an end above 2^29. */
+int ngm_bam_sort_finish(ngm_bam_sort *s, int n_ref);
+/* the next run of whole BGZF members of the sorted record stream; 0: done; > out_cap: nothing copied, call again with that much */
+long long ngm_bam_sort_next(ngm_bam_sort *s, void *out, size_t out_cap);
+/* after the last next(): the BAI file's bytes; first_member_offset = file offset of the first member next() returned; out NULL: the size */
+long long ngm_bam_sort_index(ngm_bam_sort *s, uint64_t first_member_offset, void *out, size_t out_cap);
+/* counts: records, record bytes, members written, chunks (ngm_bam_sort_next calls that compressed one), bins of the index (after
+ * ngm_bam_sort_index); ms: kernel ms of keys / sort / gather / deflate / index (HIP events) */
+int ngm_bam_sort_stats(const ngm_bam_sort *s, uint64_t counts[5], float ms[5]);
+/* with ngm_sam_options::bam set: ngm_mapper_map_sam* hands the batch's records to s under the mapper's batch seq
+ * (ngm_mapper_set_batch_seq) and returns 0 bytes instead of BGZF members; NULL detaches.  Same device: a device-to-device copy; another
+ * device: the records are downloaded and go through ngm_bam_sort_add.  When the sorter has no device memory left for the batch (its -12),
+ * ngm_mapper_map_sam* returns -28, so that the caller can tell it from the mapper's own allocations (-12). */
+int ngm_mapper_set_bam_sorter(ngm_mapper *m, ngm_bam_sort *s);
+
 /* page-locked host memory for read batches (the H2D copy then runs at PCIe rate without a staging copy) */
 void *ngm_host_alloc(size_t bytes);
 void ngm_host_free(void *p);

@@ -120,12 +120,17 @@ __device__ inline void build_lengths(const uint32_t *freq, int n, int max_bits, 
 	}
 	__syncthreads();
 	if (tid == 0) {
-		int overflow = (int) bl[max_bits + 2];
-		while (overflow > 0) {   // zlib's gen_bitlen: move one leaf down from the deepest level that has one, two of the overflowing leaves take its place
+		// how far the clamped lengths over-subscribe the code, in units of 2^-max_bits: every move below takes one unit off.  (Half the
+		// number of clamped leaves -- zlib's count, which there includes internal nodes -- is too few once leaves lie three or more
+		// levels below max_bits: the code stayed over-subscribed and the member did not inflate.)
+		int over = -(1 << max_bits);
+		for (int b = 1; b <= max_bits; ++b) over += (int) (bl[b] << (max_bits - b));
+		if (bl[max_bits + 2] == 0) over = 0;
+		while (over > 0) {   // zlib's gen_bitlen: move one leaf down from the deepest level that has one, one of the overflowing leaves becomes its brother
 			int bits = max_bits - 1;
 			while (bl[bits] == 0) --bits;
 			bl[bits] -= 1; bl[bits + 1] += 2; bl[max_bits] -= 1;
-			overflow -= 2;
+			over -= 1;
 		}
 	}
 	__syncthreads();

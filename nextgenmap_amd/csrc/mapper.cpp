@@ -1446,7 +1446,19 @@ static int map_impl(ngm_mapper *m, int n, const char *reads, const void *d_reads
 		if (bam && total > 0) {
 			// the records stay in HBM: their BGZF blocks are written there too (bgzf_device.h, the compressor's own stream -- beside the next
 			// instance's kernels), and only those travel
-			if (sam->out_cap < ngm_bgzf_bound((size_t) total)) sam->text_bytes = (long long) ngm_bgzf_bound((size_t) total);   // (> out_cap: ngm_mapper_sam_fetch with a buffer of that size)
+			if (m->sorter) {
+				// --sort: the records stay in HBM for the whole run (bam_sort.cpp); nothing travels now
+				int rc;
+				if (ngm::bam_sort_device(m->sorter) == r->device) rc = ngm::bam_sort_add_device(m->sorter, m->batch_seq, m->d_sam_text.p, (size_t) total, m->d_sam_off.p, (size_t) units);
+				else {
+					m->sorter_host.resize((size_t) total);
+					MAP_HIP_TRY(hipMemcpy(m->sorter_host.data(), m->d_sam_text.p, (size_t) total, hipMemcpyDeviceToHost));
+					rc = ngm_bam_sort_add(m->sorter, m->batch_seq, m->sorter_host.data(), (size_t) total);
+				}
+				if (rc < 0) return rc == -12 ? -28 : rc;   // (-28: the sorter is full -- not one of the mapper's own allocations, which say -12)
+				sam->text_bytes = 0;
+				m->sam_text_bytes = 0;
+			} else if (sam->out_cap < ngm_bgzf_bound((size_t) total)) sam->text_bytes = (long long) ngm_bgzf_bound((size_t) total);   // (> out_cap: ngm_mapper_sam_fetch with a buffer of that size)
 			else {
 				const long long zlen = ngm_bgzf_compress_device(m->bz, m->d_sam_text.p, (size_t) total, sam->out, sam->out_cap);
 				if (zlen < 0) return (int) zlen;
@@ -1483,6 +1495,7 @@ void ngm_pair_state_destroy(ngm_pair_state *ps) { delete ps; }
 int ngm_mapper_set_pair_state(ngm_mapper *m, ngm_pair_state *ps) { if (!m) return -22; m->ps = ps; return 0; }
 int ngm_mapper_set_batch_seq(ngm_mapper *m, uint64_t seq) { if (!m) return -22; m->batch_seq = seq; return 0; }
 int ngm_mapper_set_fast_pairing(ngm_mapper *m, int on) { if (!m) return -22; m->fast_pairing = on ? 1 : 0; return 0; }
+int ngm_mapper_set_bam_sorter(ngm_mapper *m, ngm_bam_sort *s) { if (!m) return -22; m->sorter = s; return 0; }
 
 void *ngm_host_alloc(size_t bytes) {
 	void *p = nullptr;

@@ -128,6 +128,8 @@ struct ngm_mapper {
 	// SAM text on the GPU (sam_device.h)
 	ngm_sam_options sam_opt{};
 	ngm_bgzf *bz = nullptr;   // sam_opt.bam: the BGZF compressor of this mapper's BAM records
+	ngm_bam_sort *sorter = nullptr;   // ngm_mapper_set_bam_sorter: the batch's BAM records go there instead of through bz
+	std::vector<char> sorter_host;    // ... by way of the host when the sorter lives on another device
 	bool sam_ready = false;
 	std::string sam_rg;
 	ngm::DevBuf<char> d_sam_contig_names, d_sam_rg, d_sam_names, d_sam_text;

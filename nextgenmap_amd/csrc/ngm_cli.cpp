@@ -12,7 +12,9 @@
 // Single-end and paired-end (-p -q interleaved, --qry1/--qry2), --affine, -n/--strata, SAM and BAM (--bam) output, one or
 // several GPUs (-g 0,1,...), and --argos (ScoreWriter's lines, src/writer/ScoreWriter.cpp: every scored candidate of a read, ordered on the
 // GPU -- single-end only, see ngm_mapper_map_argos), bisulfite (--bs-mapping) and SLAM-seq (--slam-seq) mapping, -5/--trim5 and --max-polya
-// (csrc/read_trim.h).  Not supported (rejected loudly): --vcf with --bs-mapping, --max-polya with --argos or --vcf, SAM/BAM *input*, --config.
+// (csrc/read_trim.h), and --sort (ours, with --bam: the records of the whole run stay in GPU memory, are sorted there into coordinate order and
+// written as the sorted BAM plus <output>.bai, csrc/bam_sort.cpp; not with --argos, --shard, --shard-output, NGM_HIP_BAM_ZLIB=1, nor a
+// contig above 2^29 bases).  Not supported (rejected loudly): --vcf with --bs-mapping, --max-polya with --argos or --vcf, SAM/BAM *input*, --config.
 //
 // Pass 2 is a pipeline, not a loop:
 //   splitter (1 thread)   cuts the input into batches: for plain 4-line FASTQ it only counts line ends in the mapped file
@@ -130,6 +132,7 @@ struct Opts {
 	int match = 10, mismatch = 15, gap_read = -1, gap_ref = -1, gap_extend = -1, affine = 0, hard_clip = 0, silent_clip = 0, no_unal = 0, fast_pairing = 0, broken_pairs = 0, max_cmrs = 2147483647;
 	int skip_save = 0, bam = 0, workers = 2, serial_reader = 0, keep_tags = 0;
 	int argos = 0, kmer_min_set = 0;
+	int sort = 0;   // --sort (ours): the BAM coordinate-sorted on the GPU, with its .bai (csrc/bam_sort.cpp)
 	ngm::trim::Options trim;   // -5/--trim5, --max-polya (Options.h:103-104)
 	float argos_min = 0.f;   // --argos-min-score (Default(ARGOS_MINSCORE, 0), Config.cpp:505)
 	int bs_mapping = 0, bs_cutoff = 6, match_tt = -1, match_tc = -1, match_set = 0, mismatch_set = 0, slam_seq = 0;
@@ -152,7 +155,7 @@ Opts parse(int argc, char **argv) {
 	Opts o;
 	for (int i = 1; i < argc; ++i) { if (i > 1) o.cmdline += " "; o.cmdline += argv[i]; }  // Config.cpp:565-574
 	enum { KSKIP = 1000, HARD, SILENT, KMIN, MB, MMP, GRP, GFP, MAXCMRS, NOUNAL, NOPROG, MAXRL, BINSZ, MAXKF, VFAST, FAST, SENS, VSENS, DEVICE,
-		SKIPSAVE, BATCH, VARIANT, SHARD, SHARDOUT, KEEPSHARDS, BAMOUT, WORKERS, SERIAL, AFFINE, GEP, PEDELIM, STRATA, BSMAP, BSCUT, MBTT, MBTC, SLAM, FASTPAIR, BROKENPAIRS, REFSCOREBUF, STATSFD, MAXPOLYA, RG0, RG_LAST = RG0 + 11, ARGOS, ARGOSMIN, VCF, KEEPTAGS, PARSEALL, UNSUPPORTED };
+		SKIPSAVE, BATCH, VARIANT, SHARD, SHARDOUT, KEEPSHARDS, BAMOUT, WORKERS, SERIAL, AFFINE, GEP, PEDELIM, STRATA, BSMAP, BSCUT, MBTT, MBTC, SLAM, FASTPAIR, BROKENPAIRS, REFSCOREBUF, STATSFD, MAXPOLYA, RG0, RG_LAST = RG0 + 11, ARGOS, ARGOSMIN, VCF, KEEPTAGS, PARSEALL, SORTOUT, UNSUPPORTED };
 	static const option lo[] = {
 		{"ref", required_argument, 0, 'r'}, {"qry", required_argument, 0, 'q'}, {"output", required_argument, 0, 'o'},
 		{"cpu-threads", required_argument, 0, 't'}, {"gpu", no_argument, 0, 'g'}, {"sensitivity", required_argument, 0, 's'},
@@ -178,7 +181,7 @@ Opts parse(int argc, char **argv) {
 		{"bs-cutoff", required_argument, 0, BSCUT}, {"match-bonus-tt", required_argument, 0, MBTT}, {"match-bonus-tc", required_argument, 0, MBTC},
 		{"slam-seq", required_argument, 0, SLAM}, {"topn", required_argument, 0, 'n'}, {"strata", no_argument, 0, STRATA},
 		{"argos", no_argument, 0, ARGOS}, {"argos-min-score", required_argument, 0, ARGOSMIN}, {"vcf", required_argument, 0, VCF},
-		{"keep-tags", no_argument, 0, KEEPTAGS}, {"parse-all", no_argument, 0, PARSEALL},
+		{"keep-tags", no_argument, 0, KEEPTAGS}, {"parse-all", no_argument, 0, PARSEALL}, {"sort", no_argument, 0, SORTOUT},
 		{"trim5", required_argument, 0, '5'}, {"max-polya", required_argument, 0, MAXPOLYA}, {"config", required_argument, 0, UNSUPPORTED},
 		{0, 0, 0, 0}};
 	int c, idx = 0;
@@ -264,11 +267,20 @@ Opts parse(int argc, char **argv) {
 		case KEEPTAGS: o.keep_tags = 1; break;   // (FASTA / FASTQ records have no tags: refused only with SAM / BAM input, in main)
 		case PARSEALL: break;                    // every record of a SAM / BAM input is a read: the default (Config.cpp:489)
 		case ARGOSMIN: o.argos_min = (float) atof(optarg); break;
+		case SORTOUT: o.sort = 1; break;
 		case UNSUPPORTED: die(std::string("option --") + lo[idx].name + " is not supported by the HIP backend yet");
 		default: die("unknown option (see src/config/Options.h of NextGenMap for the option set)");
 		}
 	}
 	if (o.ref.empty()) die("no reference given (-r/--ref)");
+	if (o.sort) {
+		// the sort is over the records of the whole run, kept in the first GPU's memory; refused before any GPU work
+		if (o.argos) die("--sort cannot be combined with --argos: argos output is text lines, not BAM records");
+		if (!o.bam) die("--sort needs -b/--bam: the sorted output is a BAM file with its .bai index (sorted SAM text is not written)");
+		if (o.shard_n > 1) die("--sort cannot be combined with --shard: the sort is over the whole run, not over one shard of it");
+		if (o.shard_output) die("--sort cannot be combined with --shard-output: the sort is over the whole run, in one process");
+		if (getenv("NGM_HIP_BAM_ZLIB")) die("--sort cannot be combined with NGM_HIP_BAM_ZLIB=1: the blocks of a sorted file only come from the GPU");
+	}
 	if (o.argos) {
 		// ScoreWriter has no paired or binary form (DoWritePair throws, src/writer/ScoreWriter.cpp:75-77); refused before any GPU work
 		if (!o.qry1.empty() || !o.qry2.empty()) die("--argos cannot be combined with --qry1/--qry2: the argos writer is single-end only (ScoreWriter::DoWritePair is not implemented)");
@@ -1242,6 +1254,7 @@ int main(int argc, char **argv) {
 	// mapping of each batch's range filled by the pool -- 1.6 M reads/s, the page faults cost more than the lock.
 	const int out_fd = ::open(o.out.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
 	if (out_fd < 0) die("cannot write " + o.out);
+	if (o.sort) (void) unlink((o.out + ".bai").c_str());   // (an index of an earlier file must not stand beside this one if the run fails)
 	uint64_t out_off = 0;
 	auto put_all = [&](const char *p, size_t n, uint64_t off) -> bool {
 		while (n) {
@@ -1255,9 +1268,11 @@ int main(int argc, char **argv) {
 	std::vector<std::string> contig_names;
 	std::vector<uint64_t> contig_lens;
 	for (int i = 0; i < ngm_ref_contig_count(ref); ++i) { contig_names.push_back(ngm_ref_contig_name(ref, i)); contig_lens.push_back(ngm_ref_contig_len(ref, i)); }
+	if (o.sort) for (size_t i = 0; i < contig_lens.size(); ++i) if (contig_lens[i] > ((uint64_t) 1 << 29))
+		die("--sort cannot index contig " + contig_names[i] + ": it has more than 2^29 bases, beyond what a BAI index reaches (a CSI index is not built)");
 	{
 		static const char *tag[12] = {"ID", "CN", "DS", "DT", "FO", "KS", "LB", "PG", "PI", "PL", "PU", "SM"};
-		std::string h = "@HD\tVN:1.0\tSO:unsorted\n";
+		std::string h = o.sort ? "@HD\tVN:1.0\tSO:coordinate\n" : "@HD\tVN:1.0\tSO:unsorted\n";
 		std::string rg;
 		if (!o.rg[0].empty()) {  // SAMWriter.cpp:46-80
 			rg = "@RG\tID:" + o.rg[0];
@@ -1342,6 +1357,27 @@ int main(int argc, char **argv) {
 			if (!workers[w].bz) die(ngm_pipeline_last_error());
 		}
 	}
+	// --sort: one sorter on the first device keeps the run's records; the mappers of that GPU hand theirs over device to device, the others
+	// (and the host-formatted routes below) through ngm_bam_sort_add
+	ngm_bam_sort *sorter = nullptr;
+	if (o.sort) {
+		ngm_bam_sort_params sp{};
+		sp.device = o.devices[0];
+		sorter = ngm_bam_sort_create(&sp);
+		if (!sorter) die(ngm_pipeline_last_error());
+		if (gpu_sam) for (Worker &w : workers) if (ngm_mapper_set_bam_sorter(w.m, sorter) < 0) die(ngm_pipeline_last_error());
+	}
+	auto pipeline_error = [&](long long rc, bool from_mapper = false) -> std::string {   // (the sorter never spills: -12 from it, -28 through a mapper, ends the run with what it held)
+		std::string e = ngm_pipeline_last_error();
+		if (sorter && rc == (from_mapper ? -28 : -12)) {
+			uint64_t sc[5] = {0, 0, 0, 0, 0};
+			(void) ngm_bam_sort_stats(sorter, sc, nullptr);
+			char pre[160];
+			snprintf(pre, sizeof(pre), "--sort keeps the run's records in GPU memory (%.2f GiB so far): ", (double) sc[1] / (double) (1ull << 30));
+			e = pre + e;
+		}
+		return e;
+	};
 
 	// ---- the record -> SAM line code (SAMWriter::DoWriteReadGeneric, SAMWriter.cpp:98-228) -----------------------------
 	struct View { const Rec *r; const ngm_hit *h; const char *row; int L; const char *cigar, *md; };
@@ -1950,9 +1986,9 @@ int main(int argc, char **argv) {
 					tb.cap = (size_t) len + (1u << 20);
 					tb.p = (char *) ngm_host_alloc(tb.cap);
 					const int got = tb.p ? ngm_mapper_sam_fetch(w.m, tb.p, tb.cap) : -1;
-					if (got < 0) len = -1; else if (o.bam) len = got;   // (BAM: the BGZF blocks are made by the fetch; it says how long they are)
+					if (got < 0) len = got; else if (o.bam) len = got;   // (BAM: the BGZF blocks are made by the fetch; it says how long they are)
 				}
-				if (len < 0) { fail(ngm_pipeline_last_error()); std::lock_guard<std::mutex> lk(text_mu); if (tb.p) text_free.push_back(tb); text_cv.notify_one(); continue; }
+				if (len < 0) { fail(pipeline_error(len, true)); std::lock_guard<std::mutex> lk(text_mu); if (tb.p) text_free.push_back(tb); text_cv.notify_one(); continue; }
 				t_map_us += us_since(tm);
 				if (o.paired) { uint64_t ps3[3] = {0, 0, 0}; if (ngm_mapper_last_pair_stats(w.m, ps3) == 0) for (int k2 = 0; k2 < 3; ++k2) pair_stat[k2] += ps3[k2]; }
 				{ float kms[8] = {0}; if (ngm_mapper_last_kernel_ms(w.m, kms) == 0) { double sum = sam_ms; for (int k2 = 0; k2 < 7; ++k2) sum += kms[k2]; t_gpu_us += (long long) (sum * 1000.0); } }
@@ -2020,10 +2056,14 @@ int main(int argc, char **argv) {
 						if (!w.bam_raw || !w.bam_out) { w.bam_raw_cap = w.bam_out_cap = 0; fail(ngm_pipeline_last_error()); continue; }
 					}
 					pool.parallel_for(n_chunks, [&](int lo, int hi) { for (int c = lo; c < hi; ++c) memcpy(w.bam_raw + off[c], b->chunks[c].data(), b->chunks[c].size()); }, 1);
-					zlen = ngm_bgzf_compress(w.bz, w.bam_raw, total, w.bam_out, w.bam_out_cap);
-					if (zlen < 0) { fail(ngm_pipeline_last_error()); continue; }
-					t_bgzf_gpu_us += (long long) (ngm_bgzf_last_kernel_ms(w.bz) * 1000.0f);
-					bgzf_in_bytes += total; bgzf_out_bytes += (unsigned long long) zlen;
+					if (sorter) {   // --sort: the batch's records go to the sorter as they are; the writer gets nothing now
+						if (const int rc = ngm_bam_sort_add(sorter, b->seq, w.bam_raw, total); rc < 0) { fail(pipeline_error(rc)); continue; }
+					} else {
+						zlen = ngm_bgzf_compress(w.bz, w.bam_raw, total, w.bam_out, w.bam_out_cap);
+						if (zlen < 0) { fail(ngm_pipeline_last_error()); continue; }
+						t_bgzf_gpu_us += (long long) (ngm_bgzf_last_kernel_ms(w.bz) * 1000.0f);
+						bgzf_in_bytes += total; bgzf_out_bytes += (unsigned long long) zlen;
+					}
 				}
 				const int n_out = (int) std::max<long long>(1, std::min<long long>(n_chunks, zlen / (2 << 20) + 1));
 				b->chunks.resize((size_t) n_out);
@@ -2112,6 +2152,50 @@ int main(int argc, char **argv) {
 	{ std::lock_guard<std::mutex> lk(out_mu); workers_done = true; }
 	out_cv.notify_all();
 	writer.join();
+	if (sorter && !failed) {
+		// --sort: every record of the run is in the sorter now.  One sort, then the sorted stream chunk by chunk as BGZF members behind the
+		// header members, the end-of-file member below, and the index next to the file
+		const auto t_sort = std::chrono::steady_clock::now();
+		const uint64_t first_member = out_off;
+		size_t cap = (size_t) 40 << 20;
+		char *buf = (char *) ngm_host_alloc(cap);
+		if (!buf) fail(ngm_pipeline_last_error());
+		else if (const int rc = ngm_bam_sort_finish(sorter, (int) contig_names.size()); rc < 0) fail(pipeline_error(rc));
+		while (!failed) {
+			const long long got = ngm_bam_sort_next(sorter, buf, cap);
+			if (got < 0) { fail(pipeline_error(got)); break; }
+			if (got == 0) break;
+			if ((size_t) got > cap) {
+				ngm_host_free(buf);
+				cap = (size_t) got;
+				buf = (char *) ngm_host_alloc(cap);
+				if (!buf) { fail(ngm_pipeline_last_error()); break; }
+				continue;
+			}
+			if (!put_all(buf, (size_t) got, out_off)) { fail("write error on " + o.out); break; }
+			out_off += (uint64_t) got;
+		}
+		ngm_host_free(buf);
+		if (!failed) {
+			const long long ilen = ngm_bam_sort_index(sorter, first_member, nullptr, 0);
+			std::string bai(ilen > 0 ? (size_t) ilen : 0, '\0');
+			if (ilen < 0 || ngm_bam_sort_index(sorter, first_member, &bai[0], bai.size()) != ilen) fail(pipeline_error(ilen));
+			else {
+				const std::string bai_path = o.out + ".bai";
+				FILE *bf = fopen(bai_path.c_str(), "wb");
+				if (!bf || fwrite(bai.data(), 1, bai.size(), bf) != bai.size() || fclose(bf) != 0) fail("write error on " + bai_path);
+			}
+		}
+		if (!failed) {
+			uint64_t sc[5] = {0, 0, 0, 0, 0};
+			float sm[5] = {0, 0, 0, 0, 0};
+			(void) ngm_bam_sort_stats(sorter, sc, sm);
+			snprintf(msg, sizeof(msg), "Sorted on the GPU: %llu records (%.1f MiB held in GPU memory); kernels: keys %.2f ms, sort %.2f ms, gather %.2f ms, deflate %.2f ms, index %.2f ms; "
+					"%llu members in %llu chunks, %llu bins; %.3f s after the last batch", (unsigned long long) sc[0], (double) sc[1] / (double) (1 << 20), sm[0], sm[1], sm[2], sm[3], sm[4],
+					(unsigned long long) sc[2], (unsigned long long) sc[3], (unsigned long long) sc[4], std::chrono::duration<double>(std::chrono::steady_clock::now() - t_sort).count());
+			info("MAIN", msg);
+		}
+	}
 	if (o.bam && o.shard_i == o.shard_n - 1) { std::string z; ngm::bam::bgzf_eof(z); if (!put_all(z.data(), z.size(), out_off)) fail("write error on " + o.out); out_off += z.size(); }   // (--shard: the end-of-file block travels with the last shard)
 	if (close(out_fd) != 0) fail("write error on " + o.out);
 	if (failed) die(fail_msg);
@@ -2232,6 +2316,7 @@ int main(int argc, char **argv) {
 	if (const char *pf = getenv("NGM_HIP_PROFILE")) prof::dump(pf);
 	for (Worker &w : workers) { ngm_mapper_destroy(w.m); ngm_host_free(w.rows); ngm_host_free(w.qrows); ngm_host_free(w.names); ngm_host_free(w.meta); ngm_host_free(w.polya);
 		ngm_bgzf_destroy(w.bz); ngm_host_free(w.bam_raw); ngm_host_free(w.bam_out); }
+	ngm_bam_sort_destroy(sorter);
 	for (TextBuf &t : text_free) ngm_host_free(t.p);
 	ngm_pair_state_destroy(pair_state);
 	for (ngm_ref *r2 : refs) ngm_ref_destroy(r2);

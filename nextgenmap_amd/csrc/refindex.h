@@ -119,6 +119,10 @@ int ngm_ref_ensure_buckets(const ngm_ref *r, int kind);
 
 namespace ngm {
 void pipeline_set_error(const char *fmt, ...);
+// bam_sort.cpp, for the mapper's SAM stage: the device formatter's records of a batch handed to a sorter on the same device (d_unit_off:
+// units + 1 offsets into d_records, the last one n_bytes; both complete), and the device a sorter lives on
+int bam_sort_add_device(struct ::ngm_bam_sort *s, uint64_t seq, const void *d_records, size_t n_bytes, const uint32_t *d_unit_off, size_t units);
+int bam_sort_device(const struct ::ngm_bam_sort *s);
 // k-mer integer as the reference builds it: 2 bits per base, A0 C1 T2 G3 ((c >> 1) & 3, CSstatic.cpp:20-22)
 inline uint32_t kmer_code_of_class(uint32_t cls) { return cls == 2 ? 3u : (cls == 3 ? 2u : cls); }
 // reverse complement of a k-mer integer (PrefixTable.cpp:94-108), valid for 2k <= 32

@@ -34,6 +34,10 @@ HIT_DTYPE = np.dtype([("mapped", "i4"), ("contig", "i4"), ("pos", "u8"), ("rever
 _bound = False
 
 
+class BamSortParams(C.Structure):   # ngm_bam_sort_params
+    _fields_ = [("device", C.c_int), ("chunk_bytes", C.c_size_t), ("max_bytes", C.c_size_t)]
+
+
 def _lib():
     global _bound
     lib = load_library()
@@ -108,6 +112,17 @@ def _lib():
         lib.ngm_bgzf_inflate.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t]
         lib.ngm_bgzf_last_kernel_ms.restype = C.c_float
         lib.ngm_bgzf_last_kernel_ms.argtypes = [C.c_void_p]
+        lib.ngm_bam_sort_create.restype = C.c_void_p
+        lib.ngm_bam_sort_create.argtypes = [C.POINTER(BamSortParams)]
+        lib.ngm_bam_sort_destroy.argtypes = [C.c_void_p]
+        lib.ngm_bam_sort_add.argtypes = [C.c_void_p, C.c_uint64, C.c_char_p, C.c_size_t]
+        lib.ngm_bam_sort_finish.argtypes = [C.c_void_p, C.c_int]
+        lib.ngm_bam_sort_next.restype = C.c_longlong
+        lib.ngm_bam_sort_next.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.ngm_bam_sort_index.restype = C.c_longlong
+        lib.ngm_bam_sort_index.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t]
+        lib.ngm_bam_sort_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.ngm_mapper_set_bam_sorter.argtypes = [C.c_void_p, C.c_void_p]
         _bound = True
     return lib
 
@@ -154,6 +169,75 @@ class Bgzf:
     def close(self):
         if self._h:
             _lib().ngm_bgzf_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BamSorter:
+    """The BAM records of a run kept in GPU memory, sorted there into coordinate order and handed back as the BGZF members of the sorted
+    file plus its BAI index (include/ngm_pipeline.h, ngm_bam_sort_*): what `ngm-hip --sort` writes."""
+
+    def __init__(self, device=0, chunk_bytes=0, max_bytes=0):
+        p = BamSortParams(device, chunk_bytes, max_bytes)
+        self._h = _lib().ngm_bam_sort_create(C.byref(p))
+        if not self._h:
+            raise _err()
+
+    def add(self, seq, records):
+        """a run of whole uncompressed BAM records; seq orders the runs"""
+        records = bytes(records)
+        if _lib().ngm_bam_sort_add(self._h, seq, records, len(records)) < 0:
+            raise _err()
+
+    def finish(self, n_ref):
+        if _lib().ngm_bam_sort_finish(self._h, n_ref) < 0:
+            raise _err()
+
+    def members(self):
+        """the sorted stream, one run of whole BGZF members per chunk"""
+        lib = _lib()
+        cap = 1 << 16
+        out = C.create_string_buffer(cap)
+        while True:
+            n = lib.ngm_bam_sort_next(self._h, out, cap)
+            if n < 0:
+                raise _err()
+            if n == 0:
+                return
+            if n > cap:
+                cap = n
+                out = C.create_string_buffer(cap)
+                continue
+            yield out.raw[:n]
+
+    def index(self, first_member_offset):
+        """the BAI file's bytes, after the last of members()"""
+        lib = _lib()
+        n = lib.ngm_bam_sort_index(self._h, first_member_offset, None, 0)
+        if n < 0:
+            raise _err()
+        out = C.create_string_buffer(max(1, n))
+        if lib.ngm_bam_sort_index(self._h, first_member_offset, out, n) != n:
+            raise _err()
+        return out.raw[:n]
+
+    def stats(self):
+        counts = (C.c_uint64 * 5)()
+        ms = (C.c_float * 5)()
+        if _lib().ngm_bam_sort_stats(self._h, counts, ms) < 0:
+            raise _err()
+        d = dict(zip(("records", "record_bytes", "members", "chunks", "bins"), (int(x) for x in counts)))
+        d.update(zip(("keys_ms", "sort_ms", "gather_ms", "deflate_ms", "index_ms"), (float(x) for x in ms)))
+        return d
+
+    def close(self):
+        if self._h:
+            _lib().ngm_bam_sort_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -369,6 +453,11 @@ class Mapper:
         rows = np.ascontiguousarray(rows, dtype=np.uint8)
         hits, cig, md = self.map_se_raw(rows)
         return hits, [bytes(r).split(b"\0", 1)[0] for r in cig], [bytes(r).split(b"\0", 1)[0] for r in md]
+
+    def set_bam_sorter(self, sorter):
+        """map_sam(bam=True) hands its records to `sorter` (a BamSorter, or None to detach) instead of returning BGZF members"""
+        if self.lib.ngm_mapper_set_bam_sorter(self.h, sorter._h if sorter is not None else None) < 0:
+            raise _err()
 
     def last_kernel_ms(self):
         ms = (C.c_float * 8)()
