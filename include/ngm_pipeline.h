@@ -298,6 +298,43 @@ int ngm_bam_sort_stats(const ngm_bam_sort *s, uint64_t counts[5], float ms[5]);
  * ngm_mapper_map_sam* returns -28, so that the caller can tell it from the mapper's own allocations (-12). */
 int ngm_mapper_set_bam_sorter(ngm_mapper *m, ngm_bam_sort *s);
 
+/* ---- `ngm-hip --coverage` (csrc/coverage.cpp): the per-base read depth of a run as bedGraph text.  One int32 counter per base of every
+ * contig (plus one slot per contig) lives in the device's memory for the whole run: 4 bytes per base, 12.4 GB for a genome of GRCh38's size.
+ * An alignment covers the reference bases under its M, = and X operations; D and N advance without covering; I, S, H and P do neither;
+ * what would lie past the contig's last base is clipped.  Lines: contig \t start \t end \t depth \n, start 0-based, end exclusive, depth > 0,
+ * one per maximal run of equal depth inside one contig, contigs in the order given, runs ascending, no header.  The sums are integers: the
+ * text depends on the set of alignments only, not on how they were cut into calls or which thread made them.  Depth is a 32-bit count.
+ * Errors: < 0 with ngm_pipeline_last_error(); the object stays destroyable after every error. */
+typedef struct ngm_coverage ngm_coverage;
+typedef struct ngm_coverage_params {
+	int device;
+	int n_ref;
+	const uint32_t *ref_len;
+	const char *const *ref_name;
+	size_t scan_chunk; /* counters scanned at a time by the finish (its temporaries are 5 bytes per counter of a chunk plus the chunk's lines);
+	                      0: 2^25; at most 2^30 */
+} ngm_coverage_params;
+/* allocates and zeroes (bases + n_ref) * 4 bytes on the device; NULL with the error set when that fails */
+ngm_coverage *ngm_coverage_create(const ngm_coverage_params *p);
+void ngm_coverage_destroy(ngm_coverage *c);
+/* n alignments: contig, 0-based position, CIGAR text cigar_text[cigar_off[i] .. cigar_off[i + 1]).  Thread-safe.  Validated on the host
+ * first: -22 with "ngm_coverage_add: alignment <i>: ..." names the first one with a ref_id outside [0, n_ref), a negative position, an
+ * unknown operation character, a number that overflows 2^28, an operation without a number or a number without an operation -- and adds
+ * nothing of the call.  -22 after ngm_coverage_finish. */
+int ngm_coverage_add(ngm_coverage *c, const int32_t *ref_id, const int32_t *pos0, const uint32_t *cigar_off /* [n + 1] */, const char *cigar_text, size_t n);
+/* no add after this; waits for the adds in flight and sets the scan up */
+int ngm_coverage_finish(ngm_coverage *c);
+/* the next lines of the file, made chunk by chunk as they are asked for: whole lines only; 0 at the end; > out_cap: nothing copied, call
+ * again with that much */
+long long ngm_coverage_next(ngm_coverage *c, void *out, size_t out_cap);
+/* counts: alignments added, and of the lines handed out so far covered bases (the sum of (end - start) * depth), runs, text bytes;
+ * ms: kernel ms of add / scan / run heads / text (HIP events) */
+int ngm_coverage_stats(const ngm_coverage *c, uint64_t counts[4], float ms[4]);
+/* every batch ngm_mapper_map_sam* finishes adds the records it writes with flag bits 0x4 and 0x100 clear -- after the output filters, the
+ * "no sequence" reads and the lost pairs -- to c, in place from the batch's arrays in device memory, on the mapper's stream; NULL detaches.
+ * When c lives on another device, the batch's (contig, position, CIGAR) arrays are downloaded and go through ngm_coverage_add. */
+int ngm_mapper_set_coverage(ngm_mapper *m, ngm_coverage *c);
+
 /* page-locked host memory for read batches (the H2D copy then runs at PCIe rate without a staging copy) */
 void *ngm_host_alloc(size_t bytes);
 void ngm_host_free(void *p);

@@ -6,6 +6,8 @@
 // candidate-order replay live in mapper_search.cpp (mapper_internal.h is what the two share).
 #define NGM_SAM_KERNELS
 #include "mapper_internal.h"
+#define NGM_COV_BATCH_KERNELS
+#include "coverage_device.h"
 #include <rocprim/rocprim.hpp>
 #include "align_device.h"
 #include "gather_device.h"
@@ -1434,6 +1436,24 @@ static int map_impl(ngm_mapper *m, int n, const char *reads, const void *d_reads
 			MAP_HIP_TRY(hipGetLastError());
 		}
 		MAP_HIP_TRY(hipEventRecord(e1, m->st));
+		// --coverage: the records just written as mapped ones add their blocks to the run's counters, from the same arrays, before the batch's
+		// buffers are reused (behind e1: not part of the SAM stage's time)
+		const bool cov_here = m->coverage && units > 0 && ngm::coverage_device(m->coverage) == r->device;
+		if (cov_here) {
+			int32_t *cov_counters = nullptr;
+			const uint64_t *cov_off = nullptr;
+			unsigned long long *cov_n = nullptr;
+			int cov_n_ref = 0;
+			if (int rc = ngm::coverage_target(m->coverage, &cov_counters, &cov_off, &cov_n_ref, &cov_n)) return rc;
+			MAP_HIP_TRY(hipEventRecord(m->cev[2], m->st));
+			hipLaunchKernelGGL(ngm::cov::cov_add_kernel<ngm::cov::CovBatch>, dim3((units + 255) / 256), dim3(256), 0, m->st, ngm::cov::CovBatch{S, units, cov_off}, cov_counters, cov_off, cov_n_ref, cov_n);
+			MAP_HIP_TRY(hipGetLastError());
+			MAP_HIP_TRY(hipEventRecord(m->cev[3], m->st));
+		} else if (m->coverage && units > 0) {
+			if (m->d_cov_mask.reserve((size_t) units)) { ngm::pipeline_set_error("out of device memory (coverage)"); return -12; }
+			hipLaunchKernelGGL(ngm::cov::cov_mask_kernel, dim3((units + 255) / 256), dim3(256), 0, m->st, S, units, m->d_cov_mask.p);
+			MAP_HIP_TRY(hipGetLastError());
+		}
 		unsigned long long ctr[7] = {0, 0, 0, 0, 0, 0, 0};
 		MAP_HIP_TRY(hipMemcpyAsync(ctr, m->d_total.p + 16, 56, hipMemcpyDeviceToHost, m->st));
 		m->sam_text_bytes = total;
@@ -1442,6 +1462,25 @@ static int map_impl(ngm_mapper *m, int n, const char *reads, const void *d_reads
 		stage_sam.done_after(e1);   // the text (~420 bytes per read) travels while the next instance's kernels run
 		MAP_HIP_TRY(hipStreamSynchronize(m->st));
 		sam->text_bytes = (long long) total;
+		if (cov_here) { float t = 0; if (hipEventElapsedTime(&t, m->cev[2], m->cev[3]) == hipSuccess) ngm::coverage_note_add_ms(m->coverage, t); }
+		else if (m->coverage && units > 0) {
+			// the coverage object lives on another device: which reads count and the CIGAR texts come down, the arrays go through ngm_coverage_add
+			const size_t str_bytes = (size_t) str_base + extra.size();
+			m->cov_mask.resize((size_t) units); m->cov_text.resize(str_bytes + 1);
+			MAP_HIP_TRY(hipMemcpy(m->cov_mask.data(), m->d_cov_mask.p, (size_t) units, hipMemcpyDeviceToHost));
+			if (str_bytes) MAP_HIP_TRY(hipMemcpy(m->cov_text.data(), m->d_str.p, str_bytes, hipMemcpyDeviceToHost));
+			m->cov_ref.clear(); m->cov_pos.clear(); m->cov_off.clear();
+			std::vector<char> packed;
+			const int per = paired ? 2 : 1;
+			for (int u = 0; u < units; ++u) for (int k = 0; k < per; ++k) {
+				if (!((m->cov_mask[u] >> k) & 1)) continue;
+				const int i = per * u + k;
+				m->cov_ref.push_back(hits[i].contig); m->cov_pos.push_back((int32_t) hits[i].pos); m->cov_off.push_back((uint32_t) packed.size());
+				packed.insert(packed.end(), m->cov_text.data() + sam_refs[i].cig_off, m->cov_text.data() + sam_refs[i].cig_off + sam_refs[i].cig_len);
+			}
+			m->cov_off.push_back((uint32_t) packed.size());
+			if (int rc = ngm_coverage_add(m->coverage, m->cov_ref.data(), m->cov_pos.data(), m->cov_off.data(), packed.data(), m->cov_ref.size())) return rc;
+		}
 		float bgzf_ms = 0.f;
 		if (bam && total > 0) {
 			// the records stay in HBM: their BGZF blocks are written there too (bgzf_device.h, the compressor's own stream -- beside the next
@@ -1496,6 +1535,7 @@ int ngm_mapper_set_pair_state(ngm_mapper *m, ngm_pair_state *ps) { if (!m) retur
 int ngm_mapper_set_batch_seq(ngm_mapper *m, uint64_t seq) { if (!m) return -22; m->batch_seq = seq; return 0; }
 int ngm_mapper_set_fast_pairing(ngm_mapper *m, int on) { if (!m) return -22; m->fast_pairing = on ? 1 : 0; return 0; }
 int ngm_mapper_set_bam_sorter(ngm_mapper *m, ngm_bam_sort *s) { if (!m) return -22; m->sorter = s; return 0; }
+int ngm_mapper_set_coverage(ngm_mapper *m, ngm_coverage *c) { if (!m) return -22; m->coverage = c; return 0; }
 
 void *ngm_host_alloc(size_t bytes) {
 	void *p = nullptr;

@@ -130,6 +130,12 @@ struct ngm_mapper {
 	ngm_bgzf *bz = nullptr;   // sam_opt.bam: the BGZF compressor of this mapper's BAM records
 	ngm_bam_sort *sorter = nullptr;   // ngm_mapper_set_bam_sorter: the batch's BAM records go there instead of through bz
 	std::vector<char> sorter_host;    // ... by way of the host when the sorter lives on another device
+	ngm_coverage *coverage = nullptr; // ngm_mapper_set_coverage: the batch's mapped primary records are added to its counters (coverage_device.h)
+	ngm::DevBuf<uint8_t> d_cov_mask;  // ... by way of the host when it lives on another device: which reads count, and the arrays for ngm_coverage_add
+	std::vector<uint8_t> cov_mask;
+	std::vector<char> cov_text;
+	std::vector<int32_t> cov_ref, cov_pos;
+	std::vector<uint32_t> cov_off;
 	bool sam_ready = false;
 	std::string sam_rg;
 	ngm::DevBuf<char> d_sam_contig_names, d_sam_rg, d_sam_names, d_sam_text;

@@ -14,7 +14,8 @@
 // GPU -- single-end only, see ngm_mapper_map_argos), bisulfite (--bs-mapping) and SLAM-seq (--slam-seq) mapping, -5/--trim5 and --max-polya
 // (csrc/read_trim.h), and --sort (ours, with --bam: the records of the whole run stay in GPU memory, are sorted there into coordinate order and
 // written as the sorted BAM plus <output>.bai, csrc/bam_sort.cpp; not with --argos, --shard, --shard-output, NGM_HIP_BAM_ZLIB=1, nor a
-// contig above 2^29 bases).  Not supported (rejected loudly): --vcf with --bs-mapping, --max-polya with --argos or --vcf, SAM/BAM *input*, --config.
+// contig above 2^29 bases), and --coverage FILE (ours: the per-base depth of the run's mapped primary records as bedGraph, counted and turned into text on the
+// GPU, csrc/coverage.cpp; not with --argos, --shard, --shard-output, nor FILE = the output).  Not supported (rejected loudly): --vcf with --bs-mapping, --max-polya with --argos or --vcf, SAM/BAM *input*, --config.
 //
 // Pass 2 is a pipeline, not a loop:
 //   splitter (1 thread)   cuts the input into batches: for plain 4-line FASTQ it only counts line ends in the mapped file
@@ -133,6 +134,7 @@ struct Opts {
 	int skip_save = 0, bam = 0, workers = 2, serial_reader = 0, keep_tags = 0;
 	int argos = 0, kmer_min_set = 0;
 	int sort = 0;   // --sort (ours): the BAM coordinate-sorted on the GPU, with its .bai (csrc/bam_sort.cpp)
+	std::string coverage;   // --coverage FILE (ours): the depth of the mapped primary records as bedGraph, made on the GPU (csrc/coverage.cpp)
 	ngm::trim::Options trim;   // -5/--trim5, --max-polya (Options.h:103-104)
 	float argos_min = 0.f;   // --argos-min-score (Default(ARGOS_MINSCORE, 0), Config.cpp:505)
 	int bs_mapping = 0, bs_cutoff = 6, match_tt = -1, match_tc = -1, match_set = 0, mismatch_set = 0, slam_seq = 0;
@@ -155,7 +157,7 @@ Opts parse(int argc, char **argv) {
 	Opts o;
 	for (int i = 1; i < argc; ++i) { if (i > 1) o.cmdline += " "; o.cmdline += argv[i]; }  // Config.cpp:565-574
 	enum { KSKIP = 1000, HARD, SILENT, KMIN, MB, MMP, GRP, GFP, MAXCMRS, NOUNAL, NOPROG, MAXRL, BINSZ, MAXKF, VFAST, FAST, SENS, VSENS, DEVICE,
-		SKIPSAVE, BATCH, VARIANT, SHARD, SHARDOUT, KEEPSHARDS, BAMOUT, WORKERS, SERIAL, AFFINE, GEP, PEDELIM, STRATA, BSMAP, BSCUT, MBTT, MBTC, SLAM, FASTPAIR, BROKENPAIRS, REFSCOREBUF, STATSFD, MAXPOLYA, RG0, RG_LAST = RG0 + 11, ARGOS, ARGOSMIN, VCF, KEEPTAGS, PARSEALL, SORTOUT, UNSUPPORTED };
+		SKIPSAVE, BATCH, VARIANT, SHARD, SHARDOUT, KEEPSHARDS, BAMOUT, WORKERS, SERIAL, AFFINE, GEP, PEDELIM, STRATA, BSMAP, BSCUT, MBTT, MBTC, SLAM, FASTPAIR, BROKENPAIRS, REFSCOREBUF, STATSFD, MAXPOLYA, RG0, RG_LAST = RG0 + 11, ARGOS, ARGOSMIN, VCF, KEEPTAGS, PARSEALL, SORTOUT, COVERAGE, UNSUPPORTED };
 	static const option lo[] = {
 		{"ref", required_argument, 0, 'r'}, {"qry", required_argument, 0, 'q'}, {"output", required_argument, 0, 'o'},
 		{"cpu-threads", required_argument, 0, 't'}, {"gpu", no_argument, 0, 'g'}, {"sensitivity", required_argument, 0, 's'},
@@ -181,7 +183,7 @@ Opts parse(int argc, char **argv) {
 		{"bs-cutoff", required_argument, 0, BSCUT}, {"match-bonus-tt", required_argument, 0, MBTT}, {"match-bonus-tc", required_argument, 0, MBTC},
 		{"slam-seq", required_argument, 0, SLAM}, {"topn", required_argument, 0, 'n'}, {"strata", no_argument, 0, STRATA},
 		{"argos", no_argument, 0, ARGOS}, {"argos-min-score", required_argument, 0, ARGOSMIN}, {"vcf", required_argument, 0, VCF},
-		{"keep-tags", no_argument, 0, KEEPTAGS}, {"parse-all", no_argument, 0, PARSEALL}, {"sort", no_argument, 0, SORTOUT},
+		{"keep-tags", no_argument, 0, KEEPTAGS}, {"parse-all", no_argument, 0, PARSEALL}, {"sort", no_argument, 0, SORTOUT}, {"coverage", required_argument, 0, COVERAGE},
 		{"trim5", required_argument, 0, '5'}, {"max-polya", required_argument, 0, MAXPOLYA}, {"config", required_argument, 0, UNSUPPORTED},
 		{0, 0, 0, 0}};
 	int c, idx = 0;
@@ -268,6 +270,7 @@ Opts parse(int argc, char **argv) {
 		case PARSEALL: break;                    // every record of a SAM / BAM input is a read: the default (Config.cpp:489)
 		case ARGOSMIN: o.argos_min = (float) atof(optarg); break;
 		case SORTOUT: o.sort = 1; break;
+		case COVERAGE: o.coverage = optarg; if (o.coverage.empty()) die("--coverage expects a file name"); break;
 		case UNSUPPORTED: die(std::string("option --") + lo[idx].name + " is not supported by the HIP backend yet");
 		default: die("unknown option (see src/config/Options.h of NextGenMap for the option set)");
 		}
@@ -280,6 +283,13 @@ Opts parse(int argc, char **argv) {
 		if (o.shard_n > 1) die("--sort cannot be combined with --shard: the sort is over the whole run, not over one shard of it");
 		if (o.shard_output) die("--sort cannot be combined with --shard-output: the sort is over the whole run, in one process");
 		if (getenv("NGM_HIP_BAM_ZLIB")) die("--sort cannot be combined with NGM_HIP_BAM_ZLIB=1: the blocks of a sorted file only come from the GPU");
+	}
+	if (!o.coverage.empty()) {
+		// the depth is over the records of the whole run, counted in the first GPU's memory; refused before any GPU work
+		if (o.argos) die("--coverage cannot be combined with --argos: argos scores candidates, no alignments are made");
+		if (o.shard_n > 1) die("--coverage cannot be combined with --shard: the depth is over the whole run, not over one shard of it");
+		if (o.shard_output) die("--coverage cannot be combined with --shard-output: the depth is over the whole run, in one process");
+		if (o.coverage == o.out) die("--coverage cannot write to the -o/--output file: " + o.out);
 	}
 	if (o.argos) {
 		// ScoreWriter has no paired or binary form (DoWritePair throws, src/writer/ScoreWriter.cpp:75-77); refused before any GPU work
@@ -1367,6 +1377,29 @@ int main(int argc, char **argv) {
 		if (!sorter) die(ngm_pipeline_last_error());
 		if (gpu_sam) for (Worker &w : workers) if (ngm_mapper_set_bam_sorter(w.m, sorter) < 0) die(ngm_pipeline_last_error());
 	}
+	// --coverage: one counter per base of the reference on the first device; every mapper adds the mapped primary records of its batches
+	// there (in place on that GPU, through ngm_coverage_add from the others), and so do the host-formatted routes below
+	ngm_coverage *coverage = nullptr;
+	FILE *coverage_file = nullptr;
+	if (!o.coverage.empty()) {
+		coverage_file = fopen(o.coverage.c_str(), "wb");   // (before the run, not after it)
+		if (!coverage_file) die("cannot write " + o.coverage);
+		std::vector<uint32_t> lens32;
+		std::vector<const char *> names;
+		uint64_t bases = 0;
+		for (size_t i = 0; i < contig_lens.size(); ++i) { lens32.push_back((uint32_t) contig_lens[i]); names.push_back(contig_names[i].c_str()); bases += contig_lens[i]; }
+		ngm_coverage_params cp{};
+		cp.device = o.devices[0]; cp.n_ref = (int) lens32.size(); cp.ref_len = lens32.data(); cp.ref_name = names.data();
+		coverage = ngm_coverage_create(&cp);
+		if (!coverage) die(std::string("--coverage: ") + ngm_pipeline_last_error());
+		char cm[200];
+		snprintf(cm, sizeof(cm), "Coverage counters: %.1f MiB on GPU %d (4 bytes per base of the reference, held for the whole run)", (double) (bases + lens32.size()) * 4.0 / (double) (1 << 20), o.devices[0]);
+		info("MAIN", cm);
+		if (gpu_sam) for (Worker &w : workers) if (ngm_mapper_set_coverage(w.m, coverage) < 0) die(ngm_pipeline_last_error());
+	}
+	// (host-formatted routes: the records write_mapped formats without 0x100, per format_range call)
+	struct CovAcc { std::vector<int32_t> ref, pos; std::vector<uint32_t> off; std::string text; };
+	static thread_local CovAcc *tl_cov = nullptr;
 	auto pipeline_error = [&](long long rc, bool from_mapper = false) -> std::string {   // (the sorter never spills: -12 from it, -28 through a mapper, ends the run with what it held)
 		std::string e = ngm_pipeline_last_error();
 		if (sorter && rc == (from_mapper ? -28 : -12)) {
@@ -1439,6 +1472,10 @@ int main(int argc, char **argv) {
 		if (h.reverse) flags |= 0x10;
 		const bool clip = o.hard_clip || o.silent_clip;
 		const int s0 = clip ? h.qstart : 0, sl = clip ? L - h.qstart - h.qend : L;
+		if (tl_cov && !(flags & 0x100)) {   // --coverage
+			tl_cov->ref.push_back(h.contig); tl_cov->pos.push_back((int32_t) h.pos); tl_cov->off.push_back((uint32_t) tl_cov->text.size());
+			tl_cov->text += v.cigar;
+		}
 		if (o.bam) {  // BAMWriter::DoWriteReadGeneric (BAMWriter.cpp:147-298)
 			char seq[1024], qual[1024];
 			const int n = std::max(0, std::min(sl, 1000));
@@ -1542,8 +1579,20 @@ int main(int argc, char **argv) {
 	// others' insert sizes -- summed over the run (the GPU formatter counts the same: ngm_mapper_last_pair_stats)
 	std::atomic<uint64_t> pair_stat[3];
 	for (auto &x : pair_stat) x = 0;
+	std::atomic<bool> cov_failed{false};   // an ngm_coverage_add of a formatted range failed: the run fails behind its batch
 	auto format_range = [&](const Batch &b, const Worker &w, int lo, int hi, std::string &s, size_t &n_total, size_t &n_mapped, size_t &n_written) {
 		struct PairAcc { std::atomic<uint64_t> *t; uint64_t v[3] = {0, 0, 0}; ~PairAcc() { for (int k = 0; k < 3; ++k) if (v[k]) t[k] += v[k]; } } pacc{pair_stat};
+		CovAcc cov_acc;
+		struct CovScope {   // the range's alignments go to the coverage when the range is formatted
+			ngm_coverage *c; CovAcc *a; std::atomic<bool> *bad;
+			~CovScope() {
+				tl_cov = nullptr;
+				if (!c || a->ref.empty()) return;
+				a->off.push_back((uint32_t) a->text.size());
+				if (ngm_coverage_add(c, a->ref.data(), a->pos.data(), a->off.data(), a->text.data(), a->ref.size()) < 0) *bad = true;
+			}
+		} cov_scope{coverage, &cov_acc, &cov_failed};
+		if (coverage) tl_cov = &cov_acc;
 		auto view = [&](int i, int t = 0) {
 			const size_t e = (size_t) i * topn + t;
 			View v{&b.recs[i], &w.hits[e], w.rows + (size_t) i * q, 0, &w.cig[e * stride], &w.md[e * stride]};
@@ -2040,6 +2089,7 @@ int main(int argc, char **argv) {
 				}
 			}, 1, (o.bam && !gpu_bgzf) ? ngm::ThreadPool::cpu_quota() : 0);   // (BAM with zlib: records + deflate keep every thread busy for the whole batch)
 			for (int c = 0; c < n_chunks; ++c) { b->n_total += ct[c]; b->n_mapped += cm[c]; b->n_written += cw[c]; }
+			if (cov_failed) { fail(std::string("--coverage: ") + ngm_pipeline_last_error()); continue; }
 			if (gpu_bgzf) {
 				// the batch's records, chunk after chunk, in page-locked memory -> whole BGZF blocks from the GPU (a batch ends with a short
 				// block: batches -- and shards -- concatenate into one valid file) -> pieces for the writer
@@ -2196,6 +2246,33 @@ int main(int argc, char **argv) {
 			info("MAIN", msg);
 		}
 	}
+	if (coverage && !failed) {
+		// --coverage: every batch has added its records.  The counters become depths and the depths lines chunk by chunk on the GPU; the
+		// lines are streamed into the file
+		const auto t_cov = std::chrono::steady_clock::now();
+		FILE *cf = coverage_file;
+		size_t cap = (size_t) 8 << 20;
+		std::vector<char> buf(cap);
+		if (const int rc = ngm_coverage_finish(coverage); rc < 0) fail(std::string("--coverage: ") + ngm_pipeline_last_error());
+		while (!failed) {
+			const long long got = ngm_coverage_next(coverage, buf.data(), cap);
+			if (got < 0) { fail(std::string("--coverage: ") + ngm_pipeline_last_error()); break; }
+			if (got == 0) break;
+			if ((size_t) got > cap) { cap = (size_t) got; buf.resize(cap); continue; }
+			if (fwrite(buf.data(), 1, (size_t) got, cf) != (size_t) got) { fail("write error on " + o.coverage); break; }
+		}
+		coverage_file = nullptr;
+		if (fclose(cf) != 0) fail("write error on " + o.coverage);
+		if (!failed) {
+			uint64_t cc[4] = {0, 0, 0, 0};
+			float cms[4] = {0, 0, 0, 0};
+			(void) ngm_coverage_stats(coverage, cc, cms);
+			snprintf(msg, sizeof(msg), "Coverage on the GPU: %llu alignments, %llu covered bases, %llu runs, %llu bytes of bedGraph; kernels: add %.2f ms, scan %.2f ms, runs %.2f ms, text %.2f ms; "
+					"%.3f s after the last batch", (unsigned long long) cc[0], (unsigned long long) cc[1], (unsigned long long) cc[2], (unsigned long long) cc[3], cms[0], cms[1], cms[2], cms[3],
+					std::chrono::duration<double>(std::chrono::steady_clock::now() - t_cov).count());
+			info("MAIN", msg);
+		}
+	}
 	if (o.bam && o.shard_i == o.shard_n - 1) { std::string z; ngm::bam::bgzf_eof(z); if (!put_all(z.data(), z.size(), out_off)) fail("write error on " + o.out); out_off += z.size(); }   // (--shard: the end-of-file block travels with the last shard)
 	if (close(out_fd) != 0) fail("write error on " + o.out);
 	if (failed) die(fail_msg);
@@ -2317,6 +2394,8 @@ int main(int argc, char **argv) {
 	for (Worker &w : workers) { ngm_mapper_destroy(w.m); ngm_host_free(w.rows); ngm_host_free(w.qrows); ngm_host_free(w.names); ngm_host_free(w.meta); ngm_host_free(w.polya);
 		ngm_bgzf_destroy(w.bz); ngm_host_free(w.bam_raw); ngm_host_free(w.bam_out); }
 	ngm_bam_sort_destroy(sorter);
+	ngm_coverage_destroy(coverage);
+	if (coverage_file) fclose(coverage_file);
 	for (TextBuf &t : text_free) ngm_host_free(t.p);
 	ngm_pair_state_destroy(pair_state);
 	for (ngm_ref *r2 : refs) ngm_ref_destroy(r2);

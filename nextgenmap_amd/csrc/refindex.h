@@ -123,6 +123,11 @@ void pipeline_set_error(const char *fmt, ...);
 // units + 1 offsets into d_records, the last one n_bytes; both complete), and the device a sorter lives on
 int bam_sort_add_device(struct ::ngm_bam_sort *s, uint64_t seq, const void *d_records, size_t n_bytes, const uint32_t *d_unit_off, size_t units);
 int bam_sort_device(const struct ::ngm_bam_sort *s);
+// coverage.cpp, for the mapper's SAM stage: the device a coverage object lives on, where a cov_add_kernel on that device adds (the counters,
+// the contigs' offsets, the count of alignments; -22 after the finish), and the time such a kernel took
+int coverage_device(const struct ::ngm_coverage *c);
+int coverage_target(struct ::ngm_coverage *c, int32_t **counters, const uint64_t **d_off, int *n_ref, unsigned long long **d_n_aln);
+void coverage_note_add_ms(struct ::ngm_coverage *c, float ms);
 // k-mer integer as the reference builds it: 2 bits per base, A0 C1 T2 G3 ((c >> 1) & 3, CSstatic.cpp:20-22)
 inline uint32_t kmer_code_of_class(uint32_t cls) { return cls == 2 ? 3u : (cls == 3 ? 2u : cls); }
 // reverse complement of a k-mer integer (PrefixTable.cpp:94-108), valid for 2k <= 32

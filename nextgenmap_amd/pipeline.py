@@ -38,6 +38,10 @@ class BamSortParams(C.Structure):   # ngm_bam_sort_params
     _fields_ = [("device", C.c_int), ("chunk_bytes", C.c_size_t), ("max_bytes", C.c_size_t)]
 
 
+class CoverageParams(C.Structure):   # ngm_coverage_params
+    _fields_ = [("device", C.c_int), ("n_ref", C.c_int), ("ref_len", C.POINTER(C.c_uint32)), ("ref_name", C.POINTER(C.c_char_p)), ("scan_chunk", C.c_size_t)]
+
+
 def _lib():
     global _bound
     lib = load_library()
@@ -123,6 +127,15 @@ def _lib():
         lib.ngm_bam_sort_index.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t]
         lib.ngm_bam_sort_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.ngm_mapper_set_bam_sorter.argtypes = [C.c_void_p, C.c_void_p]
+        lib.ngm_coverage_create.restype = C.c_void_p
+        lib.ngm_coverage_create.argtypes = [C.POINTER(CoverageParams)]
+        lib.ngm_coverage_destroy.argtypes = [C.c_void_p]
+        lib.ngm_coverage_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
+        lib.ngm_coverage_finish.argtypes = [C.c_void_p]
+        lib.ngm_coverage_next.restype = C.c_longlong
+        lib.ngm_coverage_next.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.ngm_coverage_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.ngm_mapper_set_coverage.argtypes = [C.c_void_p, C.c_void_p]
         _bound = True
     return lib
 
@@ -238,6 +251,83 @@ class BamSorter:
     def close(self):
         if self._h:
             _lib().ngm_bam_sort_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Coverage:
+    """The per-base read depth of a run, counted in GPU memory and handed back as bedGraph text (include/ngm_pipeline.h, ngm_coverage_*):
+    what `ngm-hip --coverage` writes.  contigs: [(name, length)]."""
+
+    def __init__(self, contigs, device=0, scan_chunk=0):
+        n = len(contigs)
+        self._len = (C.c_uint32 * max(1, n))(*[int(l) for _, l in contigs])
+        self._name = (C.c_char_p * max(1, n))(*[nm.encode() if isinstance(nm, str) else bytes(nm) for nm, _ in contigs])
+        p = CoverageParams(device, n, self._len, self._name, scan_chunk)
+        self._h = _lib().ngm_coverage_create(C.byref(p))
+        if not self._h:
+            raise _err()
+
+    def add(self, alignments):
+        """[(contig index, 0-based position, CIGAR text)]; raises on the first alignment the validator refuses, adding nothing"""
+        alignments = list(alignments)
+        cig = [c.encode() if isinstance(c, str) else bytes(c) for _, _, c in alignments]
+        off = np.zeros(len(cig) + 1, dtype=np.uint32)
+        off[1:] = np.cumsum([len(c) for c in cig], dtype=np.uint64)
+        self.add_arrays(np.array([a[0] for a in alignments], dtype=np.int32), np.array([a[1] for a in alignments], dtype=np.int32), off, b"".join(cig))
+
+    def add_arrays(self, ref_id, pos0, cigar_off, cigar_text):
+        ref_id = np.ascontiguousarray(ref_id, dtype=np.int32)
+        pos0 = np.ascontiguousarray(pos0, dtype=np.int32)
+        cigar_off = np.ascontiguousarray(cigar_off, dtype=np.uint32)
+        if len(pos0) != len(ref_id) or len(cigar_off) != len(ref_id) + 1:
+            raise ValueError("ref_id, pos0 of n entries and cigar_off of n + 1")
+        if _lib().ngm_coverage_add(self._h, ref_id.ctypes.data, pos0.ctypes.data, cigar_off.ctypes.data, bytes(cigar_text), len(ref_id)) < 0:
+            raise _err()
+
+    def finish(self):
+        if _lib().ngm_coverage_finish(self._h) < 0:
+            raise _err()
+
+    def next(self, cap, out=None):
+        """one ngm_coverage_next call with a buffer of cap bytes: (return value, the bytes copied)"""
+        if out is None:
+            out = C.create_string_buffer(max(1, cap))
+        n = _lib().ngm_coverage_next(self._h, out, cap)
+        if n < 0:
+            raise _err()
+        return n, (C.string_at(out, n) if n <= cap else b"")
+
+    def pieces(self, cap=1 << 20):
+        """the file, in pieces of whole lines"""
+        out = C.create_string_buffer(cap)
+        while True:
+            n, data = self.next(cap, out)
+            if n == 0:
+                return
+            if n > cap:
+                cap = n
+                out = C.create_string_buffer(cap)
+                continue
+            yield data
+
+    def stats(self):
+        counts = (C.c_uint64 * 4)()
+        ms = (C.c_float * 4)()
+        if _lib().ngm_coverage_stats(self._h, counts, ms) < 0:
+            raise _err()
+        d = dict(zip(("alignments", "covered_bases", "runs", "text_bytes"), (int(x) for x in counts)))
+        d.update(zip(("add_ms", "scan_ms", "runs_ms", "text_ms"), (float(x) for x in ms)))
+        return d
+
+    def close(self):
+        if self._h:
+            _lib().ngm_coverage_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -453,6 +543,11 @@ class Mapper:
         rows = np.ascontiguousarray(rows, dtype=np.uint8)
         hits, cig, md = self.map_se_raw(rows)
         return hits, [bytes(r).split(b"\0", 1)[0] for r in cig], [bytes(r).split(b"\0", 1)[0] for r in md]
+
+    def set_coverage(self, coverage):
+        """every batch map_sam finishes adds its mapped primary records to `coverage` (a Coverage, or None to detach)"""
+        if self.lib.ngm_mapper_set_coverage(self.h, coverage._h if coverage is not None else None) < 0:
+            raise _err()
 
     def set_bam_sorter(self, sorter):
         """map_sam(bam=True) hands its records to `sorter` (a BamSorter, or None to detach) instead of returning BGZF members"""
