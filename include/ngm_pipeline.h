@@ -403,6 +403,18 @@ int ngm_debug_align_finish(void *engine /* ngm_hip_ctx * */, int mode, int n, co
  * ones no read owns are left as 0xFFFFFFFF. */
 int ngm_debug_expand_pairs(int device, int n_reads, const uint32_t *base, const uint32_t *count, uint64_t n_cand, uint32_t *out);
 
+/* test hook: the paired-end selection of the score stage (pair_simple_kernel, csrc/gather_device.h, and the three instances of
+ * pair_choice_kernel, csrc/pair_device.h: ScoreBuffer::top1PE + CheckPairs, src/ScoreBuffer.cpp:368-502, as far as the scores alone decide)
+ * over host arrays, through the very launch sequence the mapper runs and always with the pairs with choices on the GPU.  Reads 2p and
+ * 2p + 1 are pair p (the odd read is mate `a`); read i owns candidates [base[i], base[i] + count[i]); max_insert <= 0: no upper bound.
+ * Out, as the mapper downloads them: info[n_pairs] (>= 0: settled, bit 0 = taken, bits 1.. = insert size; -1: the host's; <= -2: entry
+ * -2 - info, from 2^30 on in the second half of `entries`), mapq / n_best [2 n_pairs] (in/out: written for taken one-candidate pairs only),
+ * counts = {tied, small, large, large beyond 2 048 candidates above the cut-off}, entries (ngm::PairOut[2 n_pairs + 2]: eight int32
+ * {flags, wa, wb, dist, dmin, dmax, tied_ix, pair}) and tops (ngm::PairTop[n_pairs + 1]: int32 d[8], a[8], b[8]); what no kernel wrote
+ * reads as -1.  tests/test_gpu_pair_choice.py compares it with tests/pair_choice_model.py. */
+int ngm_debug_pair_select(int device, int n_pairs, const uint32_t *base, const uint32_t *count, uint64_t n_cand, const float *scores, const uint32_t *loc,
+		const uint16_t *read_len, int min_insert, int max_insert, float cutoff, int32_t *info, int32_t *mapq, int32_t *n_best, uint32_t counts[4], void *entries, void *tops);
+
 /* of path counter [7] (reads searched by the heavy-read kernel, csrc/cs_heavy_device.h), summed over all batches: [0] reads given a second
  * pass (T from the first pass's maximum), [1] table passes started over with twice the parts, [2] reads a class could not certify and
  * queued again, [3] times the pool of global-memory vote tables had to grow (one more synchronisation in that batch) */

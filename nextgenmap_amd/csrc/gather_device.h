@@ -240,7 +240,8 @@ __global__ __launch_bounds__(256) void select_top1_kernel(int n_reads, const uin
 // its score is positive (MAPQ 60 for both mates, no equally good pair), otherwise the single-end selection of
 // select_top1_kernel stands and the pair is flagged as failed.
 // info[pair] >= 0: bit 0 = pair taken, bits 1.. = its insert size (the host only sums those for the running mean, ScoreBuffer.h:90);
-// -1: a mate without candidates (top1SE for the other one: the host's); <= -2: a pair with choices -- entry -2 - info[pair] of
+// -1: a mate without candidates (top1SE for the other one: the host's), or a taken pair whose insert size needs more than the 30 bits
+// there are (no upper window bound, mates 2^30 or more apart: the host's select_pair settles it); <= -2: a pair with choices -- entry -2 - info[pair] of
 // pair_choice_kernel's output (pair_device.h): the pair is appended to the list of the small pairs (both mates at most 64
 // candidates: one wave each there) or, beyond 2^30, to the list of the large ones.
 __global__ void pair_simple_kernel(int n_pairs, const uint32_t *__restrict__ cand_base, const uint32_t *__restrict__ cand_count,
@@ -275,6 +276,7 @@ __global__ void pair_simple_kernel(int n_pairs, const uint32_t *__restrict__ can
 	const int cur = (int) ((l2 > l1) ? l2 - l1 + (uint64_t) read_len[rb] : l1 - l2 + (uint64_t) read_len[ra]);
 	const float ps = scores[ba] + scores[bb];
 	const bool found = cur > min_d && cur < max_d && ps > 0.0f;
+	if (found && cur >= (1 << 30)) { info[pi] = -1; return; }   // (cur << 1) | 1 would be negative: read as an entry of pair_choice_kernel
 	if (found) { mapq[ra] = 60; mapq[rb] = 60; n_best[ra] = 0; n_best[rb] = 0; }
 	info[pi] = found ? ((cur << 1) | 1) : 0;
 }

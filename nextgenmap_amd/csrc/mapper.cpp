@@ -602,6 +602,40 @@ static void select_pair(ngm_mapper *m, const long dist_sum, const long dist_coun
 	}
 }
 
+// The pair selection's launches on `st`, shared by map_impl and the test hook ngm_debug_pair_select: pair_simple_kernel settles the pairs whose
+// mates have one candidate each and -- with `choice_on_gpu` -- sorts the others into two lists, which the three instances of pair_choice_kernel
+// (pair_device.h) then work through.  tied_n[4]: [0] tied pairs, [1] small pairs, [2] large pairs, [3] large pairs beyond kPairCap; list:
+// 3 npairs + 2 words (small, large, huge); out: 2 npairs + 2 entries (small pairs from 0, large ones from npairs); tops: npairs + 1.
+// The four of them may be null without choice_on_gpu.
+static int launch_pair_select(hipStream_t st, size_t npairs, const uint32_t *cand_base, const uint32_t *cand_count, const float *scores, const uint32_t *loc,
+		const uint16_t *read_len, int min_insert, int max_insert, float pair_score_cutoff, int32_t *mapq, int32_t *n_best, int32_t *info, bool choice_on_gpu,
+		uint32_t *tied_n, uint32_t *list, ngm::PairOut *out, ngm::PairTop *tops) {
+	const int min_d = min_insert, max_d = max_insert > 0 ? max_insert : INT_MAX;
+	if (choice_on_gpu) MAP_HIP_TRY(hipMemsetAsync(tied_n, 0, 16, st));
+	uint32_t *counts = choice_on_gpu ? tied_n + 1 : nullptr;
+	hipLaunchKernelGGL(ngm::pair_simple_kernel, dim3((unsigned) ((npairs + 255) / 256)), dim3(256), 0, st, (int) npairs, cand_base, cand_count, scores, loc, read_len, min_d, max_d, mapq, n_best, info,
+			list, list ? list + npairs : nullptr, counts);
+	MAP_HIP_TRY(hipGetLastError());
+	if (!choice_on_gpu) return 0;
+	// persistent workgroups over the two lists (their lengths stay on the device); entries of the small pairs at out[0 ..), of the large
+	// ones at out[npairs ..) (2^30 + ... in the numbering pair_simple_kernel puts into `info`)
+	const float cutoff = pair_score_cutoff > 0 ? pair_score_cutoff : 0.9f;
+	uint32_t *const huge_list = list + 2 * npairs, *const huge_count = tied_n + 3;   // entries of the large pairs with more than kPairCap candidates above the cut-off
+	hipLaunchKernelGGL((ngm::pair_choice_kernel<64, 64>), dim3((unsigned) std::min<size_t>(npairs, 8192)), dim3(64), ngm::pair_choice_lds_bytes(64), st, (const uint32_t *) list, (const uint32_t *) counts,
+			cand_base, cand_count, scores, loc, read_len, min_d, max_d, cutoff, out, tops, tied_n, (uint32_t) npairs, (uint32_t *) nullptr, (uint32_t *) nullptr, (const uint32_t *) nullptr);
+	hipLaunchKernelGGL((ngm::pair_choice_kernel<ngm::kPairThreads, ngm::kPairCap>), dim3((unsigned) std::min<size_t>(npairs, 1024)), dim3(ngm::kPairThreads), ngm::pair_choice_lds_bytes(ngm::kPairCap), st,
+			(const uint32_t *) (list + npairs), (const uint32_t *) (counts + 1), cand_base, cand_count, scores, loc, read_len, min_d, max_d, cutoff,
+			out + npairs, tops, tied_n, (uint32_t) npairs, huge_list, huge_count, (const uint32_t *) nullptr);
+	// ... and what outgrew those lists once more with kPairCapHuge of them (96 KB of LDS: one workgroup per CU; a few hundred pairs of repeat families per batch)
+	static const bool huge_attr = [] { (void) hipFuncSetAttribute((const void *) ngm::pair_choice_kernel<1024, ngm::kPairCapHuge>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ngm::pair_choice_lds_bytes(ngm::kPairCapHuge)); return true; }();
+	(void) huge_attr;
+	hipLaunchKernelGGL((ngm::pair_choice_kernel<1024, ngm::kPairCapHuge>), dim3((unsigned) std::min<size_t>(npairs, 256)), dim3(1024), ngm::pair_choice_lds_bytes(ngm::kPairCapHuge), st,   // (one workgroup per CU either way: sixteen waves share a pair)
+			(const uint32_t *) huge_list, (const uint32_t *) huge_count, cand_base, cand_count, scores, loc, read_len, min_d, max_d, cutoff,
+			out + npairs, tops, tied_n, (uint32_t) npairs, (uint32_t *) nullptr, (uint32_t *) nullptr, (const uint32_t *) (list + npairs));
+	MAP_HIP_TRY(hipGetLastError());
+	return 0;
+}
+
 static int map_impl(ngm_mapper *m, int n, const char *reads, const void *d_reads_ext, ngm_hit *hits, char *cigars, char *mds, bool paired, SamCall *sam) {
 	if (!m) return -22;
 	// shared paired-end state: wait for this batch's turn before the running mean is read, pass it on when the batch is
@@ -744,32 +778,10 @@ static int map_impl(ngm_mapper *m, int n, const char *reads, const void *d_reads
 			if (choice_on_gpu) {
 				if (m->d_pair_out.reserve(2 * npairs + 2) || m->d_pair_top.reserve(npairs + 1) || m->d_pair_tied_n.reserve(4) || m->p_pair_tied_n.reserve(4) || m->d_pair_list.reserve(3 * npairs + 2)) {
 					ngm::pipeline_set_error("out of memory (pair selection)"); return -12; }
-				MAP_HIP_TRY(hipMemsetAsync(m->d_pair_tied_n.p, 0, 16, m->st));   // [0] tied pairs, [1] small pairs, [2] large pairs
 			}
-			uint32_t *counts = choice_on_gpu ? m->d_pair_tied_n.p + 1 : nullptr;
-			hipLaunchKernelGGL(ngm::pair_simple_kernel, dim3((n / 2 + 255) / 256), dim3(256), 0, m->st, n / 2, m->d_cand_base.p, m->d_cand_count.p, m->d_scores.p,
-					m->d_out_loc.p, m->d_read_len.p, m->prm.min_insert_size, m->prm.max_insert_size > 0 ? m->prm.max_insert_size : INT_MAX, m->d_mapq.p, m->d_nbest.p, m->d_pair_info.p,
-					m->d_pair_list.p, m->d_pair_list.p + npairs, counts);
-			MAP_HIP_TRY(hipGetLastError());
+			if (int rc = launch_pair_select(m->st, npairs, m->d_cand_base.p, m->d_cand_count.p, m->d_scores.p, m->d_out_loc.p, m->d_read_len.p, m->prm.min_insert_size, m->prm.max_insert_size,
+					m->prm.pair_score_cutoff, m->d_mapq.p, m->d_nbest.p, m->d_pair_info.p, choice_on_gpu, m->d_pair_tied_n.p, m->d_pair_list.p, m->d_pair_out.p, m->d_pair_top.p)) return rc;
 			if (choice_on_gpu) {
-				// persistent workgroups over the two lists (their lengths stay on the device); entries of the small pairs at out[0 ..), of the large
-				// ones at out[npairs ..) (2^30 + ... in the numbering pair_simple_kernel puts into d_pair_info)
-				const int min_d = m->prm.min_insert_size, max_d = m->prm.max_insert_size > 0 ? m->prm.max_insert_size : INT_MAX;
-				const float cutoff = m->prm.pair_score_cutoff > 0 ? m->prm.pair_score_cutoff : 0.9f;
-				uint32_t *const huge_list = m->d_pair_list.p + 2 * npairs, *const huge_count = m->d_pair_tied_n.p + 3;   // entries of the large pairs with more than kPairCap candidates above the cut-off
-				hipLaunchKernelGGL((ngm::pair_choice_kernel<64, 64>), dim3((unsigned) std::min<size_t>(npairs, 8192)), dim3(64), ngm::pair_choice_lds_bytes(64), m->st, (const uint32_t *) m->d_pair_list.p, (const uint32_t *) counts,
-						m->d_cand_base.p, m->d_cand_count.p, m->d_scores.p, m->d_out_loc.p, m->d_read_len.p, min_d, max_d, cutoff, m->d_pair_out.p, m->d_pair_top.p, m->d_pair_tied_n.p, (uint32_t) npairs,
-						(uint32_t *) nullptr, (uint32_t *) nullptr, (const uint32_t *) nullptr);
-				hipLaunchKernelGGL((ngm::pair_choice_kernel<ngm::kPairThreads, ngm::kPairCap>), dim3((unsigned) std::min<size_t>(npairs, 1024)), dim3(ngm::kPairThreads), ngm::pair_choice_lds_bytes(ngm::kPairCap), m->st,
-						(const uint32_t *) (m->d_pair_list.p + npairs), (const uint32_t *) (counts + 1), m->d_cand_base.p, m->d_cand_count.p, m->d_scores.p, m->d_out_loc.p, m->d_read_len.p, min_d, max_d, cutoff,
-						m->d_pair_out.p + npairs, m->d_pair_top.p, m->d_pair_tied_n.p, (uint32_t) npairs, huge_list, huge_count, (const uint32_t *) nullptr);
-				// ... and what outgrew those lists once more with kPairCapHuge of them (96 KB of LDS: one workgroup per CU; a few hundred pairs of repeat families per batch)
-				static const bool huge_attr = [] { (void) hipFuncSetAttribute((const void *) ngm::pair_choice_kernel<1024, ngm::kPairCapHuge>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ngm::pair_choice_lds_bytes(ngm::kPairCapHuge)); return true; }();
-				(void) huge_attr;
-				hipLaunchKernelGGL((ngm::pair_choice_kernel<1024, ngm::kPairCapHuge>), dim3((unsigned) std::min<size_t>(npairs, 256)), dim3(1024), ngm::pair_choice_lds_bytes(ngm::kPairCapHuge), m->st,   // (one workgroup per CU either way: sixteen waves share a pair)
-						(const uint32_t *) huge_list, (const uint32_t *) huge_count, m->d_cand_base.p, m->d_cand_count.p, m->d_scores.p, m->d_out_loc.p, m->d_read_len.p, min_d, max_d, cutoff,
-						m->d_pair_out.p + npairs, m->d_pair_top.p, m->d_pair_tied_n.p, (uint32_t) npairs, (uint32_t *) nullptr, (uint32_t *) nullptr, (const uint32_t *) (m->d_pair_list.p + npairs));
-				MAP_HIP_TRY(hipGetLastError());
 				MAP_HIP_TRY(hipMemcpyAsync(m->p_pair_tied_n.p, m->d_pair_tied_n.p, 16, hipMemcpyDeviceToHost, m->st));
 			}
 			MAP_HIP_TRY(hipMemcpyAsync(m->p_pair_info.p, m->d_pair_info.p, (size_t) (n / 2) * 4, hipMemcpyDeviceToHost, m->st));
@@ -1695,6 +1707,53 @@ int ngm_debug_expand_pairs(int device, int n_reads, const uint32_t *base, const 
 	};
 	const int rc = run();
 	d_base.release(); d_count.release(); d_out.release();
+	return rc;
+}
+
+int ngm_debug_pair_select(int device, int n_pairs, const uint32_t *base, const uint32_t *count, uint64_t n_cand, const float *scores, const uint32_t *loc,
+		const uint16_t *read_len, int min_insert, int max_insert, float cutoff, int32_t *info, int32_t *mapq, int32_t *n_best, uint32_t counts[4], void *entries, void *tops) {
+	if (n_pairs <= 0 || !base || !count || !read_len || !info || !mapq || !n_best || !counts || !entries || !tops || (n_cand && (!scores || !loc))) return -22;
+	const size_t npairs = (size_t) n_pairs, n = 2 * npairs, nc = (size_t) std::max<uint64_t>(n_cand, 1);
+	for (size_t i = 0; i < n; ++i) if ((uint64_t) base[i] + count[i] > n_cand) { ngm::pipeline_set_error("ngm_debug_pair_select: read %zu owns candidates beyond n_cand", i); return -22; }
+	DevGuard g(device);
+	ngm::DevBuf<uint32_t> d_base, d_count, d_loc, d_tied_n, d_list;
+	ngm::DevBuf<uint16_t> d_len;
+	ngm::DevBuf<float> d_sc;
+	ngm::DevBuf<int32_t> d_mq, d_nb, d_info;
+	ngm::DevBuf<ngm::PairOut> d_out;
+	ngm::DevBuf<ngm::PairTop> d_top;
+	auto run = [&]() -> int {
+		if (d_base.reserve(n) || d_count.reserve(n) || d_len.reserve(n) || d_loc.reserve(nc) || d_sc.reserve(nc) || d_mq.reserve(n) || d_nb.reserve(n) || d_info.reserve(npairs + 1) ||
+				d_tied_n.reserve(4) || d_list.reserve(3 * npairs + 2) || d_out.reserve(2 * npairs + 2) || d_top.reserve(npairs + 1)) {
+			ngm::pipeline_set_error("out of device memory (ngm_debug_pair_select)"); return -12; }
+		MAP_HIP_TRY(hipMemcpy(d_base.p, base, n * 4, hipMemcpyHostToDevice));
+		MAP_HIP_TRY(hipMemcpy(d_count.p, count, n * 4, hipMemcpyHostToDevice));
+		MAP_HIP_TRY(hipMemcpy(d_len.p, read_len, n * 2, hipMemcpyHostToDevice));
+		MAP_HIP_TRY(hipMemcpy(d_mq.p, mapq, n * 4, hipMemcpyHostToDevice));
+		MAP_HIP_TRY(hipMemcpy(d_nb.p, n_best, n * 4, hipMemcpyHostToDevice));
+		if (n_cand) {
+			MAP_HIP_TRY(hipMemcpy(d_sc.p, scores, (size_t) n_cand * 4, hipMemcpyHostToDevice));
+			MAP_HIP_TRY(hipMemcpy(d_loc.p, loc, (size_t) n_cand * 4, hipMemcpyHostToDevice));
+		}
+		// (what no kernel writes reads as -1 everywhere: an entry's `pair` field tells whether it was written)
+		MAP_HIP_TRY(hipMemset(d_info.p, 0xFF, (npairs + 1) * 4));
+		MAP_HIP_TRY(hipMemset(d_out.p, 0xFF, (2 * npairs + 2) * sizeof(ngm::PairOut)));
+		MAP_HIP_TRY(hipMemset(d_top.p, 0xFF, (npairs + 1) * sizeof(ngm::PairTop)));
+		MAP_HIP_TRY(hipDeviceSynchronize());
+		if (int rc = launch_pair_select(0, npairs, d_base.p, d_count.p, d_sc.p, d_loc.p, d_len.p, min_insert, max_insert, cutoff, d_mq.p, d_nb.p, d_info.p, true,
+				d_tied_n.p, d_list.p, d_out.p, d_top.p)) return rc;
+		MAP_HIP_TRY(hipDeviceSynchronize());
+		MAP_HIP_TRY(hipMemcpy(info, d_info.p, npairs * 4, hipMemcpyDeviceToHost));
+		MAP_HIP_TRY(hipMemcpy(mapq, d_mq.p, n * 4, hipMemcpyDeviceToHost));
+		MAP_HIP_TRY(hipMemcpy(n_best, d_nb.p, n * 4, hipMemcpyDeviceToHost));
+		MAP_HIP_TRY(hipMemcpy(counts, d_tied_n.p, 16, hipMemcpyDeviceToHost));
+		MAP_HIP_TRY(hipMemcpy(entries, d_out.p, (2 * npairs + 2) * sizeof(ngm::PairOut), hipMemcpyDeviceToHost));
+		MAP_HIP_TRY(hipMemcpy(tops, d_top.p, (npairs + 1) * sizeof(ngm::PairTop), hipMemcpyDeviceToHost));
+		return 0;
+	};
+	const int rc = run();
+	d_base.release(); d_count.release(); d_loc.release(); d_tied_n.release(); d_list.release(); d_len.release(); d_sc.release(); d_mq.release(); d_nb.release(); d_info.release();
+	d_out.release(); d_top.release();
 	return rc;
 }
 
