@@ -335,6 +335,58 @@ int ngm_coverage_stats(const ngm_coverage *c, uint64_t counts[4], float ms[4]);
  * When c lives on another device, the batch's (contig, position, CIGAR) arrays are downloaded and go through ngm_coverage_add. */
 int ngm_mapper_set_coverage(ngm_mapper *m, ngm_coverage *c);
 
+/* ---- `ngm-hip --snp` (csrc/snp.cpp): the per-base mismatch pileup of a run and its single-base substitution calls as VCF text
+ * ("--snp", holds the definition).  Coverage's difference array (int32) and three uint32 counters per base -- a read base b
+ * over a reference base r != b counts in slot (b - r - 1) & 3 -- live in the device's memory for the whole run: 16 bytes per base, about
+ * 50 GB for a genome of GRCh38's size.  Depth is ngm_coverage's depth.  An M, = or X column inside the contig votes for its read base when
+ * the reference base (case folded) and the read base are one of ACGT and differ, and the record has no quality text or the column's Phred
+ * quality is at least min_qual.  A base is a call when depth >= max(1, min_cov) and (double) n >= min_frac * (double) depth for the
+ * alternative with the largest count n > 0 (ties: the first of A, C, G, T).  The file: a header (fileformat, source with the three
+ * thresholds, one ##contig per contig, the INFO lines of DP and AO, the column line), then one line per call, contigs in the order given,
+ * positions ascending: name \t pos (1-based) \t . \t REF \t ALT \t . \t PASS \t DP=depth;AO=n.  The sums are integers: the text depends on
+ * the set of alignments and the thresholds only.  Errors: < 0 with ngm_pipeline_last_error(); the object stays destroyable after every error. */
+typedef struct ngm_snp ngm_snp;
+typedef struct ngm_snp_params {
+	int device;
+	int n_ref;
+	const uint32_t *ref_len;
+	const char *const *ref_name;
+	const char *const *ref_seq;  /* one ASCII string of ref_len[c] letters per contig (ngm_snp_create only) */
+	uint32_t min_cov;            /* N */
+	double min_frac;             /* F, in (0, 1] */
+	int min_qual;                /* Q, 0..93 */
+	const char *min_frac_text;   /* F as the header prints it (the option's text); NULL: printf("%g") of min_frac */
+	size_t scan_chunk;           /* slots scanned at a time by the finish (its temporaries are 5 bytes per slot of a chunk plus the chunk's
+	                                lines); 0: 2^25; at most 2^30 */
+} ngm_snp_params;
+/* allocates and zeroes (bases + n_ref) * 16 bytes on the device and uploads the reference packed to 4 bits per base; NULL with the error
+ * set when that fails */
+ngm_snp *ngm_snp_create(const ngm_snp_params *p);
+/* the same over the contigs of r, on r's device, reading r's resident packed genome instead of a copy (n_ref, ref_len, ref_name, ref_seq
+ * and device of p are not read); r must outlive the object */
+ngm_snp *ngm_snp_create_for_ref(const ngm_ref *r, const ngm_snp_params *p);
+void ngm_snp_destroy(ngm_snp *s);
+/* n alignments: contig, 0-based position, CIGAR text cigar_text[cigar_off[i] .. cigar_off[i + 1]), the sequence as the SAM record prints it
+ * seq_text[seq_off[i] .. seq_off[i + 1]), and qual_text: NULL (no record has qualities), or a C string of Phred+33 characters under the
+ * sequence's offsets.  Thread-safe.  Validated on the host first: -22 with "ngm_snp_add: alignment <i>: ..." names the first one that
+ * ngm_coverage_add would refuse, whose sequence is shorter or longer than the read bases its CIGAR consumes (M, =, X, I, S), or whose
+ * range the quality text does not reach (a quality text that goes on past the last alignment names that one) -- and adds nothing of the
+ * call.  -22 after ngm_snp_finish. */
+int ngm_snp_add(ngm_snp *s, const int32_t *ref_id, const int32_t *pos0, const uint32_t *cigar_off /* [n + 1] */, const char *cigar_text,
+                const uint32_t *seq_off /* [n + 1] */, const char *seq_text, const char *qual_text, size_t n);
+/* no add after this; waits for the adds in flight and sets the scan up */
+int ngm_snp_finish(ngm_snp *s);
+/* the next lines of the file, made chunk by chunk as they are asked for; the header is the first piece: whole lines only; 0 at the end;
+ * > out_cap: nothing copied, call again with that much */
+long long ngm_snp_next(ngm_snp *s, void *out, size_t out_cap);
+/* counts: alignments added, mismatching bases counted, and of the text handed out so far calls, text bytes (header included), covered bases
+ * (the sum of the depths); ms: kernel ms of add / scan / call flags / text (HIP events) */
+int ngm_snp_stats(const ngm_snp *s, uint64_t counts[5], float ms[4]);
+/* every batch ngm_mapper_map_sam* finishes adds the records ngm_mapper_set_coverage would add to s, in place from the batch's arrays in
+ * device memory, on the mapper's stream; NULL detaches.  When s lives on another device, the batch's arrays are downloaded and go through
+ * ngm_snp_add. */
+int ngm_mapper_set_snp(ngm_mapper *m, ngm_snp *s);
+
 /* page-locked host memory for read batches (the H2D copy then runs at PCIe rate without a staging copy) */
 void *ngm_host_alloc(size_t bytes);
 void ngm_host_free(void *p);

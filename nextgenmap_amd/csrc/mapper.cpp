@@ -8,6 +8,7 @@
 #include "mapper_internal.h"
 #define NGM_COV_BATCH_KERNELS
 #include "coverage_device.h"
+#include "snp_device.h"
 #include <rocprim/rocprim.hpp>
 #include "align_device.h"
 #include "gather_device.h"
@@ -1461,7 +1462,19 @@ static int map_impl(ngm_mapper *m, int n, const char *reads, const void *d_reads
 			hipLaunchKernelGGL(ngm::cov::cov_add_kernel<ngm::cov::CovBatch>, dim3((units + 255) / 256), dim3(256), 0, m->st, ngm::cov::CovBatch{S, units, cov_off}, cov_counters, cov_off, cov_n_ref, cov_n);
 			MAP_HIP_TRY(hipGetLastError());
 			MAP_HIP_TRY(hipEventRecord(m->cev[3], m->st));
-		} else if (m->coverage && units > 0) {
+		}
+		// --snp: the same records add their depth blocks and their mismatching, qualifying columns to the run's SNP counters (snp_device.h)
+		const bool snp_here = m->snp && units > 0 && ngm::snp_device(m->snp) == r->device;
+		if (snp_here) {
+			ngm::snp::Target snp_to{};
+			if (int rc = ngm::snp_target(m->snp, &snp_to)) return rc;
+			MAP_HIP_TRY(hipEventRecord(m->cev[4], m->st));
+			hipLaunchKernelGGL(ngm::snp::snp_add_kernel<ngm::snp::SnpBatch>, dim3((units + 255) / 256), dim3(256), 0, m->st, ngm::snp::SnpBatch{S, units}, snp_to);
+			MAP_HIP_TRY(hipGetLastError());
+			MAP_HIP_TRY(hipEventRecord(m->cev[5], m->st));
+		}
+		const bool cov_away = m->coverage && units > 0 && !cov_here, snp_away = m->snp && units > 0 && !snp_here;
+		if (cov_away || snp_away) {
 			if (m->d_cov_mask.reserve((size_t) units)) { ngm::pipeline_set_error("out of device memory (coverage)"); return -12; }
 			hipLaunchKernelGGL(ngm::cov::cov_mask_kernel, dim3((units + 255) / 256), dim3(256), 0, m->st, S, units, m->d_cov_mask.p);
 			MAP_HIP_TRY(hipGetLastError());
@@ -1475,12 +1488,16 @@ static int map_impl(ngm_mapper *m, int n, const char *reads, const void *d_reads
 		MAP_HIP_TRY(hipStreamSynchronize(m->st));
 		sam->text_bytes = (long long) total;
 		if (cov_here) { float t = 0; if (hipEventElapsedTime(&t, m->cev[2], m->cev[3]) == hipSuccess) ngm::coverage_note_add_ms(m->coverage, t); }
-		else if (m->coverage && units > 0) {
-			// the coverage object lives on another device: which reads count and the CIGAR texts come down, the arrays go through ngm_coverage_add
+		if (snp_here) { float t = 0; if (hipEventElapsedTime(&t, m->cev[4], m->cev[5]) == hipSuccess) ngm::snp_note_add_ms(m->snp, t); }
+		if (cov_away || snp_away) {
+			// the object lives on another device: which reads count and the CIGAR texts come down
 			const size_t str_bytes = (size_t) str_base + extra.size();
 			m->cov_mask.resize((size_t) units); m->cov_text.resize(str_bytes + 1);
 			MAP_HIP_TRY(hipMemcpy(m->cov_mask.data(), m->d_cov_mask.p, (size_t) units, hipMemcpyDeviceToHost));
 			if (str_bytes) MAP_HIP_TRY(hipMemcpy(m->cov_text.data(), m->d_str.p, str_bytes, hipMemcpyDeviceToHost));
+		}
+		if (cov_away) {
+			// ... and the arrays go through ngm_coverage_add
 			m->cov_ref.clear(); m->cov_pos.clear(); m->cov_off.clear();
 			std::vector<char> packed;
 			const int per = paired ? 2 : 1;
@@ -1492,6 +1509,45 @@ static int map_impl(ngm_mapper *m, int n, const char *reads, const void *d_reads
 			}
 			m->cov_off.push_back((uint32_t) packed.size());
 			if (int rc = ngm_coverage_add(m->coverage, m->cov_ref.data(), m->cov_pos.data(), m->cov_off.data(), packed.data(), m->cov_ref.size())) return rc;
+		}
+		if (snp_away) {
+			// ... with the read rows; the sequences and qualities are put as the records print them (bam_mapped, sam_device.h) and the arrays
+			// go through ngm_snp_add -- the records with a quality string and those without one in a call each
+			m->snp_rows.resize((size_t) n * q);
+			MAP_HIP_TRY(hipMemcpy(m->snp_rows.data(), m->d_reads.p, (size_t) n * q, hipMemcpyDeviceToHost));
+			const ngm::SamMeta *meta = (const ngm::SamMeta *) sam->meta;
+			const uint8_t *quals = (const uint8_t *) sam->quals;
+			const int per = paired ? 2 : 1;
+			const bool clip = m->prm.hard_clip || m->prm.silent_clip;
+			for (int with_q = 0; with_q < 2; ++with_q) {
+				std::vector<int32_t> s_ref, s_pos;
+				std::vector<uint32_t> c_off, s_off;
+				std::string c_text, s_text, q_text;
+				for (int u = 0; u < units; ++u) for (int k = 0; k < per; ++k) {
+					if (!((m->cov_mask[u] >> k) & 1)) continue;
+					const int i = per * u + k;
+					const int qlen = meta[i].qual_len & 0x7FFF;
+					if ((qlen != 0) != (with_q != 0)) continue;
+					const uint8_t *row = m->snp_rows.data() + (size_t) i * q, *qrow = quals + (size_t) i * q;
+					const int L = (int) strnlen((const char *) row, (size_t) q);
+					const int s0 = std::max(0, std::min(clip ? hits[i].qstart : 0, L));
+					const int sl = std::max(0, std::min(clip ? L - hits[i].qstart - hits[i].qend : L, L - s0));
+					const int QL = std::min(qlen, L);
+					s_ref.push_back(hits[i].contig); s_pos.push_back((int32_t) hits[i].pos); c_off.push_back((uint32_t) c_text.size()); s_off.push_back((uint32_t) s_text.size());
+					c_text.append(m->cov_text.data() + sam_refs[i].cig_off, sam_refs[i].cig_len);
+					for (int t = 0; t < sl; ++t) {
+						if (!hits[i].reverse) { s_text.push_back((char) row[s0 + t]); if (with_q) q_text.push_back(s0 + t < QL ? (char) qrow[s0 + t] : ':'); }
+						else {
+							const char ch = (char) row[L - 1 - (s0 + t)];
+							s_text.push_back(ch == 'A' ? 'T' : ch == 'T' ? 'A' : ch == 'C' ? 'G' : ch == 'G' ? 'C' : ch);
+							if (with_q) q_text.push_back(QL - 1 - (s0 + t) >= 0 ? (char) qrow[QL - 1 - (s0 + t)] : ':');
+						}
+					}
+				}
+				c_off.push_back((uint32_t) c_text.size()); s_off.push_back((uint32_t) s_text.size());
+				if (s_ref.empty()) continue;
+				if (int rc = ngm_snp_add(m->snp, s_ref.data(), s_pos.data(), c_off.data(), c_text.data(), s_off.data(), s_text.data(), with_q ? q_text.c_str() : nullptr, s_ref.size())) return rc;
+			}
 		}
 		float bgzf_ms = 0.f;
 		if (bam && total > 0) {
@@ -1548,6 +1604,7 @@ int ngm_mapper_set_batch_seq(ngm_mapper *m, uint64_t seq) { if (!m) return -22; 
 int ngm_mapper_set_fast_pairing(ngm_mapper *m, int on) { if (!m) return -22; m->fast_pairing = on ? 1 : 0; return 0; }
 int ngm_mapper_set_bam_sorter(ngm_mapper *m, ngm_bam_sort *s) { if (!m) return -22; m->sorter = s; return 0; }
 int ngm_mapper_set_coverage(ngm_mapper *m, ngm_coverage *c) { if (!m) return -22; m->coverage = c; return 0; }
+int ngm_mapper_set_snp(ngm_mapper *m, ngm_snp *s) { if (!m) return -22; m->snp = s; return 0; }
 
 void *ngm_host_alloc(size_t bytes) {
 	void *p = nullptr;

@@ -136,6 +136,8 @@ struct ngm_mapper {
 	std::vector<char> cov_text;
 	std::vector<int32_t> cov_ref, cov_pos;
 	std::vector<uint32_t> cov_off;
+	ngm_snp *snp = nullptr;           // ngm_mapper_set_snp: the same records are added to its counters (snp_device.h)
+	std::vector<uint8_t> snp_rows;    // ... by way of the host when it lives on another device: the batch's read rows
 	bool sam_ready = false;
 	std::string sam_rg;
 	ngm::DevBuf<char> d_sam_contig_names, d_sam_rg, d_sam_names, d_sam_text;

@@ -15,7 +15,9 @@
 // (csrc/read_trim.h), and --sort (ours, with --bam: the records of the whole run stay in GPU memory, are sorted there into coordinate order and
 // written as the sorted BAM plus <output>.bai, csrc/bam_sort.cpp; not with --argos, --shard, --shard-output, NGM_HIP_BAM_ZLIB=1, nor a
 // contig above 2^29 bases), and --coverage FILE (ours: the per-base depth of the run's mapped primary records as bedGraph, counted and turned into text on the
-// GPU, csrc/coverage.cpp; not with --argos, --shard, --shard-output, nor FILE = the output).  Not supported (rejected loudly): --vcf with --bs-mapping, --max-polya with --argos or --vcf, SAM/BAM *input*, --config.
+// GPU, csrc/coverage.cpp; not with --argos, --shard, --shard-output, nor FILE = the output), and --snp FILE with --snp-min-cov / --snp-min-frac /
+// --snp-min-qual (ours: the mismatch pileup of the same records and its single-base substitution calls as VCF, counted and turned into text on the GPU,
+// csrc/snp.cpp; not with --argos, --shard, --shard-output, --bs-mapping, --vcf, nor FILE = the output or the --coverage file).  Not supported (rejected loudly): --vcf with --bs-mapping, --max-polya with --argos or --vcf, SAM/BAM *input*, --config.
 //
 // Pass 2 is a pipeline, not a loop:
 //   splitter (1 thread)   cuts the input into batches: for plain 4-line FASTQ it only counts line ends in the mapped file
@@ -135,6 +137,9 @@ struct Opts {
 	int argos = 0, kmer_min_set = 0;
 	int sort = 0;   // --sort (ours): the BAM coordinate-sorted on the GPU, with its .bai (csrc/bam_sort.cpp)
 	std::string coverage;   // --coverage FILE (ours): the depth of the mapped primary records as bedGraph, made on the GPU (csrc/coverage.cpp)
+	std::string snp, snp_frac_text = "0.8";   // --snp FILE (ours): SNP calls of the mapped primary records as VCF, made on the GPU (csrc/snp.cpp); --snp-min-frac as given
+	long snp_min_cov = 10, snp_min_qual = 15;   // --snp-min-cov, --snp-min-qual
+	double snp_min_frac = 0.8;
 	ngm::trim::Options trim;   // -5/--trim5, --max-polya (Options.h:103-104)
 	float argos_min = 0.f;   // --argos-min-score (Default(ARGOS_MINSCORE, 0), Config.cpp:505)
 	int bs_mapping = 0, bs_cutoff = 6, match_tt = -1, match_tc = -1, match_set = 0, mismatch_set = 0, slam_seq = 0;
@@ -157,7 +162,7 @@ Opts parse(int argc, char **argv) {
 	Opts o;
 	for (int i = 1; i < argc; ++i) { if (i > 1) o.cmdline += " "; o.cmdline += argv[i]; }  // Config.cpp:565-574
 	enum { KSKIP = 1000, HARD, SILENT, KMIN, MB, MMP, GRP, GFP, MAXCMRS, NOUNAL, NOPROG, MAXRL, BINSZ, MAXKF, VFAST, FAST, SENS, VSENS, DEVICE,
-		SKIPSAVE, BATCH, VARIANT, SHARD, SHARDOUT, KEEPSHARDS, BAMOUT, WORKERS, SERIAL, AFFINE, GEP, PEDELIM, STRATA, BSMAP, BSCUT, MBTT, MBTC, SLAM, FASTPAIR, BROKENPAIRS, REFSCOREBUF, STATSFD, MAXPOLYA, RG0, RG_LAST = RG0 + 11, ARGOS, ARGOSMIN, VCF, KEEPTAGS, PARSEALL, SORTOUT, COVERAGE, UNSUPPORTED };
+		SKIPSAVE, BATCH, VARIANT, SHARD, SHARDOUT, KEEPSHARDS, BAMOUT, WORKERS, SERIAL, AFFINE, GEP, PEDELIM, STRATA, BSMAP, BSCUT, MBTT, MBTC, SLAM, FASTPAIR, BROKENPAIRS, REFSCOREBUF, STATSFD, MAXPOLYA, RG0, RG_LAST = RG0 + 11, ARGOS, ARGOSMIN, VCF, KEEPTAGS, PARSEALL, SORTOUT, COVERAGE, SNP, SNPCOV, SNPFRAC, SNPQUAL, UNSUPPORTED };
 	static const option lo[] = {
 		{"ref", required_argument, 0, 'r'}, {"qry", required_argument, 0, 'q'}, {"output", required_argument, 0, 'o'},
 		{"cpu-threads", required_argument, 0, 't'}, {"gpu", no_argument, 0, 'g'}, {"sensitivity", required_argument, 0, 's'},
@@ -184,6 +189,7 @@ Opts parse(int argc, char **argv) {
 		{"slam-seq", required_argument, 0, SLAM}, {"topn", required_argument, 0, 'n'}, {"strata", no_argument, 0, STRATA},
 		{"argos", no_argument, 0, ARGOS}, {"argos-min-score", required_argument, 0, ARGOSMIN}, {"vcf", required_argument, 0, VCF},
 		{"keep-tags", no_argument, 0, KEEPTAGS}, {"parse-all", no_argument, 0, PARSEALL}, {"sort", no_argument, 0, SORTOUT}, {"coverage", required_argument, 0, COVERAGE},
+		{"snp", required_argument, 0, SNP}, {"snp-min-cov", required_argument, 0, SNPCOV}, {"snp-min-frac", required_argument, 0, SNPFRAC}, {"snp-min-qual", required_argument, 0, SNPQUAL},
 		{"trim5", required_argument, 0, '5'}, {"max-polya", required_argument, 0, MAXPOLYA}, {"config", required_argument, 0, UNSUPPORTED},
 		{0, 0, 0, 0}};
 	int c, idx = 0;
@@ -271,6 +277,10 @@ Opts parse(int argc, char **argv) {
 		case ARGOSMIN: o.argos_min = (float) atof(optarg); break;
 		case SORTOUT: o.sort = 1; break;
 		case COVERAGE: o.coverage = optarg; if (o.coverage.empty()) die("--coverage expects a file name"); break;
+		case SNP: o.snp = optarg; if (o.snp.empty()) die("--snp expects a file name"); break;
+		case SNPCOV: { char *e = nullptr; o.snp_min_cov = strtol(optarg, &e, 10); if (e == optarg || *e || o.snp_min_cov < 0 || o.snp_min_cov > 2147483647L) die("--snp-min-cov expects a count of 0 or more"); break; }
+		case SNPFRAC: { char *e = nullptr; o.snp_min_frac = strtod(optarg, &e); o.snp_frac_text = optarg; if (e == optarg || *e || !(o.snp_min_frac > 0.0 && o.snp_min_frac <= 1.0)) die("--snp-min-frac expects a fraction in (0, 1]"); break; }
+		case SNPQUAL: { char *e = nullptr; o.snp_min_qual = strtol(optarg, &e, 10); if (e == optarg || *e || o.snp_min_qual < 0 || o.snp_min_qual > 93) die("--snp-min-qual expects a Phred quality in 0..93"); break; }
 		case UNSUPPORTED: die(std::string("option --") + lo[idx].name + " is not supported by the HIP backend yet");
 		default: die("unknown option (see src/config/Options.h of NextGenMap for the option set)");
 		}
@@ -290,6 +300,16 @@ Opts parse(int argc, char **argv) {
 		if (o.shard_n > 1) die("--coverage cannot be combined with --shard: the depth is over the whole run, not over one shard of it");
 		if (o.shard_output) die("--coverage cannot be combined with --shard-output: the depth is over the whole run, in one process");
 		if (o.coverage == o.out) die("--coverage cannot write to the -o/--output file: " + o.out);
+	}
+	if (!o.snp.empty()) {
+		// the pileup is over the records of the whole run, counted in the first GPU's memory; refused before any GPU work
+		if (o.argos) die("--snp cannot be combined with --argos: argos scores candidates, no alignments are made");
+		if (o.shard_n > 1) die("--snp cannot be combined with --shard: the pileup is over the whole run, not over one shard of it");
+		if (o.shard_output) die("--snp cannot be combined with --shard-output: the pileup is over the whole run, in one process");
+		if (o.bs_mapping) die("--snp cannot be combined with --bs-mapping: bisulfite conversions are not variants, and a strand-aware pileup is not built");
+		if (!o.vcf.empty()) die("--snp cannot be combined with --vcf: calling over an index built with known variants is not checked");
+		if (o.snp == o.out) die("--snp cannot be combined with -o " + o.out + ": the calls and the records need a file each");
+		if (o.snp == o.coverage) die("--snp cannot be combined with --coverage " + o.coverage + ": the calls and the depth need a file each");
 	}
 	if (o.argos) {
 		// ScoreWriter has no paired or binary form (DoWritePair throws, src/writer/ScoreWriter.cpp:75-77); refused before any GPU work
@@ -1397,9 +1417,29 @@ int main(int argc, char **argv) {
 		info("MAIN", cm);
 		if (gpu_sam) for (Worker &w : workers) if (ngm_mapper_set_coverage(w.m, coverage) < 0) die(ngm_pipeline_last_error());
 	}
+	// --snp: coverage's counters and three mismatch counters per base on the first device, beside that GPU's resident reference; fed like the
+	// coverage, by every mapper and by the host-formatted routes below
+	ngm_snp *snp = nullptr;
+	FILE *snp_file = nullptr;
+	if (!o.snp.empty()) {
+		snp_file = fopen(o.snp.c_str(), "wb");   // (before the run, not after it)
+		if (!snp_file) die("cannot write " + o.snp);
+		uint64_t bases = 0;
+		for (size_t i = 0; i < contig_lens.size(); ++i) bases += contig_lens[i];
+		ngm_snp_params sp{};
+		sp.min_cov = (uint32_t) o.snp_min_cov; sp.min_frac = o.snp_min_frac; sp.min_qual = (int) o.snp_min_qual; sp.min_frac_text = o.snp_frac_text.c_str();
+		snp = ngm_snp_create_for_ref(refs[0], &sp);
+		if (!snp) die(std::string("--snp: ") + ngm_pipeline_last_error());
+		char cm[200];
+		snprintf(cm, sizeof(cm), "SNP counters: %.1f MiB on GPU %d (16 bytes per base of the reference, held for the whole run)", (double) (bases + contig_lens.size()) * 16.0 / (double) (1 << 20), o.devices[0]);
+		info("MAIN", cm);
+		if (gpu_sam) for (Worker &w : workers) if (ngm_mapper_set_snp(w.m, snp) < 0) die(ngm_pipeline_last_error());
+	}
 	// (host-formatted routes: the records write_mapped formats without 0x100, per format_range call)
 	struct CovAcc { std::vector<int32_t> ref, pos; std::vector<uint32_t> off; std::string text; };
 	static thread_local CovAcc *tl_cov = nullptr;
+	struct SnpAcc { std::vector<int32_t> ref, pos; std::vector<uint32_t> off, seq_off; std::string text, seq, qual; };   // [0]: records without a quality string, [1]: with one
+	static thread_local SnpAcc *tl_snp = nullptr;
 	auto pipeline_error = [&](long long rc, bool from_mapper = false) -> std::string {   // (the sorter never spills: -12 from it, -28 through a mapper, ends the run with what it held)
 		std::string e = ngm_pipeline_last_error();
 		if (sorter && rc == (from_mapper ? -28 : -12)) {
@@ -1475,6 +1515,20 @@ int main(int argc, char **argv) {
 		if (tl_cov && !(flags & 0x100)) {   // --coverage
 			tl_cov->ref.push_back(h.contig); tl_cov->pos.push_back((int32_t) h.pos); tl_cov->off.push_back((uint32_t) tl_cov->text.size());
 			tl_cov->text += v.cigar;
+		}
+		if (tl_snp && !(flags & 0x100)) {   // --snp: the sequence and the qualities as the record prints them
+			SnpAcc &a = tl_snp[noq ? 0 : 1];
+			a.ref.push_back(h.contig); a.pos.push_back((int32_t) h.pos); a.off.push_back((uint32_t) a.text.size()); a.seq_off.push_back((uint32_t) a.seq.size());
+			a.text += v.cigar;
+			const int QL = std::min<int>((int) v.r->qual_len, L);
+			for (int t = 0; t < sl; ++t) {
+				if (!h.reverse) { a.seq.push_back(v.row[s0 + t]); if (!noq) a.qual.push_back((s0 + t < QL) ? v.r->qual[s0 + t] : ':'); }
+				else {
+					const char ch = v.row[L - 1 - (s0 + t)];
+					a.seq.push_back(ch == 'A' ? 'T' : ch == 'T' ? 'A' : ch == 'C' ? 'G' : ch == 'G' ? 'C' : ch);
+					if (!noq) a.qual.push_back((QL - 1 - (s0 + t) >= 0) ? v.r->qual[QL - 1 - (s0 + t)] : ':');
+				}
+			}
 		}
 		if (o.bam) {  // BAMWriter::DoWriteReadGeneric (BAMWriter.cpp:147-298)
 			char seq[1024], qual[1024];
@@ -1579,6 +1633,7 @@ int main(int argc, char **argv) {
 	// others' insert sizes -- summed over the run (the GPU formatter counts the same: ngm_mapper_last_pair_stats)
 	std::atomic<uint64_t> pair_stat[3];
 	for (auto &x : pair_stat) x = 0;
+	std::atomic<bool> snp_failed{false};   // ... or an ngm_snp_add
 	std::atomic<bool> cov_failed{false};   // an ngm_coverage_add of a formatted range failed: the run fails behind its batch
 	auto format_range = [&](const Batch &b, const Worker &w, int lo, int hi, std::string &s, size_t &n_total, size_t &n_mapped, size_t &n_written) {
 		struct PairAcc { std::atomic<uint64_t> *t; uint64_t v[3] = {0, 0, 0}; ~PairAcc() { for (int k = 0; k < 3; ++k) if (v[k]) t[k] += v[k]; } } pacc{pair_stat};
@@ -1593,6 +1648,19 @@ int main(int argc, char **argv) {
 			}
 		} cov_scope{coverage, &cov_acc, &cov_failed};
 		if (coverage) tl_cov = &cov_acc;
+		SnpAcc snp_acc[2];
+		struct SnpScope {   // ... and to the SNP counters
+			ngm_snp *c; SnpAcc *a; std::atomic<bool> *bad;
+			~SnpScope() {
+				tl_snp = nullptr;
+				for (int k = 0; c && k < 2; ++k) {
+					if (a[k].ref.empty()) continue;
+					a[k].off.push_back((uint32_t) a[k].text.size()); a[k].seq_off.push_back((uint32_t) a[k].seq.size());
+					if (ngm_snp_add(c, a[k].ref.data(), a[k].pos.data(), a[k].off.data(), a[k].text.data(), a[k].seq_off.data(), a[k].seq.data(), k ? a[k].qual.c_str() : nullptr, a[k].ref.size()) < 0) *bad = true;
+				}
+			}
+		} snp_scope{snp, snp_acc, &snp_failed};
+		if (snp) tl_snp = snp_acc;
 		auto view = [&](int i, int t = 0) {
 			const size_t e = (size_t) i * topn + t;
 			View v{&b.recs[i], &w.hits[e], w.rows + (size_t) i * q, 0, &w.cig[e * stride], &w.md[e * stride]};
@@ -2090,6 +2158,7 @@ int main(int argc, char **argv) {
 			}, 1, (o.bam && !gpu_bgzf) ? ngm::ThreadPool::cpu_quota() : 0);   // (BAM with zlib: records + deflate keep every thread busy for the whole batch)
 			for (int c = 0; c < n_chunks; ++c) { b->n_total += ct[c]; b->n_mapped += cm[c]; b->n_written += cw[c]; }
 			if (cov_failed) { fail(std::string("--coverage: ") + ngm_pipeline_last_error()); continue; }
+			if (snp_failed) { fail(std::string("--snp: ") + ngm_pipeline_last_error()); continue; }
 			if (gpu_bgzf) {
 				// the batch's records, chunk after chunk, in page-locked memory -> whole BGZF blocks from the GPU (a batch ends with a short
 				// block: batches -- and shards -- concatenate into one valid file) -> pieces for the writer
@@ -2273,6 +2342,33 @@ int main(int argc, char **argv) {
 			info("MAIN", msg);
 		}
 	}
+	if (snp && !failed) {
+		// --snp: every batch has added its records.  The difference array becomes depths, the counters calls and the calls lines chunk by chunk
+		// on the GPU; the lines are streamed into the file behind the header
+		const auto t_snp = std::chrono::steady_clock::now();
+		FILE *sf = snp_file;
+		size_t cap = (size_t) 8 << 20;
+		std::vector<char> buf(cap);
+		if (const int rc = ngm_snp_finish(snp); rc < 0) fail(std::string("--snp: ") + ngm_pipeline_last_error());
+		while (!failed) {
+			const long long got = ngm_snp_next(snp, buf.data(), cap);
+			if (got < 0) { fail(std::string("--snp: ") + ngm_pipeline_last_error()); break; }
+			if (got == 0) break;
+			if ((size_t) got > cap) { cap = (size_t) got; buf.resize(cap); continue; }
+			if (fwrite(buf.data(), 1, (size_t) got, sf) != (size_t) got) { fail("write error on " + o.snp); break; }
+		}
+		snp_file = nullptr;
+		if (fclose(sf) != 0) fail("write error on " + o.snp);
+		if (!failed) {
+			uint64_t sc[5] = {0, 0, 0, 0, 0};
+			float sms[4] = {0, 0, 0, 0};
+			(void) ngm_snp_stats(snp, sc, sms);
+			snprintf(msg, sizeof(msg), "SNPs on the GPU: %llu alignments, %llu mismatching bases counted, %llu calls, %llu bytes of VCF; kernels: add %.2f ms, scan %.2f ms, flag %.2f ms, text %.2f ms; "
+					"%llu covered bases; %.3f s after the last batch", (unsigned long long) sc[0], (unsigned long long) sc[1], (unsigned long long) sc[2], (unsigned long long) sc[3], sms[0], sms[1], sms[2], sms[3],
+					(unsigned long long) sc[4], std::chrono::duration<double>(std::chrono::steady_clock::now() - t_snp).count());
+			info("MAIN", msg);
+		}
+	}
 	if (o.bam && o.shard_i == o.shard_n - 1) { std::string z; ngm::bam::bgzf_eof(z); if (!put_all(z.data(), z.size(), out_off)) fail("write error on " + o.out); out_off += z.size(); }   // (--shard: the end-of-file block travels with the last shard)
 	if (close(out_fd) != 0) fail("write error on " + o.out);
 	if (failed) die(fail_msg);
@@ -2396,6 +2492,8 @@ int main(int argc, char **argv) {
 	ngm_bam_sort_destroy(sorter);
 	ngm_coverage_destroy(coverage);
 	if (coverage_file) fclose(coverage_file);
+	ngm_snp_destroy(snp);
+	if (snp_file) fclose(snp_file);
 	for (TextBuf &t : text_free) ngm_host_free(t.p);
 	ngm_pair_state_destroy(pair_state);
 	for (ngm_ref *r2 : refs) ngm_ref_destroy(r2);

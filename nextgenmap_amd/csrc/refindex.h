@@ -128,6 +128,11 @@ int bam_sort_device(const struct ::ngm_bam_sort *s);
 int coverage_device(const struct ::ngm_coverage *c);
 int coverage_target(struct ::ngm_coverage *c, int32_t **counters, const uint64_t **d_off, int *n_ref, unsigned long long **d_n_aln);
 void coverage_note_add_ms(struct ::ngm_coverage *c, float ms);
+// snp.cpp, the same three for an SNP object: where a snp_add_kernel on its device adds (snp_device.h's Target)
+namespace snp { struct Target; }
+int snp_device(const struct ::ngm_snp *c);
+int snp_target(struct ::ngm_snp *c, snp::Target *t);
+void snp_note_add_ms(struct ::ngm_snp *c, float ms);
 // k-mer integer as the reference builds it: 2 bits per base, A0 C1 T2 G3 ((c >> 1) & 3, CSstatic.cpp:20-22)
 inline uint32_t kmer_code_of_class(uint32_t cls) { return cls == 2 ? 3u : (cls == 3 ? 2u : cls); }
 // reverse complement of a k-mer integer (PrefixTable.cpp:94-108), valid for 2k <= 32

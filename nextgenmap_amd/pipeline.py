@@ -42,6 +42,11 @@ class CoverageParams(C.Structure):   # ngm_coverage_params
     _fields_ = [("device", C.c_int), ("n_ref", C.c_int), ("ref_len", C.POINTER(C.c_uint32)), ("ref_name", C.POINTER(C.c_char_p)), ("scan_chunk", C.c_size_t)]
 
 
+class SnpParams(C.Structure):   # ngm_snp_params
+    _fields_ = [("device", C.c_int), ("n_ref", C.c_int), ("ref_len", C.POINTER(C.c_uint32)), ("ref_name", C.POINTER(C.c_char_p)), ("ref_seq", C.POINTER(C.c_char_p)),
+                ("min_cov", C.c_uint32), ("min_frac", C.c_double), ("min_qual", C.c_int), ("min_frac_text", C.c_char_p), ("scan_chunk", C.c_size_t)]
+
+
 def _lib():
     global _bound
     lib = load_library()
@@ -136,6 +141,17 @@ def _lib():
         lib.ngm_coverage_next.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         lib.ngm_coverage_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.ngm_mapper_set_coverage.argtypes = [C.c_void_p, C.c_void_p]
+        lib.ngm_snp_create.restype = C.c_void_p
+        lib.ngm_snp_create.argtypes = [C.POINTER(SnpParams)]
+        lib.ngm_snp_create_for_ref.restype = C.c_void_p
+        lib.ngm_snp_create_for_ref.argtypes = [C.c_void_p, C.POINTER(SnpParams)]
+        lib.ngm_snp_destroy.argtypes = [C.c_void_p]
+        lib.ngm_snp_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_char_p, C.c_char_p, C.c_size_t]
+        lib.ngm_snp_finish.argtypes = [C.c_void_p]
+        lib.ngm_snp_next.restype = C.c_longlong
+        lib.ngm_snp_next.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.ngm_snp_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.ngm_mapper_set_snp.argtypes = [C.c_void_p, C.c_void_p]
         _bound = True
     return lib
 
@@ -328,6 +344,109 @@ class Coverage:
     def close(self):
         if self._h:
             _lib().ngm_coverage_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SnpCaller:
+    """The mismatch pileup of a run, counted in GPU memory, and its single-base substitution calls handed back as VCF text
+    (include/ngm_pipeline.h, ngm_snp_*): what `ngm-hip --snp` writes.  contigs: [(name, sequence)]; min_frac: a number, or the text the
+    header prints (its float() is the threshold); reference: a Reference whose resident genome is read instead (contigs is then not used)."""
+
+    def __init__(self, contigs, device=0, min_cov=10, min_frac="0.8", min_qual=15, scan_chunk=0, reference=None):
+        b = lambda x: x.encode() if isinstance(x, str) else bytes(x)
+        text = min_frac if isinstance(min_frac, (str, bytes)) else repr(float(min_frac))
+        p = SnpParams()
+        p.device, p.min_cov, p.min_frac, p.min_qual, p.min_frac_text, p.scan_chunk = device, min_cov, float(text), min_qual, b(text), scan_chunk
+        if reference is not None:
+            self._ref = reference   # (it must outlive this object)
+            self._h = _lib().ngm_snp_create_for_ref(reference.h, C.byref(p))
+        else:
+            n = len(contigs)
+            self._seq_bytes = [b(sq) for _, sq in contigs]
+            self._len = (C.c_uint32 * max(1, n))(*[len(sq) for sq in self._seq_bytes])
+            self._name = (C.c_char_p * max(1, n))(*[b(nm) for nm, _ in contigs])
+            self._seq = (C.c_char_p * max(1, n))(*self._seq_bytes)
+            p.n_ref, p.ref_len, p.ref_name, p.ref_seq = n, self._len, self._name, self._seq
+            self._h = _lib().ngm_snp_create(C.byref(p))
+        if not self._h:
+            raise _err()
+
+    def add(self, records):
+        """[(contig index, 0-based position, CIGAR text, sequence, qualities or None)]: all with qualities or all without; raises on the
+        first record the validator refuses, adding nothing"""
+        records = list(records)
+        b = lambda x: x.encode() if isinstance(x, str) else bytes(x)
+        cig = [b(r[2]) for r in records]
+        seq = [b(r[3]) for r in records]
+        with_q = [r[4] is not None for r in records]
+        if any(with_q) and not all(with_q):
+            raise ValueError("records with and without qualities go into separate calls")
+        qual = None
+        if records and all(with_q):
+            if any(len(r[4]) != len(sq) for r, sq in zip(records, seq)):
+                raise ValueError("a quality string has another length than its sequence")
+            qual = b"".join(b(r[4]) for r in records)
+        off = np.zeros(len(cig) + 1, dtype=np.uint32)
+        off[1:] = np.cumsum([len(c) for c in cig], dtype=np.uint64)
+        soff = np.zeros(len(seq) + 1, dtype=np.uint32)
+        soff[1:] = np.cumsum([len(c) for c in seq], dtype=np.uint64)
+        self.add_arrays(np.array([r[0] for r in records], dtype=np.int32), np.array([r[1] for r in records], dtype=np.int32), off, b"".join(cig), soff, b"".join(seq), qual)
+
+    def add_arrays(self, ref_id, pos0, cigar_off, cigar_text, seq_off, seq_text, qual_text=None):
+        ref_id = np.ascontiguousarray(ref_id, dtype=np.int32)
+        pos0 = np.ascontiguousarray(pos0, dtype=np.int32)
+        cigar_off = np.ascontiguousarray(cigar_off, dtype=np.uint32)
+        seq_off = np.ascontiguousarray(seq_off, dtype=np.uint32)
+        if len(pos0) != len(ref_id) or len(cigar_off) != len(ref_id) + 1 or len(seq_off) != len(ref_id) + 1:
+            raise ValueError("ref_id, pos0 of n entries and cigar_off, seq_off of n + 1")
+        if _lib().ngm_snp_add(self._h, ref_id.ctypes.data, pos0.ctypes.data, cigar_off.ctypes.data, bytes(cigar_text), seq_off.ctypes.data, bytes(seq_text),
+                              None if qual_text is None else bytes(qual_text), len(ref_id)) < 0:
+            raise _err()
+
+    def finish(self):
+        if _lib().ngm_snp_finish(self._h) < 0:
+            raise _err()
+
+    def next(self, cap, out=None):
+        """one ngm_snp_next call with a buffer of cap bytes: (return value, the bytes copied)"""
+        if out is None:
+            out = C.create_string_buffer(max(1, cap))
+        n = _lib().ngm_snp_next(self._h, out, cap)
+        if n < 0:
+            raise _err()
+        return n, (C.string_at(out, n) if n <= cap else b"")
+
+    def pieces(self, cap=1 << 20):
+        """the file, in pieces of whole lines; the header is the first"""
+        out = C.create_string_buffer(cap)
+        while True:
+            n, data = self.next(cap, out)
+            if n == 0:
+                return
+            if n > cap:
+                cap = n
+                out = C.create_string_buffer(cap)
+                continue
+            yield data
+
+    def stats(self):
+        counts = (C.c_uint64 * 5)()
+        ms = (C.c_float * 4)()
+        if _lib().ngm_snp_stats(self._h, counts, ms) < 0:
+            raise _err()
+        d = dict(zip(("alignments", "alt_bases", "calls", "text_bytes", "covered_bases"), (int(x) for x in counts)))
+        d.update(zip(("add_ms", "scan_ms", "flag_ms", "text_ms"), (float(x) for x in ms)))
+        return d
+
+    def close(self):
+        if self._h:
+            _lib().ngm_snp_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -547,6 +666,11 @@ class Mapper:
     def set_coverage(self, coverage):
         """every batch map_sam finishes adds its mapped primary records to `coverage` (a Coverage, or None to detach)"""
         if self.lib.ngm_mapper_set_coverage(self.h, coverage._h if coverage is not None else None) < 0:
+            raise _err()
+
+    def set_snp(self, snp):
+        """every batch map_sam finishes adds its mapped primary records to `snp` (a SnpCaller, or None to detach)"""
+        if self.lib.ngm_mapper_set_snp(self.h, snp._h if snp is not None else None) < 0:
             raise _err()
 
     def set_bam_sorter(self, sorter):
