@@ -15,37 +15,16 @@
 
 #include "../../include/ngm_pipeline.h"
 #include "bam_sort_device.h"
+#include "device_util.h"
 #include "refindex.h"
 
 namespace bs = ngm::bamsort;
 
-#define SORT_HIP_TRY(expr)                                                                      \
-	do {                                                                                        \
-		hipError_t e_ = (expr);                                                                 \
-		if (e_ != hipSuccess) {                                                                 \
-			ngm::pipeline_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-			return -5;                                                                          \
-		}                                                                                       \
-	} while (0)
+using ngm::Buf;
+using ngm::DeviceGuard;
+using ngm::blocks_of;
 
 namespace {
-template <typename T>
-struct Buf {   // device memory of exactly the size asked for (the sorter's arrays are sized once)
-	T *p = nullptr;
-	size_t n = 0;
-	int alloc(size_t count) {
-		release();
-		if (hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) { (void) hipGetLastError(); p = nullptr; return -1; }
-		n = count;
-		return 0;
-	}
-	void release() { if (p) (void) hipFree(p); p = nullptr; n = 0; }
-	~Buf() { release(); }
-	Buf() = default;
-	Buf(const Buf &) = delete;
-	Buf &operator=(const Buf &) = delete;
-};
-
 struct Segment {
 	uint64_t seq = 0;
 	uint8_t *d = nullptr;          // the run's bytes, 16 bytes of padding behind them
@@ -54,13 +33,6 @@ struct Segment {
 	uint32_t n_rec = 0;
 };
 
-struct DeviceGuard {   // an add from a thread that works on another GPU leaves that thread's device as it was
-	int prev = -1;
-	explicit DeviceGuard(int device) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; if (prev != device) (void) hipSetDevice(device); else prev = -1; }
-	~DeviceGuard() { if (prev >= 0) (void) hipSetDevice(prev); }
-};
-
-unsigned blocks_of(uint64_t n) { return (unsigned) ((n + 255) / 256); }
 }  // namespace
 
 struct ngm_bam_sort {
@@ -138,35 +110,32 @@ int out_of_memory(const ngm_bam_sort *s, const char *what, size_t bytes) {
 	return -12;
 }
 
-template <typename T>
-int grow(Buf<T> &b, size_t n) { return n <= b.n ? 0 : b.alloc(n + n / 4 + 64); }   // the scratch of add: allocated when a batch is larger than any before
-
 // d_off: n_ranges + 1 offsets into the segment's bytes, on the device.  Record offsets from them; the records are checked on the way.
 // expect_records >= 0 (the host has walked the chain): count, scan and write in one go, one synchronisation; < 0 (the device formatter's
 // units): the count comes back first, for the size of the offsets.  The scratch arrays are the sorter's: no allocation but the segment's own.
 int index_segment(ngm_bam_sort *s, Segment &sg, const uint32_t *d_off, uint32_t n_ranges, long long expect_records) {
 	size_t tb = 0;
-	SORT_HIP_TRY(rocprim::exclusive_scan(nullptr, tb, (uint32_t *) nullptr, (uint32_t *) nullptr, 0u, (size_t) n_ranges + 1, rocprim::plus<uint32_t>(), s->st));
-	if (grow(s->w_count, (size_t) n_ranges + 1) || grow(s->w_base, (size_t) n_ranges + 1) || grow(s->w_bad, 1) || grow(s->w_tmp, tb + 16)) return out_of_memory(s, "record offsets", ((size_t) n_ranges + 1) * 8 + tb);
+	NGM_HIP_TRY(rocprim::exclusive_scan(nullptr, tb, (uint32_t *) nullptr, (uint32_t *) nullptr, 0u, (size_t) n_ranges + 1, rocprim::plus<uint32_t>(), s->st));
+	if (s->w_count.grow((size_t) n_ranges + 1) || s->w_base.grow((size_t) n_ranges + 1) || s->w_bad.grow(1) || s->w_tmp.grow(tb + 16)) return out_of_memory(s, "record offsets", ((size_t) n_ranges + 1) * 8 + tb);
 	auto write = [&](uint32_t cap) -> int {
 		if (cap == 0) return 0;
 		if (hipMalloc(&sg.d_rec_off, (size_t) cap * 4) != hipSuccess) { (void) hipGetLastError(); sg.d_rec_off = nullptr; return out_of_memory(s, "record offsets", (size_t) cap * 4); }
 		hipLaunchKernelGGL(bs::walk_ranges_kernel<true>, dim3(blocks_of(n_ranges)), dim3(256), 0, s->st, (const uint8_t *) sg.d, d_off, n_ranges, (uint32_t *) nullptr, (const uint32_t *) s->w_base.p,
 				sg.d_rec_off, cap, s->w_bad.p);
-		SORT_HIP_TRY(hipGetLastError());
+		NGM_HIP_TRY(hipGetLastError());
 		return 0;
 	};
-	SORT_HIP_TRY(hipMemsetAsync(s->w_bad.p, 0xFF, 4, s->st));
-	SORT_HIP_TRY(hipMemsetAsync(s->w_count.p + n_ranges, 0, 4, s->st));
+	NGM_HIP_TRY(hipMemsetAsync(s->w_bad.p, 0xFF, 4, s->st));
+	NGM_HIP_TRY(hipMemsetAsync(s->w_count.p + n_ranges, 0, 4, s->st));
 	hipLaunchKernelGGL(bs::walk_ranges_kernel<false>, dim3(blocks_of(n_ranges)), dim3(256), 0, s->st, (const uint8_t *) sg.d, d_off, n_ranges, s->w_count.p, (const uint32_t *) nullptr,
 			(uint32_t *) nullptr, 0u, s->w_bad.p);
-	SORT_HIP_TRY(hipGetLastError());
-	SORT_HIP_TRY(rocprim::exclusive_scan(s->w_tmp.p, tb, s->w_count.p, s->w_base.p, 0u, (size_t) n_ranges + 1, rocprim::plus<uint32_t>(), s->st));
+	NGM_HIP_TRY(hipGetLastError());
+	NGM_HIP_TRY(rocprim::exclusive_scan(s->w_tmp.p, tb, s->w_count.p, s->w_base.p, 0u, (size_t) n_ranges + 1, rocprim::plus<uint32_t>(), s->st));
 	if (expect_records >= 0) { if (int rc = write((uint32_t) expect_records)) return rc; }
 	uint32_t h_bad = 0, h_total = 0;
-	SORT_HIP_TRY(hipMemcpyAsync(&h_bad, s->w_bad.p, 4, hipMemcpyDeviceToHost, s->st));
-	SORT_HIP_TRY(hipMemcpyAsync(&h_total, s->w_base.p + n_ranges, 4, hipMemcpyDeviceToHost, s->st));
-	SORT_HIP_TRY(hipStreamSynchronize(s->st));
+	NGM_HIP_TRY(hipMemcpyAsync(&h_bad, s->w_bad.p, 4, hipMemcpyDeviceToHost, s->st));
+	NGM_HIP_TRY(hipMemcpyAsync(&h_total, s->w_base.p + n_ranges, 4, hipMemcpyDeviceToHost, s->st));
+	NGM_HIP_TRY(hipStreamSynchronize(s->st));
 	if (h_bad != 0xFFFFFFFFu || (expect_records >= 0 && (long long) h_total != expect_records)) {
 		ngm::pipeline_set_error("ngm_bam_sort_add: seq %llu: the records of range %u do not form a chain of block_size that ends with it", (unsigned long long) sg.seq, h_bad);
 		return -22;
@@ -174,7 +143,7 @@ int index_segment(ngm_bam_sort *s, Segment &sg, const uint32_t *d_off, uint32_t 
 	sg.n_rec = h_total;
 	if (expect_records < 0) {
 		if (int rc = write(h_total)) return rc;
-		SORT_HIP_TRY(hipStreamSynchronize(s->st));   // (d_off is the mapper's: it is free again when this returns)
+		NGM_HIP_TRY(hipStreamSynchronize(s->st));   // (d_off is the mapper's: it is free again when this returns)
 	}
 	return 0;
 }
@@ -195,11 +164,11 @@ int add_segment(ngm_bam_sort *s, uint64_t seq, const void *src, bool src_on_devi
 	if (hipMalloc(&sg.d, n_bytes + 16) != hipSuccess) { (void) hipGetLastError(); s->seqs.erase(seq); return out_of_memory(s, "a segment of records", n_bytes + 16); }
 	int rc = 0;
 	auto body = [&]() -> int {
-		SORT_HIP_TRY(hipMemsetAsync(sg.d + n_bytes, 0, 16, s->st));
-		SORT_HIP_TRY(hipMemcpyAsync(sg.d, src, n_bytes, src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->st));
+		NGM_HIP_TRY(hipMemsetAsync(sg.d + n_bytes, 0, 16, s->st));
+		NGM_HIP_TRY(hipMemcpyAsync(sg.d, src, n_bytes, src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->st));
 		if (h_off) {
-			if (grow(s->w_off, (size_t) n_ranges + 1)) return out_of_memory(s, "range offsets", ((size_t) n_ranges + 1) * 4);
-			SORT_HIP_TRY(hipMemcpyAsync(s->w_off.p, h_off, ((size_t) n_ranges + 1) * 4, hipMemcpyHostToDevice, s->st));   // (pageable memory: staged before the call returns)
+			if (s->w_off.grow((size_t) n_ranges + 1)) return out_of_memory(s, "range offsets", ((size_t) n_ranges + 1) * 4);
+			NGM_HIP_TRY(hipMemcpyAsync(s->w_off.p, h_off, ((size_t) n_ranges + 1) * 4, hipMemcpyHostToDevice, s->st));   // (pageable memory: staged before the call returns)
 		}
 		return index_segment(s, sg, h_off ? s->w_off.p : d_off, n_ranges, expect_records);
 	};
@@ -250,20 +219,20 @@ extern "C" int ngm_bam_sort_finish(ngm_bam_sort *s, int n_ref) {
 	if (key_in.alloc(n) || s->key.alloc(n) || ptr.alloc(n) || idx_in.alloc(n) || idx.alloc(n) || len.alloc(n) || end_in.alloc(n) || bin_flag.alloc(n) || ctr.alloc(2))
 		return out_of_memory(s, "the sort's arrays", (size_t) n * 44);
 	const unsigned long long ctr0[2] = {~0ull, 0ull};
-	SORT_HIP_TRY(hipMemcpyAsync(ctr.p, ctr0, 16, hipMemcpyHostToDevice, s->st));
-	SORT_HIP_TRY(hipEventRecord(s->ev0, s->st));
+	NGM_HIP_TRY(hipMemcpyAsync(ctr.p, ctr0, 16, hipMemcpyHostToDevice, s->st));
+	NGM_HIP_TRY(hipEventRecord(s->ev0, s->st));
 	uint64_t g0 = 0;
 	for (const Segment &sg : s->segs) {
 		if (!sg.n_rec) continue;
 		hipLaunchKernelGGL(bs::keys_kernel, dim3(blocks_of(sg.n_rec)), dim3(256), 0, s->st, (const uint8_t *) sg.d, (const uint32_t *) sg.d_rec_off, sg.n_rec, g0, n_ref, key_in.p, idx_in.p, ptr.p,
 				len.p, end_in.p, bin_flag.p, ctr.p, ctr.p + 1);
-		SORT_HIP_TRY(hipGetLastError());
+		NGM_HIP_TRY(hipGetLastError());
 		g0 += sg.n_rec;
 	}
-	SORT_HIP_TRY(hipEventRecord(s->ev1, s->st));
+	NGM_HIP_TRY(hipEventRecord(s->ev1, s->st));
 	unsigned long long h_ctr[2] = {0, 0};
-	SORT_HIP_TRY(hipMemcpyAsync(h_ctr, ctr.p, 16, hipMemcpyDeviceToHost, s->st));
-	SORT_HIP_TRY(hipStreamSynchronize(s->st));
+	NGM_HIP_TRY(hipMemcpyAsync(h_ctr, ctr.p, 16, hipMemcpyDeviceToHost, s->st));
+	NGM_HIP_TRY(hipStreamSynchronize(s->st));
 	(void) hipEventElapsedTime(&s->ms[0], s->ev0, s->ev1);
 	if (h_ctr[0] != ~0ull) {
 		uint64_t g = h_ctr[0] >> 8, seq = 0, at = g;
@@ -277,30 +246,30 @@ extern "C" int ngm_bam_sort_finish(ngm_bam_sort *s, int n_ref) {
 	s->n_no_coor = h_ctr[1];
 	// one stable radix sort of (key, record number): equal keys keep the run order
 	size_t tb = 0;
-	SORT_HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, key_in.p, s->key.p, idx_in.p, idx.p, (size_t) n, 0, 64, s->st));
+	NGM_HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, key_in.p, s->key.p, idx_in.p, idx.p, (size_t) n, 0, 64, s->st));
 	{
 		Buf<uint8_t> tmp;
 		if (tmp.alloc(tb + 16)) return out_of_memory(s, "the sort", tb);
-		SORT_HIP_TRY(hipEventRecord(s->ev0, s->st));
-		SORT_HIP_TRY(rocprim::radix_sort_pairs(tmp.p, tb, key_in.p, s->key.p, idx_in.p, idx.p, (size_t) n, 0, 64, s->st));
-		SORT_HIP_TRY(hipEventRecord(s->ev1, s->st));
-		SORT_HIP_TRY(hipStreamSynchronize(s->st));
+		NGM_HIP_TRY(hipEventRecord(s->ev0, s->st));
+		NGM_HIP_TRY(rocprim::radix_sort_pairs(tmp.p, tb, key_in.p, s->key.p, idx_in.p, idx.p, (size_t) n, 0, 64, s->st));
+		NGM_HIP_TRY(hipEventRecord(s->ev1, s->st));
+		NGM_HIP_TRY(hipStreamSynchronize(s->st));
 		(void) hipEventElapsedTime(&s->ms[1], s->ev0, s->ev1);
 	}
 	key_in.release(); idx_in.release();
 	if (s_len.alloc(n + 1) || s->u.alloc(n + 1) || s->s_ptr.alloc(n) || s->s_end.alloc(n) || s->s_bin_flag.alloc(n)) return out_of_memory(s, "the sorted arrays", (size_t) n * 32);
-	SORT_HIP_TRY(hipMemsetAsync(s_len.p + n, 0, 8, s->st));
+	NGM_HIP_TRY(hipMemsetAsync(s_len.p + n, 0, 8, s->st));
 	hipLaunchKernelGGL(bs::permute_kernel, dim3(blocks_of(n)), dim3(256), 0, s->st, (const uint32_t *) idx.p, n, (const uint64_t *) ptr.p, (const uint32_t *) len.p, (const uint32_t *) end_in.p,
 			(const uint32_t *) bin_flag.p, s->s_ptr.p, s_len.p, s->s_end.p, s->s_bin_flag.p);
-	SORT_HIP_TRY(hipGetLastError());
-	SORT_HIP_TRY(rocprim::exclusive_scan(nullptr, tb, s_len.p, s->u.p, (uint64_t) 0, (size_t) n + 1, rocprim::plus<uint64_t>(), s->st));
+	NGM_HIP_TRY(hipGetLastError());
+	NGM_HIP_TRY(rocprim::exclusive_scan(nullptr, tb, s_len.p, s->u.p, (uint64_t) 0, (size_t) n + 1, rocprim::plus<uint64_t>(), s->st));
 	{
 		Buf<uint8_t> tmp;
 		if (tmp.alloc(tb + 16)) return out_of_memory(s, "a scan", tb);
-		SORT_HIP_TRY(rocprim::exclusive_scan(tmp.p, tb, s_len.p, s->u.p, (uint64_t) 0, (size_t) n + 1, rocprim::plus<uint64_t>(), s->st));
+		NGM_HIP_TRY(rocprim::exclusive_scan(tmp.p, tb, s_len.p, s->u.p, (uint64_t) 0, (size_t) n + 1, rocprim::plus<uint64_t>(), s->st));
 		uint64_t total = 0;
-		SORT_HIP_TRY(hipMemcpyAsync(&total, s->u.p + n, 8, hipMemcpyDeviceToHost, s->st));
-		SORT_HIP_TRY(hipStreamSynchronize(s->st));
+		NGM_HIP_TRY(hipMemcpyAsync(&total, s->u.p + n, 8, hipMemcpyDeviceToHost, s->st));
+		NGM_HIP_TRY(hipStreamSynchronize(s->st));
 		if (total != s->total_bytes) { ngm::pipeline_set_error("ngm_bam_sort_finish: the records' lengths sum to %llu bytes, %llu were added", (unsigned long long) total, (unsigned long long) s->total_bytes); return -5; }
 	}
 	s->sorted = true;
@@ -313,11 +282,11 @@ int launch_gather(ngm_bam_sort *s, uint64_t c) {
 	const int b = (int) (c & 1);
 	const uint64_t s0 = c * s->chunk_bytes, nb = std::min<uint64_t>(s->chunk_bytes, s->total_bytes - s0);
 	if (!s->chunk[b].p && s->chunk[b].alloc(std::min<uint64_t>(s->chunk_bytes, s->total_bytes) + 16)) return out_of_memory(s, "a chunk of the sorted stream", s->chunk_bytes);
-	SORT_HIP_TRY(hipEventRecord(s->evg[b][0], s->st_gather));
+	NGM_HIP_TRY(hipEventRecord(s->evg[b][0], s->st_gather));
 	const unsigned grid = (unsigned) std::min<uint64_t>((nb + bs::kGatherBlockBytes - 1) / bs::kGatherBlockBytes, (uint64_t) s->grid * 8);
 	hipLaunchKernelGGL(bs::gather_kernel, dim3(grid), dim3(256), 0, s->st_gather, (const uint64_t *) s->u.p, (const uint64_t *) s->s_ptr.p, s->n_rec, s0, nb, s->chunk[b].p);
-	SORT_HIP_TRY(hipGetLastError());
-	SORT_HIP_TRY(hipEventRecord(s->evg[b][1], s->st_gather));
+	NGM_HIP_TRY(hipGetLastError());
+	NGM_HIP_TRY(hipEventRecord(s->evg[b][1], s->st_gather));
 	s->gathered[b] = (long long) c;
 	return 0;
 }
@@ -334,7 +303,7 @@ extern "C" long long ngm_bam_sort_next(ngm_bam_sort *s, void *out, size_t out_ca
 	DeviceGuard g(s->device);
 	const int b = (int) (c & 1);
 	if (s->gathered[b] != (long long) c) { if (int rc = launch_gather(s, c)) return rc; }
-	SORT_HIP_TRY(hipEventSynchronize(s->evg[b][1]));
+	NGM_HIP_TRY(hipEventSynchronize(s->evg[b][1]));
 	float t = 0.f;
 	if (s->timed[b] != (long long) c && hipEventElapsedTime(&t, s->evg[b][0], s->evg[b][1]) == hipSuccess) { s->ms[2] += t; s->timed[b] = (long long) c; }   // (once per chunk, also when the call is repeated)
 	// the next chunk is gathered (its own stream, the other buffer) while this one is compressed
@@ -373,63 +342,63 @@ int build_index(ngm_bam_sort *s, uint64_t first) {
 		if (C.alloc(s->C.size()) || vbeg.alloc(n_coor) || vend.alloc(n_coor) || head.alloc(n_coor + 1) || before.alloc(n_coor + 1) || refs.alloc((size_t) n_ref * 6) ||
 				n_intv.alloc((size_t) n_ref + 1) || win_base.alloc((size_t) n_ref + 1) || ref_mapped.alloc((size_t) n_ref))
 			return out_of_memory(s, "the index arrays", (size_t) n_coor * 24);
-		SORT_HIP_TRY(hipMemcpyAsync(C.p, s->C.data(), s->C.size() * 8, hipMemcpyHostToDevice, s->st));
-		SORT_HIP_TRY(hipMemsetAsync(refs.p, 0, (size_t) n_ref * 48, s->st));
+		NGM_HIP_TRY(hipMemcpyAsync(C.p, s->C.data(), s->C.size() * 8, hipMemcpyHostToDevice, s->st));
+		NGM_HIP_TRY(hipMemsetAsync(refs.p, 0, (size_t) n_ref * 48, s->st));
 		bs::IndexArgs I{};
 		I.n_coor = n_coor; I.key = s->key.p; I.u = s->u.p; I.s_end = s->s_end.p; I.s_bin_flag = s->s_bin_flag.p; I.C = C.p; I.first = first; I.vbeg = vbeg.p; I.vend = vend.p; I.head = head.p;
 		I.ref_vbeg = refs.p; I.ref_vend = refs.p + n_ref; I.ref_first = refs.p + 2 * (size_t) n_ref; I.ref_last = refs.p + 3 * (size_t) n_ref; I.ref_unmapped = refs.p + 4 * (size_t) n_ref;
 		I.ref_maxend = refs.p + 5 * (size_t) n_ref;
-		SORT_HIP_TRY(hipEventRecord(s->ev0, s->st));
+		NGM_HIP_TRY(hipEventRecord(s->ev0, s->st));
 		hipLaunchKernelGGL(bs::index_records_kernel, dim3(blocks_of(n_coor)), dim3(256), 0, s->st, I);
-		SORT_HIP_TRY(hipGetLastError());
+		NGM_HIP_TRY(hipGetLastError());
 		size_t tb = 0;
-		SORT_HIP_TRY(rocprim::exclusive_scan(nullptr, tb, head.p, before.p, 0u, (size_t) n_coor + 1, rocprim::plus<uint32_t>(), s->st));
+		NGM_HIP_TRY(rocprim::exclusive_scan(nullptr, tb, head.p, before.p, 0u, (size_t) n_coor + 1, rocprim::plus<uint32_t>(), s->st));
 		if (tmp.alloc(tb + 16)) return out_of_memory(s, "a scan", tb);
-		SORT_HIP_TRY(rocprim::exclusive_scan(tmp.p, tb, head.p, before.p, 0u, (size_t) n_coor + 1, rocprim::plus<uint32_t>(), s->st));
+		NGM_HIP_TRY(rocprim::exclusive_scan(tmp.p, tb, head.p, before.p, 0u, (size_t) n_coor + 1, rocprim::plus<uint32_t>(), s->st));
 		uint32_t n_chunks = 0;
-		SORT_HIP_TRY(hipMemcpyAsync(&n_chunks, before.p + n_coor, 4, hipMemcpyDeviceToHost, s->st));
+		NGM_HIP_TRY(hipMemcpyAsync(&n_chunks, before.p + n_coor, 4, hipMemcpyDeviceToHost, s->st));
 		// the windows of the references
 		hipLaunchKernelGGL(bs::ref_windows_kernel, dim3(blocks_of((uint64_t) n_ref + 1)), dim3(256), 0, s->st, n_ref, (const unsigned long long *) I.ref_maxend, (const unsigned long long *) I.ref_first,
 				(const unsigned long long *) I.ref_last, (const unsigned long long *) I.ref_unmapped, n_intv.p, ref_mapped.p);
-		SORT_HIP_TRY(hipGetLastError());
-		SORT_HIP_TRY(rocprim::exclusive_scan(nullptr, tb, n_intv.p, win_base.p, (uint64_t) 0, (size_t) n_ref + 1, rocprim::plus<uint64_t>(), s->st));
+		NGM_HIP_TRY(hipGetLastError());
+		NGM_HIP_TRY(rocprim::exclusive_scan(nullptr, tb, n_intv.p, win_base.p, (uint64_t) 0, (size_t) n_ref + 1, rocprim::plus<uint64_t>(), s->st));
 		if (tb + 16 > tmp.n && tmp.alloc(tb + 16)) return out_of_memory(s, "a scan", tb);
-		SORT_HIP_TRY(rocprim::exclusive_scan(tmp.p, tb, n_intv.p, win_base.p, (uint64_t) 0, (size_t) n_ref + 1, rocprim::plus<uint64_t>(), s->st));
-		SORT_HIP_TRY(hipMemcpyAsync(h_win_base.data(), win_base.p, ((size_t) n_ref + 1) * 8, hipMemcpyDeviceToHost, s->st));
-		SORT_HIP_TRY(hipStreamSynchronize(s->st));
+		NGM_HIP_TRY(rocprim::exclusive_scan(tmp.p, tb, n_intv.p, win_base.p, (uint64_t) 0, (size_t) n_ref + 1, rocprim::plus<uint64_t>(), s->st));
+		NGM_HIP_TRY(hipMemcpyAsync(h_win_base.data(), win_base.p, ((size_t) n_ref + 1) * 8, hipMemcpyDeviceToHost, s->st));
+		NGM_HIP_TRY(hipStreamSynchronize(s->st));
 		const uint64_t n_win = h_win_base[n_ref];
 		// the chunks, stably sorted by (reference, bin)
 		if (ckey.alloc(n_chunks) || ckey_s.alloc(n_chunks) || cval.alloc(n_chunks) || cval_s.alloc(n_chunks) || cbeg.alloc(n_chunks) || cend.alloc(n_chunks) || cbeg_s.alloc(n_chunks) ||
 				cend_s.alloc(n_chunks) || rev.alloc(n_win) || rev_s.alloc(n_win))
 			return out_of_memory(s, "the index arrays", (size_t) n_chunks * 56 + (size_t) n_win * 16);
 		hipLaunchKernelGGL(bs::chunks_kernel, dim3(blocks_of(n_coor)), dim3(256), 0, s->st, I, (const uint32_t *) before.p, ckey.p, cval.p, cbeg.p, cend.p);
-		SORT_HIP_TRY(hipGetLastError());
-		SORT_HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, ckey.p, ckey_s.p, cval.p, cval_s.p, (size_t) n_chunks, 0, 64, s->st));
+		NGM_HIP_TRY(hipGetLastError());
+		NGM_HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, ckey.p, ckey_s.p, cval.p, cval_s.p, (size_t) n_chunks, 0, 64, s->st));
 		if (tb + 16 > tmp.n && tmp.alloc(tb + 16)) return out_of_memory(s, "the sort of the chunks", tb);
-		SORT_HIP_TRY(rocprim::radix_sort_pairs(tmp.p, tb, ckey.p, ckey_s.p, cval.p, cval_s.p, (size_t) n_chunks, 0, 64, s->st));
+		NGM_HIP_TRY(rocprim::radix_sort_pairs(tmp.p, tb, ckey.p, ckey_s.p, cval.p, cval_s.p, (size_t) n_chunks, 0, 64, s->st));
 		hipLaunchKernelGGL(bs::chunks_permute_kernel, dim3(blocks_of(n_chunks)), dim3(256), 0, s->st, (const uint32_t *) cval_s.p, (uint64_t) n_chunks, (const uint64_t *) cbeg.p,
 				(const uint64_t *) cend.p, cbeg_s.p, cend_s.p);
-		SORT_HIP_TRY(hipGetLastError());
+		NGM_HIP_TRY(hipGetLastError());
 		// the linear index
-		SORT_HIP_TRY(hipMemsetAsync(rev.p, 0xFF, n_win * 8, s->st));
+		NGM_HIP_TRY(hipMemsetAsync(rev.p, 0xFF, n_win * 8, s->st));
 		hipLaunchKernelGGL(bs::windows_kernel, dim3(blocks_of(n_coor)), dim3(256), 0, s->st, I, (const uint64_t *) win_base.p, n_win, rev.p);
-		SORT_HIP_TRY(hipGetLastError());
-		SORT_HIP_TRY(rocprim::inclusive_scan(nullptr, tb, rev.p, rev_s.p, (size_t) n_win, rocprim::minimum<unsigned long long>(), s->st));
+		NGM_HIP_TRY(hipGetLastError());
+		NGM_HIP_TRY(rocprim::inclusive_scan(nullptr, tb, rev.p, rev_s.p, (size_t) n_win, rocprim::minimum<unsigned long long>(), s->st));
 		if (tb + 16 > tmp.n && tmp.alloc(tb + 16)) return out_of_memory(s, "a scan", tb);
-		SORT_HIP_TRY(rocprim::inclusive_scan(tmp.p, tb, rev.p, rev_s.p, (size_t) n_win, rocprim::minimum<unsigned long long>(), s->st));
+		NGM_HIP_TRY(rocprim::inclusive_scan(tmp.p, tb, rev.p, rev_s.p, (size_t) n_win, rocprim::minimum<unsigned long long>(), s->st));
 		hipLaunchKernelGGL(bs::reverse_kernel, dim3(blocks_of(n_win)), dim3(256), 0, s->st, (const uint64_t *) rev_s.p, n_win, (uint64_t *) rev.p);
-		SORT_HIP_TRY(hipGetLastError());
-		SORT_HIP_TRY(hipEventRecord(s->ev1, s->st));
+		NGM_HIP_TRY(hipGetLastError());
+		NGM_HIP_TRY(hipEventRecord(s->ev1, s->st));
 		h_ioff.resize(n_win); h_ckey.resize(n_chunks); h_cbeg.resize(n_chunks); h_cend.resize(n_chunks);
-		SORT_HIP_TRY(hipMemcpyAsync(h_ioff.data(), rev.p, n_win * 8, hipMemcpyDeviceToHost, s->st));
-		SORT_HIP_TRY(hipMemcpyAsync(h_ckey.data(), ckey_s.p, (size_t) n_chunks * 8, hipMemcpyDeviceToHost, s->st));
-		SORT_HIP_TRY(hipMemcpyAsync(h_cbeg.data(), cbeg_s.p, (size_t) n_chunks * 8, hipMemcpyDeviceToHost, s->st));
-		SORT_HIP_TRY(hipMemcpyAsync(h_cend.data(), cend_s.p, (size_t) n_chunks * 8, hipMemcpyDeviceToHost, s->st));
-		SORT_HIP_TRY(hipMemcpyAsync(h_ref.data(), I.ref_vbeg, (size_t) n_ref * 8, hipMemcpyDeviceToHost, s->st));
-		SORT_HIP_TRY(hipMemcpyAsync(h_ref.data() + n_ref, I.ref_vend, (size_t) n_ref * 8, hipMemcpyDeviceToHost, s->st));
-		SORT_HIP_TRY(hipMemcpyAsync(h_ref.data() + 2 * (size_t) n_ref, ref_mapped.p, (size_t) n_ref * 8, hipMemcpyDeviceToHost, s->st));
-		SORT_HIP_TRY(hipMemcpyAsync(h_ref.data() + 3 * (size_t) n_ref, I.ref_unmapped, (size_t) n_ref * 8, hipMemcpyDeviceToHost, s->st));
-		SORT_HIP_TRY(hipStreamSynchronize(s->st));
+		NGM_HIP_TRY(hipMemcpyAsync(h_ioff.data(), rev.p, n_win * 8, hipMemcpyDeviceToHost, s->st));
+		NGM_HIP_TRY(hipMemcpyAsync(h_ckey.data(), ckey_s.p, (size_t) n_chunks * 8, hipMemcpyDeviceToHost, s->st));
+		NGM_HIP_TRY(hipMemcpyAsync(h_cbeg.data(), cbeg_s.p, (size_t) n_chunks * 8, hipMemcpyDeviceToHost, s->st));
+		NGM_HIP_TRY(hipMemcpyAsync(h_cend.data(), cend_s.p, (size_t) n_chunks * 8, hipMemcpyDeviceToHost, s->st));
+		NGM_HIP_TRY(hipMemcpyAsync(h_ref.data(), I.ref_vbeg, (size_t) n_ref * 8, hipMemcpyDeviceToHost, s->st));
+		NGM_HIP_TRY(hipMemcpyAsync(h_ref.data() + n_ref, I.ref_vend, (size_t) n_ref * 8, hipMemcpyDeviceToHost, s->st));
+		NGM_HIP_TRY(hipMemcpyAsync(h_ref.data() + 2 * (size_t) n_ref, ref_mapped.p, (size_t) n_ref * 8, hipMemcpyDeviceToHost, s->st));
+		NGM_HIP_TRY(hipMemcpyAsync(h_ref.data() + 3 * (size_t) n_ref, I.ref_unmapped, (size_t) n_ref * 8, hipMemcpyDeviceToHost, s->st));
+		NGM_HIP_TRY(hipStreamSynchronize(s->st));
 		(void) hipEventElapsedTime(&s->ms[4], s->ev0, s->ev1);
 		A.n_chunks = n_chunks;
 	}

@@ -16,45 +16,16 @@
 #include "../../include/ngm_pipeline.h"
 #define NGM_COV_FINISH_KERNELS
 #include "coverage_device.h"
+#include "device_util.h"
 #include "refindex.h"
 
 namespace cv = ngm::cov;
 
-#define COV_HIP_TRY(expr)                                                                       \
-	do {                                                                                        \
-		hipError_t e_ = (expr);                                                                 \
-		if (e_ != hipSuccess) {                                                                 \
-			ngm::pipeline_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-			return -5;                                                                          \
-		}                                                                                       \
-	} while (0)
+using ngm::Buf;
+using ngm::DeviceGuard;
+using ngm::blocks_of;
 
 namespace {
-template <typename T>
-struct Buf {
-	T *p = nullptr;
-	size_t n = 0;
-	int alloc(size_t count) {
-		release();
-		if (hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) { (void) hipGetLastError(); p = nullptr; return -1; }
-		n = count;
-		return 0;
-	}
-	int grow(size_t count) { return count <= n ? 0 : alloc(count + count / 4 + 64); }
-	void release() { if (p) (void) hipFree(p); p = nullptr; n = 0; }
-	~Buf() { release(); }
-	Buf() = default;
-	Buf(const Buf &) = delete;
-	Buf &operator=(const Buf &) = delete;
-};
-
-struct DeviceGuard {   // a call from a thread that works on another GPU leaves that thread's device as it was
-	int prev = -1;
-	explicit DeviceGuard(int device) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; if (prev != device) (void) hipSetDevice(device); else prev = -1; }
-	~DeviceGuard() { if (prev >= 0) (void) hipSetDevice(prev); }
-};
-
-unsigned blocks_of(uint64_t n) { return (unsigned) ((n + 255) / 256); }
 constexpr size_t kDefaultChunk = (size_t) 1 << 25;   // slots scanned at a time: 128 MiB of counters, 160 MiB of temporaries
 constexpr size_t kMaxChunk = (size_t) 1 << 30;       // (the heads' chunk offsets are 32-bit)
 }  // namespace
@@ -141,16 +112,16 @@ extern "C" int ngm_coverage_add(ngm_coverage *c, const int32_t *ref_id, const in
 	DeviceGuard g(c->device);
 	const size_t t0 = cigar_off[0], tn = cigar_off[n] - t0;
 	if (c->a_ref.grow(n) || c->a_pos.grow(n) || c->a_off.grow(n + 1) || c->a_text.grow(tn + 1)) { ngm::pipeline_set_error("out of device memory for %zu alignments", n); return -12; }
-	COV_HIP_TRY(hipMemcpyAsync(c->a_ref.p, ref_id, n * 4, hipMemcpyHostToDevice, c->st));
-	COV_HIP_TRY(hipMemcpyAsync(c->a_pos.p, pos0, n * 4, hipMemcpyHostToDevice, c->st));
-	COV_HIP_TRY(hipMemcpyAsync(c->a_off.p, cigar_off, (n + 1) * 4, hipMemcpyHostToDevice, c->st));
-	if (tn) COV_HIP_TRY(hipMemcpyAsync(c->a_text.p, cigar_text + t0, tn, hipMemcpyHostToDevice, c->st));
+	NGM_HIP_TRY(hipMemcpyAsync(c->a_ref.p, ref_id, n * 4, hipMemcpyHostToDevice, c->st));
+	NGM_HIP_TRY(hipMemcpyAsync(c->a_pos.p, pos0, n * 4, hipMemcpyHostToDevice, c->st));
+	NGM_HIP_TRY(hipMemcpyAsync(c->a_off.p, cigar_off, (n + 1) * 4, hipMemcpyHostToDevice, c->st));
+	if (tn) NGM_HIP_TRY(hipMemcpyAsync(c->a_text.p, cigar_text + t0, tn, hipMemcpyHostToDevice, c->st));
 	cv::CovArrays S{c->a_ref.p, c->a_pos.p, c->a_off.p, c->a_text.p - t0, (uint32_t) n};   // (the offsets count from the caller's first byte)
-	COV_HIP_TRY(hipEventRecord(c->ev[0], c->st));
+	NGM_HIP_TRY(hipEventRecord(c->ev[0], c->st));
 	hipLaunchKernelGGL(cv::cov_add_kernel<cv::CovArrays>, dim3(blocks_of(n)), dim3(256), 0, c->st, S, c->counters.p, (const uint64_t *) c->d_off.p, c->n_ref, c->d_tot.p);
-	COV_HIP_TRY(hipGetLastError());
-	COV_HIP_TRY(hipEventRecord(c->ev[1], c->st));
-	COV_HIP_TRY(hipStreamSynchronize(c->st));
+	NGM_HIP_TRY(hipGetLastError());
+	NGM_HIP_TRY(hipEventRecord(c->ev[1], c->st));
+	NGM_HIP_TRY(hipStreamSynchronize(c->st));
 	float t = 0.f;
 	if (hipEventElapsedTime(&t, c->ev[0], c->ev[1]) == hipSuccess) c->ms[0] += t;
 	return 0;
@@ -177,12 +148,12 @@ extern "C" int ngm_coverage_finish(ngm_coverage *c) {
 	if (c->finished) { ngm::pipeline_set_error("ngm_coverage_finish: called twice"); return -22; }
 	c->finished = true;
 	DeviceGuard g(c->device);
-	COV_HIP_TRY(hipDeviceSynchronize());   // (the mappers' streams on this device have added their last batch)
+	NGM_HIP_TRY(hipDeviceSynchronize());   // (the mappers' streams on this device have added their last batch)
 	c->a_ref.release(); c->a_pos.release(); c->a_off.release(); c->a_text.release();
 	const size_t n = (size_t) std::min<uint64_t>(c->chunk, c->off[c->n_ref]);
 	size_t tb = 0, tb2 = 0;
-	COV_HIP_TRY(rocprim::inclusive_scan(nullptr, tb, (int32_t *) nullptr, (int32_t *) nullptr, (int32_t) 0, n, rocprim::plus<int32_t>(), c->st));
-	COV_HIP_TRY(rocprim::select(nullptr, tb2, rocprim::counting_iterator<uint32_t>(0), (uint8_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr, n, c->st));
+	NGM_HIP_TRY(rocprim::inclusive_scan(nullptr, tb, (int32_t *) nullptr, (int32_t *) nullptr, (int32_t) 0, n, rocprim::plus<int32_t>(), c->st));
+	NGM_HIP_TRY(rocprim::select(nullptr, tb2, rocprim::counting_iterator<uint32_t>(0), (uint8_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr, n, c->st));
 	if (c->flag.alloc(n) || c->head.alloc(n) || c->tmp.alloc(std::max(tb, tb2) + 16)) { ngm::pipeline_set_error("out of device memory for the coverage scan (%zu slots per chunk)", n); return -12; }
 	return 0;
 }
@@ -194,19 +165,19 @@ int scan_chunk(ngm_coverage *c) {
 	const size_t n = (size_t) std::min<uint64_t>(c->chunk, c->off[c->n_ref] - s0);
 	int32_t *depth = c->counters.p + s0;
 	size_t tb = c->tmp.n;
-	COV_HIP_TRY(hipEventRecord(c->ev[0], c->st));
-	COV_HIP_TRY(rocprim::inclusive_scan(c->tmp.p, tb, depth, depth, c->open_depth, n, rocprim::plus<int32_t>(), c->st));   // (in place, the depth in front carried in)
-	COV_HIP_TRY(hipEventRecord(c->ev[1], c->st));
+	NGM_HIP_TRY(hipEventRecord(c->ev[0], c->st));
+	NGM_HIP_TRY(rocprim::inclusive_scan(c->tmp.p, tb, depth, depth, c->open_depth, n, rocprim::plus<int32_t>(), c->st));   // (in place, the depth in front carried in)
+	NGM_HIP_TRY(hipEventRecord(c->ev[1], c->st));
 	hipLaunchKernelGGL(cv::cov_heads_kernel, dim3(blocks_of(n)), dim3(256), 0, c->st, (const int32_t *) depth, (uint32_t) n, c->open_depth, c->flag.p);
-	COV_HIP_TRY(hipGetLastError());
+	NGM_HIP_TRY(hipGetLastError());
 	tb = c->tmp.n;
-	COV_HIP_TRY(rocprim::select(c->tmp.p, tb, rocprim::counting_iterator<uint32_t>(0), c->flag.p, c->head.p, c->d_m.p, n, c->st));
-	COV_HIP_TRY(hipEventRecord(c->ev[2], c->st));
+	NGM_HIP_TRY(rocprim::select(c->tmp.p, tb, rocprim::counting_iterator<uint32_t>(0), c->flag.p, c->head.p, c->d_m.p, n, c->st));
+	NGM_HIP_TRY(hipEventRecord(c->ev[2], c->st));
 	uint32_t m = 0;
 	int32_t last_depth = 0;
-	COV_HIP_TRY(hipMemcpyAsync(&m, c->d_m.p, 4, hipMemcpyDeviceToHost, c->st));
-	COV_HIP_TRY(hipMemcpyAsync(&last_depth, depth + n - 1, 4, hipMemcpyDeviceToHost, c->st));
-	COV_HIP_TRY(hipStreamSynchronize(c->st));
+	NGM_HIP_TRY(hipMemcpyAsync(&m, c->d_m.p, 4, hipMemcpyDeviceToHost, c->st));
+	NGM_HIP_TRY(hipMemcpyAsync(&last_depth, depth + n - 1, 4, hipMemcpyDeviceToHost, c->st));
+	NGM_HIP_TRY(hipStreamSynchronize(c->st));
 	float t = 0.f;
 	if (hipEventElapsedTime(&t, c->ev[0], c->ev[1]) == hipSuccess) c->ms[1] += t;
 	if (hipEventElapsedTime(&t, c->ev[1], c->ev[2]) == hipSuccess) c->ms[2] += t;
@@ -218,30 +189,30 @@ int scan_chunk(ngm_coverage *c) {
 	cv::TextArgs T{};
 	T.depth = depth; T.head = c->head.p; T.m = m; T.s0 = s0; T.open_off = c->open_off; T.open_depth = c->open_depth; T.off = c->d_off.p; T.n_ref = c->n_ref;
 	T.names = c->d_names.p; T.name_off = c->d_name_off.p; T.len = c->len.p; T.line_off = c->line_off.p; T.totals = c->d_tot.p + 1;
-	COV_HIP_TRY(hipEventRecord(c->ev[3], c->st));
-	COV_HIP_TRY(hipMemsetAsync(c->len.p + m, 0, 4, c->st));
+	NGM_HIP_TRY(hipEventRecord(c->ev[3], c->st));
+	NGM_HIP_TRY(hipMemsetAsync(c->len.p + m, 0, 4, c->st));
 	hipLaunchKernelGGL(cv::cov_lengths_kernel, dim3(blocks_of(m)), dim3(256), 0, c->st, T);
-	COV_HIP_TRY(hipGetLastError());
+	NGM_HIP_TRY(hipGetLastError());
 	auto widen = rocprim::make_transform_iterator(c->len.p, [] __host__ __device__ (uint32_t x) { return (uint64_t) x; });
 	size_t sb = 0;
-	COV_HIP_TRY(rocprim::exclusive_scan(nullptr, sb, widen, c->line_off.p, (uint64_t) 0, (size_t) m + 1, rocprim::plus<uint64_t>(), c->st));
+	NGM_HIP_TRY(rocprim::exclusive_scan(nullptr, sb, widen, c->line_off.p, (uint64_t) 0, (size_t) m + 1, rocprim::plus<uint64_t>(), c->st));
 	if (c->tmp.grow(sb + 16)) { ngm::pipeline_set_error("out of device memory for a scan"); return -12; }
-	COV_HIP_TRY(rocprim::exclusive_scan(c->tmp.p, sb, widen, c->line_off.p, (uint64_t) 0, (size_t) m + 1, rocprim::plus<uint64_t>(), c->st));
+	NGM_HIP_TRY(rocprim::exclusive_scan(c->tmp.p, sb, widen, c->line_off.p, (uint64_t) 0, (size_t) m + 1, rocprim::plus<uint64_t>(), c->st));
 	uint64_t total = 0;
 	uint32_t last_head = 0;
-	COV_HIP_TRY(hipMemcpyAsync(&total, c->line_off.p + m, 8, hipMemcpyDeviceToHost, c->st));
-	COV_HIP_TRY(hipMemcpyAsync(&last_head, c->head.p + (m - 1), 4, hipMemcpyDeviceToHost, c->st));
-	COV_HIP_TRY(hipStreamSynchronize(c->st));
+	NGM_HIP_TRY(hipMemcpyAsync(&total, c->line_off.p + m, 8, hipMemcpyDeviceToHost, c->st));
+	NGM_HIP_TRY(hipMemcpyAsync(&last_head, c->head.p + (m - 1), 4, hipMemcpyDeviceToHost, c->st));
+	NGM_HIP_TRY(hipStreamSynchronize(c->st));
 	if (total) {
 		if (c->d_text.grow((size_t) total)) { ngm::pipeline_set_error("out of device memory for %llu bytes of lines", (unsigned long long) total); return -12; }
 		T.out = c->d_text.p;
 		hipLaunchKernelGGL(cv::cov_write_kernel, dim3(blocks_of(m)), dim3(256), 0, c->st, T);
-		COV_HIP_TRY(hipGetLastError());
+		NGM_HIP_TRY(hipGetLastError());
 	}
-	COV_HIP_TRY(hipEventRecord(c->ev[4], c->st));
+	NGM_HIP_TRY(hipEventRecord(c->ev[4], c->st));
 	c->text.resize((size_t) total);
-	if (total) COV_HIP_TRY(hipMemcpyAsync(c->text.data(), c->d_text.p, (size_t) total, hipMemcpyDeviceToHost, c->st));
-	COV_HIP_TRY(hipStreamSynchronize(c->st));
+	if (total) NGM_HIP_TRY(hipMemcpyAsync(c->text.data(), c->d_text.p, (size_t) total, hipMemcpyDeviceToHost, c->st));
+	NGM_HIP_TRY(hipStreamSynchronize(c->st));
 	if (hipEventElapsedTime(&t, c->ev[3], c->ev[4]) == hipSuccess) c->ms[3] += t;
 	c->open_off = s0 + last_head;
 	c->open_depth = last_depth;

@@ -1,0 +1,50 @@
+// device_util.h -- what the host sides of the run-long side outputs (bam_sort.cpp, coverage.cpp, snp.cpp) share: device memory that frees
+// itself, a guard for the calling thread's device, the launch grid of the 256-thread kernels, and the HIP error check of the C ABI.
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+
+#include <hip/hip_runtime.h>
+
+#include "refindex.h"   // ngm::pipeline_set_error
+
+// a failed HIP call: its text becomes ngm_pipeline_last_error() and the calling function returns -5
+#define NGM_HIP_TRY(expr)                                                                       \
+	do {                                                                                        \
+		hipError_t e_ = (expr);                                                                 \
+		if (e_ != hipSuccess) {                                                                 \
+			ngm::pipeline_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+			return -5;                                                                          \
+		}                                                                                       \
+	} while (0)
+
+namespace ngm {
+
+template <typename T>
+struct Buf {   // device memory: alloc() of exactly the size asked for, grow() with a quarter to spare when it has to
+	T *p = nullptr;
+	size_t n = 0;
+	int alloc(size_t count) {
+		release();
+		if (hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) { (void) hipGetLastError(); p = nullptr; return -1; }
+		n = count;
+		return 0;
+	}
+	int grow(size_t count) { return count <= n ? 0 : alloc(count + count / 4 + 64); }
+	void release() { if (p) (void) hipFree(p); p = nullptr; n = 0; }
+	~Buf() { release(); }
+	Buf() = default;
+	Buf(const Buf &) = delete;
+	Buf &operator=(const Buf &) = delete;
+};
+
+struct DeviceGuard {   // a call from a thread that works on another GPU leaves that thread's device as it was
+	int prev = -1;
+	explicit DeviceGuard(int device) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; if (prev != device) (void) hipSetDevice(device); else prev = -1; }
+	~DeviceGuard() { if (prev >= 0) (void) hipSetDevice(prev); }
+};
+
+inline unsigned blocks_of(uint64_t n) { return (unsigned) ((n + 255) / 256); }
+
+}  // namespace ngm

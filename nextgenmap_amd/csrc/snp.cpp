@@ -16,46 +16,17 @@
 #include "../../include/ngm_pipeline.h"
 #define NGM_SNP_FINISH_KERNELS
 #include "snp_device.h"
+#include "device_util.h"
 #include "refindex.h"
 
 namespace cv = ngm::cov;
 namespace sn = ngm::snp;
 
-#define SNP_HIP_TRY(expr)                                                                       \
-	do {                                                                                        \
-		hipError_t e_ = (expr);                                                                 \
-		if (e_ != hipSuccess) {                                                                 \
-			ngm::pipeline_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-			return -5;                                                                          \
-		}                                                                                       \
-	} while (0)
+using ngm::Buf;
+using ngm::DeviceGuard;
+using ngm::blocks_of;
 
 namespace {
-template <typename T>
-struct Buf {
-	T *p = nullptr;
-	size_t n = 0;
-	int alloc(size_t count) {
-		release();
-		if (hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) { (void) hipGetLastError(); p = nullptr; return -1; }
-		n = count;
-		return 0;
-	}
-	int grow(size_t count) { return count <= n ? 0 : alloc(count + count / 4 + 64); }
-	void release() { if (p) (void) hipFree(p); p = nullptr; n = 0; }
-	~Buf() { release(); }
-	Buf() = default;
-	Buf(const Buf &) = delete;
-	Buf &operator=(const Buf &) = delete;
-};
-
-struct DeviceGuard {   // a call from a thread that works on another GPU leaves that thread's device as it was
-	int prev = -1;
-	explicit DeviceGuard(int device) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; if (prev != device) (void) hipSetDevice(device); else prev = -1; }
-	~DeviceGuard() { if (prev >= 0) (void) hipSetDevice(prev); }
-};
-
-unsigned blocks_of(uint64_t n) { return (unsigned) ((n + 255) / 256); }
 constexpr size_t kDefaultChunk = (size_t) 1 << 25;   // slots scanned at a time
 constexpr size_t kMaxChunk = (size_t) 1 << 30;       // (the calls' chunk offsets are 32-bit)
 }  // namespace
@@ -203,20 +174,20 @@ extern "C" int ngm_snp_add(ngm_snp *c, const int32_t *ref_id, const int32_t *pos
 		ngm::pipeline_set_error("out of device memory for %zu alignments", n);
 		return -12;
 	}
-	SNP_HIP_TRY(hipMemcpyAsync(c->a_ref.p, ref_id, n * 4, hipMemcpyHostToDevice, c->st));
-	SNP_HIP_TRY(hipMemcpyAsync(c->a_pos.p, pos0, n * 4, hipMemcpyHostToDevice, c->st));
-	SNP_HIP_TRY(hipMemcpyAsync(c->a_off.p, cigar_off, (n + 1) * 4, hipMemcpyHostToDevice, c->st));
-	SNP_HIP_TRY(hipMemcpyAsync(c->a_soff.p, seq_off, (n + 1) * 4, hipMemcpyHostToDevice, c->st));
-	if (tn) SNP_HIP_TRY(hipMemcpyAsync(c->a_text.p, cigar_text + t0, tn, hipMemcpyHostToDevice, c->st));
-	if (sn_bytes) SNP_HIP_TRY(hipMemcpyAsync(c->a_seq.p, seq_text + s0, sn_bytes, hipMemcpyHostToDevice, c->st));
-	if (sn_bytes && qual_text) SNP_HIP_TRY(hipMemcpyAsync(c->a_qual.p, qual_text + s0, sn_bytes, hipMemcpyHostToDevice, c->st));
+	NGM_HIP_TRY(hipMemcpyAsync(c->a_ref.p, ref_id, n * 4, hipMemcpyHostToDevice, c->st));
+	NGM_HIP_TRY(hipMemcpyAsync(c->a_pos.p, pos0, n * 4, hipMemcpyHostToDevice, c->st));
+	NGM_HIP_TRY(hipMemcpyAsync(c->a_off.p, cigar_off, (n + 1) * 4, hipMemcpyHostToDevice, c->st));
+	NGM_HIP_TRY(hipMemcpyAsync(c->a_soff.p, seq_off, (n + 1) * 4, hipMemcpyHostToDevice, c->st));
+	if (tn) NGM_HIP_TRY(hipMemcpyAsync(c->a_text.p, cigar_text + t0, tn, hipMemcpyHostToDevice, c->st));
+	if (sn_bytes) NGM_HIP_TRY(hipMemcpyAsync(c->a_seq.p, seq_text + s0, sn_bytes, hipMemcpyHostToDevice, c->st));
+	if (sn_bytes && qual_text) NGM_HIP_TRY(hipMemcpyAsync(c->a_qual.p, qual_text + s0, sn_bytes, hipMemcpyHostToDevice, c->st));
 	// (the offsets count from the caller's first byte)
 	sn::SnpArrays S{c->a_ref.p, c->a_pos.p, c->a_off.p, c->a_text.p - t0, c->a_soff.p, c->a_seq.p - s0, qual_text ? c->a_qual.p - s0 : nullptr, (uint32_t) n};
-	SNP_HIP_TRY(hipEventRecord(c->ev[0], c->st));
+	NGM_HIP_TRY(hipEventRecord(c->ev[0], c->st));
 	hipLaunchKernelGGL(sn::snp_add_kernel<sn::SnpArrays>, dim3(blocks_of(n)), dim3(256), 0, c->st, S, target_of(c));
-	SNP_HIP_TRY(hipGetLastError());
-	SNP_HIP_TRY(hipEventRecord(c->ev[1], c->st));
-	SNP_HIP_TRY(hipStreamSynchronize(c->st));
+	NGM_HIP_TRY(hipGetLastError());
+	NGM_HIP_TRY(hipEventRecord(c->ev[1], c->st));
+	NGM_HIP_TRY(hipStreamSynchronize(c->st));
 	float t = 0.f;
 	if (hipEventElapsedTime(&t, c->ev[0], c->ev[1]) == hipSuccess) c->ms[0] += t;
 	return 0;
@@ -243,12 +214,12 @@ extern "C" int ngm_snp_finish(ngm_snp *c) {
 	if (c->finished) { ngm::pipeline_set_error("ngm_snp_finish: called twice"); return -22; }
 	c->finished = true;
 	DeviceGuard g(c->device);
-	SNP_HIP_TRY(hipDeviceSynchronize());   // (the mappers' streams on this device have added their last batch)
+	NGM_HIP_TRY(hipDeviceSynchronize());   // (the mappers' streams on this device have added their last batch)
 	c->a_ref.release(); c->a_pos.release(); c->a_off.release(); c->a_soff.release(); c->a_text.release(); c->a_seq.release(); c->a_qual.release();
 	const size_t n = (size_t) std::min<uint64_t>(c->chunk, c->off[c->n_ref]);
 	size_t tb = 0, tb2 = 0;
-	SNP_HIP_TRY(rocprim::inclusive_scan(nullptr, tb, (int32_t *) nullptr, (int32_t *) nullptr, (int32_t) 0, n, rocprim::plus<int32_t>(), c->st));
-	SNP_HIP_TRY(rocprim::select(nullptr, tb2, rocprim::counting_iterator<uint32_t>(0), (uint8_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr, n, c->st));
+	NGM_HIP_TRY(rocprim::inclusive_scan(nullptr, tb, (int32_t *) nullptr, (int32_t *) nullptr, (int32_t) 0, n, rocprim::plus<int32_t>(), c->st));
+	NGM_HIP_TRY(rocprim::select(nullptr, tb2, rocprim::counting_iterator<uint32_t>(0), (uint8_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr, n, c->st));
 	if (c->flag.alloc(n) || c->idx.alloc(n) || c->tmp.alloc(std::max(tb, tb2) + 16)) { ngm::pipeline_set_error("out of device memory for the SNP scan (%zu slots per chunk)", n); return -12; }
 	return 0;
 }
@@ -260,22 +231,22 @@ int scan_chunk(ngm_snp *c) {
 	const size_t n = (size_t) std::min<uint64_t>(c->chunk, c->off[c->n_ref] - s0);
 	int32_t *depth = c->diff.p + s0;
 	size_t tb = c->tmp.n;
-	SNP_HIP_TRY(hipEventRecord(c->ev[0], c->st));
-	SNP_HIP_TRY(rocprim::inclusive_scan(c->tmp.p, tb, depth, depth, c->carry, n, rocprim::plus<int32_t>(), c->st));   // (in place, the depth in front carried in)
-	SNP_HIP_TRY(hipEventRecord(c->ev[1], c->st));
+	NGM_HIP_TRY(hipEventRecord(c->ev[0], c->st));
+	NGM_HIP_TRY(rocprim::inclusive_scan(c->tmp.p, tb, depth, depth, c->carry, n, rocprim::plus<int32_t>(), c->st));   // (in place, the depth in front carried in)
+	NGM_HIP_TRY(hipEventRecord(c->ev[1], c->st));
 	sn::ChunkArgs T{};
 	T.depth = depth; T.alt = c->alt.p + 3u * s0; T.n = (uint32_t) n; T.s0 = s0; T.off = c->d_off.p; T.n_ref = c->n_ref; T.genome = c->genome; T.start = c->d_start.p;
 	T.rule = c->rule; T.flag = c->flag.p; T.idx = c->idx.p; T.names = c->d_names.p; T.name_off = c->d_name_off.p; T.totals = c->d_tot.p + 2;
 	hipLaunchKernelGGL(sn::snp_flag_kernel, dim3(blocks_of(n)), dim3(256), 0, c->st, T);
-	SNP_HIP_TRY(hipGetLastError());
+	NGM_HIP_TRY(hipGetLastError());
 	tb = c->tmp.n;
-	SNP_HIP_TRY(rocprim::select(c->tmp.p, tb, rocprim::counting_iterator<uint32_t>(0), c->flag.p, c->idx.p, c->d_m.p, n, c->st));
-	SNP_HIP_TRY(hipEventRecord(c->ev[2], c->st));
+	NGM_HIP_TRY(rocprim::select(c->tmp.p, tb, rocprim::counting_iterator<uint32_t>(0), c->flag.p, c->idx.p, c->d_m.p, n, c->st));
+	NGM_HIP_TRY(hipEventRecord(c->ev[2], c->st));
 	uint32_t m = 0;
 	int32_t last_depth = 0;
-	SNP_HIP_TRY(hipMemcpyAsync(&m, c->d_m.p, 4, hipMemcpyDeviceToHost, c->st));
-	SNP_HIP_TRY(hipMemcpyAsync(&last_depth, depth + n - 1, 4, hipMemcpyDeviceToHost, c->st));
-	SNP_HIP_TRY(hipStreamSynchronize(c->st));
+	NGM_HIP_TRY(hipMemcpyAsync(&m, c->d_m.p, 4, hipMemcpyDeviceToHost, c->st));
+	NGM_HIP_TRY(hipMemcpyAsync(&last_depth, depth + n - 1, 4, hipMemcpyDeviceToHost, c->st));
+	NGM_HIP_TRY(hipStreamSynchronize(c->st));
 	float t = 0.f;
 	if (hipEventElapsedTime(&t, c->ev[0], c->ev[1]) == hipSuccess) c->ms[1] += t;
 	if (hipEventElapsedTime(&t, c->ev[1], c->ev[2]) == hipSuccess) c->ms[2] += t;
@@ -286,28 +257,28 @@ int scan_chunk(ngm_snp *c) {
 	if (m == 0) return 0;
 	if (c->len.grow((size_t) m + 1) || c->line_off.grow((size_t) m + 1)) { ngm::pipeline_set_error("out of device memory for the lines of %u calls", m); return -12; }
 	T.m = m; T.len = c->len.p; T.line_off = c->line_off.p;
-	SNP_HIP_TRY(hipEventRecord(c->ev[3], c->st));
-	SNP_HIP_TRY(hipMemsetAsync(c->len.p + m, 0, 4, c->st));
+	NGM_HIP_TRY(hipEventRecord(c->ev[3], c->st));
+	NGM_HIP_TRY(hipMemsetAsync(c->len.p + m, 0, 4, c->st));
 	hipLaunchKernelGGL(sn::snp_lengths_kernel, dim3(blocks_of(m)), dim3(256), 0, c->st, T);
-	SNP_HIP_TRY(hipGetLastError());
+	NGM_HIP_TRY(hipGetLastError());
 	auto widen = rocprim::make_transform_iterator(c->len.p, [] __host__ __device__ (uint32_t x) { return (uint64_t) x; });
 	size_t sb = 0;
-	SNP_HIP_TRY(rocprim::exclusive_scan(nullptr, sb, widen, c->line_off.p, (uint64_t) 0, (size_t) m + 1, rocprim::plus<uint64_t>(), c->st));
+	NGM_HIP_TRY(rocprim::exclusive_scan(nullptr, sb, widen, c->line_off.p, (uint64_t) 0, (size_t) m + 1, rocprim::plus<uint64_t>(), c->st));
 	if (c->tmp.grow(sb + 16)) { ngm::pipeline_set_error("out of device memory for a scan"); return -12; }
-	SNP_HIP_TRY(rocprim::exclusive_scan(c->tmp.p, sb, widen, c->line_off.p, (uint64_t) 0, (size_t) m + 1, rocprim::plus<uint64_t>(), c->st));
+	NGM_HIP_TRY(rocprim::exclusive_scan(c->tmp.p, sb, widen, c->line_off.p, (uint64_t) 0, (size_t) m + 1, rocprim::plus<uint64_t>(), c->st));
 	uint64_t total = 0;
-	SNP_HIP_TRY(hipMemcpyAsync(&total, c->line_off.p + m, 8, hipMemcpyDeviceToHost, c->st));
-	SNP_HIP_TRY(hipStreamSynchronize(c->st));
+	NGM_HIP_TRY(hipMemcpyAsync(&total, c->line_off.p + m, 8, hipMemcpyDeviceToHost, c->st));
+	NGM_HIP_TRY(hipStreamSynchronize(c->st));
 	if (total) {
 		if (c->d_text.grow((size_t) total)) { ngm::pipeline_set_error("out of device memory for %llu bytes of lines", (unsigned long long) total); return -12; }
 		T.out = c->d_text.p;
 		hipLaunchKernelGGL(sn::snp_write_kernel, dim3(blocks_of(m)), dim3(256), 0, c->st, T);
-		SNP_HIP_TRY(hipGetLastError());
+		NGM_HIP_TRY(hipGetLastError());
 	}
-	SNP_HIP_TRY(hipEventRecord(c->ev[4], c->st));
+	NGM_HIP_TRY(hipEventRecord(c->ev[4], c->st));
 	c->text.resize((size_t) total);
-	if (total) SNP_HIP_TRY(hipMemcpyAsync(c->text.data(), c->d_text.p, (size_t) total, hipMemcpyDeviceToHost, c->st));
-	SNP_HIP_TRY(hipStreamSynchronize(c->st));
+	if (total) NGM_HIP_TRY(hipMemcpyAsync(c->text.data(), c->d_text.p, (size_t) total, hipMemcpyDeviceToHost, c->st));
+	NGM_HIP_TRY(hipStreamSynchronize(c->st));
 	if (hipEventElapsedTime(&t, c->ev[3], c->ev[4]) == hipSuccess) c->ms[3] += t;
 	return 0;
 }

@@ -1,15 +1,23 @@
 // CPU-only driver for tests/test_host_units.py: the header-only host pieces of the product that need no GPU.
 //   bam <out.bam>        a small BAM file written with csrc/bam_writer.h (header, dictionary, records in several BGZF chunks, EOF)
 //   pool                 ngm::ThreadPool::parallel_for: sums, concurrent callers, nested use
+//   format <spec> [out.bam]   the host formatter of `ngm-hip` (csrc/cli_format.h) over the records a text file describes:
+//                        opt <key> <value> | contig <name> <bases> | rec <name> <row or -> <qualities or *> <seq_len> <unit> <polya>, followed by
+//                        topn lines: hit <mapped> <contig> <pos> <reverse> <mapq> <score> <identity> <nm> <qstart> <qend> <n_candidates> <n_best>
+//                        <max_votes> <pair_flags> <cigar> <md>.  Prints the SAM text (with out.bam: writes the records as a BAM file instead), what the
+//                        --coverage / --snp callbacks got ("#cov", "#snp"), and "#counts total mapped written pairs broken insert_sum"
 #include <atomic>
 #include <cstdio>
 #include <cstring>
+#include <fstream>
 #include <numeric>
+#include <sstream>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "../../nextgenmap_amd/csrc/bam_writer.h"
+#include "../../nextgenmap_amd/csrc/cli_format.h"
 #include "../../nextgenmap_amd/csrc/thread_pool.h"
 
 static int write_bam(const char *path) {
@@ -79,7 +87,108 @@ static int test_pool() {
 	return total == expect ? 0 : 1;
 }
 
+static int format_records(const char *spec, const char *bam_out) {
+	using ngm::cli::HostFormatter;
+	HostFormatter f;
+	f.q = 16;
+	std::vector<std::string> contig_seq;
+	struct Text { std::string name, row, qual; };
+	std::vector<Text> text;
+	std::vector<ngm::cli::Rec> recs;
+	std::vector<ngm_hit> hits;
+	std::vector<std::string> cig, md;
+	bool cov = false, snp = false;
+	std::ifstream in(spec);
+	for (std::string line; std::getline(in, line);) {
+		std::istringstream ls(line);
+		std::string kind;
+		if (!(ls >> kind) || kind[0] == '#') continue;
+		if (kind == "opt") {
+			std::string k, v;
+			ls >> k >> v;
+			if (k == "min_identity") f.min_identity = std::stof(v); else if (k == "min_residues") f.min_residues = std::stof(v); else if (k == "min_mq") f.min_mq = std::stoi(v);
+			else if (k == "paired") f.paired = std::stoi(v); else if (k == "topn") f.topn = std::stoi(v); else if (k == "strata") f.strata = std::stoi(v);
+			else if (k == "clip") f.clip = std::stoi(v); else if (k == "no_unal") f.no_unal = std::stoi(v); else if (k == "bs_mapping") f.bs_mapping = std::stoi(v);
+			else if (k == "slam_seq") f.slam_seq = std::stoi(v); else if (k == "variant") f.variant = std::stoi(v); else if (k == "xa_tag") f.xa_tag = std::stoi(v) != 0;
+			else if (k == "rg") f.set_read_group(v); else if (k == "min_insert") f.min_insert = std::stoi(v); else if (k == "max_insert") f.max_insert = std::stoi(v);
+			else if (k == "coverage") cov = std::stoi(v) != 0; else if (k == "snp") snp = std::stoi(v) != 0;
+			else { fprintf(stderr, "unknown option %s\n", k.c_str()); return 65; }
+		} else if (kind == "contig") {
+			std::string name, bases;
+			ls >> name >> bases;
+			f.contig_names.push_back(name); contig_seq.push_back(bases);
+		} else if (kind == "rec") {
+			Text t;
+			unsigned seq_len = 0, unit = 0, polya = 0;
+			ls >> t.name >> t.row >> t.qual >> seq_len >> unit >> polya;
+			if (t.row == "-") t.row.clear();
+			if (t.qual == "*") t.qual.clear();
+			t.row.resize((size_t) f.q, '\0');
+			text.push_back(t);
+			recs.push_back(ngm::cli::Rec{nullptr, nullptr, nullptr, 0, seq_len, 0, (uint8_t) unit, (uint16_t) polya});
+		} else if (kind == "hit") {
+			ngm_hit h{};
+			std::string c, m;
+			ls >> h.mapped >> h.contig >> h.pos >> h.reverse >> h.mapq >> h.score >> h.identity >> h.nm >> h.qstart >> h.qend >> h.n_candidates >> h.n_best >> h.max_votes >> h.pair_flags >> c >> m;
+			if (!ls) { fprintf(stderr, "bad hit line: %s\n", line.c_str()); return 65; }
+			hits.push_back(h); cig.push_back(c); md.push_back(m);
+		} else { fprintf(stderr, "unknown line: %s\n", line.c_str()); return 65; }
+	}
+	f.bam = bam_out != nullptr;
+	f.stride = (size_t) 4 * f.q;
+	const size_t n = recs.size();
+	if (hits.size() != n * (size_t) f.topn) { fprintf(stderr, "%zu records need %zu hits, not %zu\n", n, n * (size_t) f.topn, hits.size()); return 65; }
+	std::vector<char> rows(n * (size_t) f.q + 1, '\0'), cigs(hits.size() * f.stride + 1, '\0'), mds(hits.size() * f.stride + 1, '\0');
+	for (size_t i = 0; i < n; ++i) {
+		memcpy(&rows[i * (size_t) f.q], text[i].row.data(), (size_t) f.q);
+		recs[i].name = text[i].name.data(); recs[i].name_len = (uint32_t) text[i].name.size();
+		recs[i].qual = text[i].qual.data(); recs[i].qual_len = (uint32_t) text[i].qual.size();
+	}
+	for (size_t e = 0; e < hits.size(); ++e) {
+		if (cig[e].size() >= f.stride || md[e].size() >= f.stride) return 65;
+		memcpy(&cigs[e * f.stride], cig[e].data(), cig[e].size()); memcpy(&mds[e * f.stride], md[e].data(), md[e].size());
+	}
+	f.ref_classes = [&](int contig, uint64_t pos, int span, uint8_t *out) {
+		for (int k = 0; k < span; ++k) {
+			const char ch = pos + (uint64_t) k < contig_seq[contig].size() ? contig_seq[contig][pos + (uint64_t) k] : 'N';
+			out[k] = ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : ch == 'T' ? 3 : ch == 'N' ? 5 : 4;
+		}
+	};
+	std::string side;
+	if (cov) f.add_coverage = [&](const ngm::cli::CovAcc &a) {
+		side += "#cov";
+		for (size_t i = 0; i < a.ref.size(); ++i) side += " " + std::to_string(a.ref[i]) + ":" + std::to_string(a.pos[i]) + ":" + a.text.substr(a.off[i], a.off[i + 1] - a.off[i]);
+		side += "\n";
+	};
+	if (snp) f.add_snp = [&](const ngm::cli::SnpAcc &a, bool has_qual) {
+		side += has_qual ? "#snp qual" : "#snp noqual";
+		if (a.qual.size() != (has_qual ? a.seq.size() : 0)) side += " QUALITY-LENGTH-DIFFERS";
+		for (size_t i = 0; i < a.ref.size(); ++i) {
+			side += " " + std::to_string(a.ref[i]) + ":" + std::to_string(a.pos[i]) + ":" + a.text.substr(a.off[i], a.off[i + 1] - a.off[i]) + ":" + a.seq.substr(a.seq_off[i], a.seq_off[i + 1] - a.seq_off[i]);
+			if (has_qual) side += ":" + a.qual.substr(a.seq_off[i], a.seq_off[i + 1] - a.seq_off[i]);
+		}
+		side += "\n";
+	};
+	std::string out;
+	HostFormatter::Counts c;
+	f.format_range(HostFormatter::Input{recs.data(), hits.data(), rows.data(), cigs.data(), mds.data()}, 0, (int) n, out, c);
+	if (bam_out) {
+		std::string raw, file;
+		std::vector<uint64_t> lens;
+		for (const std::string &b : contig_seq) lens.push_back(b.size());
+		ngm::bam::put_header(raw, "@HD\tVN:1.0\tSO:unsorted\n", f.contig_names, lens);
+		raw += out;
+		if (!ngm::bam::bgzf_compress(raw.data(), raw.size(), file)) return 2;
+		ngm::bam::bgzf_eof(file);
+		std::ofstream(bam_out, std::ios::binary).write(file.data(), (std::streamsize) file.size());
+	} else fwrite(out.data(), 1, out.size(), stdout);
+	fwrite(side.data(), 1, side.size(), stdout);
+	printf("#counts %zu %zu %zu %llu %llu %llu\n", c.total, c.mapped, c.written, (unsigned long long) c.pair[0], (unsigned long long) c.pair[1], (unsigned long long) c.pair[2]);
+	return 0;
+}
+
 int main(int argc, char **argv) {
+	if (argc >= 3 && !strcmp(argv[1], "format")) return format_records(argv[2], argc >= 4 ? argv[3] : nullptr);
 	if (argc >= 3 && !strcmp(argv[1], "bam")) return write_bam(argv[2]);
 	if (argc >= 2 && !strcmp(argv[1], "pool")) return test_pool();
 	return 64;
