@@ -472,6 +472,13 @@ int ngm_debug_pair_select(int device, int n_pairs, const uint32_t *base, const u
  * queued again, [3] times the pool of global-memory vote tables had to grow (one more synchronisation in that batch) */
 int ngm_mapper_heavy_counters(ngm_mapper *m, uint64_t out[4]);
 
+/* of the last ngm_mapper_map_* call, how its search + score turn went: [0] 1 when the per-read arrays of the search (candidate offsets,
+ * counts, best votes) travelled behind the score stage instead of in front of the search's synchronisation (0 under
+ * NGM_HIP_CS_EAGER_ARRAYS=1, read when the mapper is created), [1] search attempts (more than one: the candidate regions overflowed and
+ * the batch was searched again with four times the room), [2] score-stage buffers that had to grow behind the synchronisation, inside
+ * the turn, because the count predicted in front of the search was too small.  tests/test_gpu_search_turn.py */
+int ngm_mapper_search_turn_counters(ngm_mapper *m, uint64_t out[3]);
+
 /* work counters of the last candidate search: [0] k-mers looked up, [1] index hits voted, [2] candidates emitted
  * (algorithmic bytes of the search = 20 * kmers + 4 * hits + 16 * candidates) */
 int ngm_mapper_cs_counters(ngm_mapper *m, uint64_t out[3]);

@@ -30,6 +30,21 @@ constexpr int kCsqPoolFlag = 12;      // 1: the tables of the queued reads need 
 constexpr int kCsqGlobalCount = 13;   // reads given to cs_global_kernel
 constexpr int kCsqPoolNeed = 14;      // [14..15] slots the tables need (64-bit)
 
+// The words a search starts from, cleared in ONE dispatch (five hipMemsetAsync before: each a fill kernel of its own at the head of the
+// turn): the status block, the region cursors, the counters, the control block, and the per-read candidate counts (a read no pass has
+// finished -- a pass skipped for want of pool room -- has no candidates yet).  Any grid: the threads stride over each block.
+__global__ __launch_bounds__(256) void cs_reset_kernel(uint32_t *__restrict__ status, int status_words, unsigned long long *__restrict__ total, int total_words,
+		unsigned long long *__restrict__ counters, int counter_words, uint32_t *__restrict__ ctl, int ctl_words, uint32_t *__restrict__ cand_count, int n_reads) {
+	const int stride = (int) (gridDim.x * blockDim.x), t0 = (int) (blockIdx.x * blockDim.x + threadIdx.x);
+	for (int i = t0; i < n_reads; i += stride) cand_count[i] = 0u;
+	for (int i = t0; i < total_words; i += stride) total[i] = 0ull;
+	for (int i = t0; i < counter_words; i += stride) counters[i] = 0ull;
+	if (blockIdx.x == 0) {
+		for (int i = (int) threadIdx.x; i < status_words; i += (int) blockDim.x) status[i] = 0u;
+		for (int i = (int) threadIdx.x; i < ctl_words; i += (int) blockDim.x) ctl[i] = 0u;
+	}
+}
+
 // Deals the queue into the class lists.  One workgroup (the queue is a few thousand to a few hundred thousand entries; in-place
 // compaction of the entries that stay needs no second buffer this way).  A read with h index hits goes to class 0 when h < b0, else to
 // class 1 when h < b1, else to class 2 when h < b2, else it STAYS queued (b0 <= b1 <= b2; a bound equal to the one before it closes the

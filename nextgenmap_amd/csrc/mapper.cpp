@@ -166,6 +166,7 @@ ngm_mapper *ngm_mapper_create(const ngm_ref *ref, const ngm_mapper_params *p) {
 	for (auto &e : m->ev) (void) hipEventCreate(&e);
 	for (auto &e : m->cev) (void) hipEventCreate(&e);
 	for (auto &e : m->oev) (void) hipEventCreate(&e);
+	if (const char *e = getenv("NGM_HIP_CS_EAGER_ARRAYS")) m->cs_eager_arrays = atoi(e) != 0;   // read per mapper: one process may hold one of each kind
 	if (ngm::cs_configure(m, p) != 0) { ngm_mapper_destroy(m); return nullptr; }
 	return m;
 }
@@ -701,23 +702,27 @@ static int map_impl(ngm_mapper *m, int n, const char *reads, const void *d_reads
 		}
 		hits = m->p_sam_hits.p;
 	}
-	GpuStage stage_cs(m);
-	m->cs_paired = paired;
-	if (int rc = run_cs(m, n, &stage_cs)) return rc;
-	MAP_HIP_TRY(hipEventRecord(m->ev[1], m->st));
-	const uint64_t np = m->n_cand;
-	lap(0);
-	if (const char *dump = getenv("NGM_HIP_DUMP_COUNTS")) {  // diagnostics: candidates per read, appended batch after batch
-		if (int rc = cs_host_arrays(m)) return rc;
-		if (FILE *f = fopen(dump, "ab")) { fwrite(m->h_count.data(), 4, (size_t) n, f); fclose(f); }
-	}
-
-	if (m->p_winner.reserve(n) || m->p_mapq.reserve(n) || m->p_nbest.reserve(n) || m->p_best.reserve(n) || m->p_loc.reserve(np + 1) ||
-			m->p_sv.reserve(np + 1) || (paired && m->p_scores.reserve(np + 1))) { ngm::pipeline_set_error("out of pinned host memory"); return -12; }
-	uint32_t *h_winner = m->p_winner.p, *h_loc = m->p_loc.p, *h_sv = m->p_sv.p;
+	// ---- in front of the search, outside the turn: everything the score stage needs from the host.  What is sized by the number of reads
+	// is final here; what is sized by the number of candidates is reserved for a predicted count -- 5/4 of the most this mapper has seen,
+	// at least one per read -- and once more for the real count behind the search's synchronisation: a no-op when it fits, a buffer that
+	// grows inside the turn when it does not (the first batches of a run; counted in turn_dbg[2]).
+	if (m->p_winner.reserve(n) || m->p_mapq.reserve(n) || m->p_nbest.reserve(n) || m->p_best.reserve(n)) { ngm::pipeline_set_error("out of pinned host memory"); return -12; }
+	if (m->d_winner.reserve(n) || m->d_mapq.reserve(n) || m->d_nbest.reserve(n) || m->d_best.reserve(n)) { ngm::pipeline_set_error("out of device memory (score stage)"); return -12; }
+	uint64_t regrown = 0;
+	auto reserve_for_candidates = [&](uint64_t cnt, bool device, bool count) -> int {
+		auto grow = [&](auto &buf, size_t want) { if (count && buf.cap < want) ++regrown; return buf.reserve(want); };
+		if (grow(m->p_loc, cnt + 1) || grow(m->p_sv, cnt + 1) || (paired && grow(m->p_scores, cnt + 1))) { ngm::pipeline_set_error("out of pinned host memory"); return -12; }
+		if (!device) return 0;
+		if (grow(m->d_pair_read, cnt) || grow(m->d_scores, cnt)) { ngm::pipeline_set_error("out of device memory (score stage)"); return -12; }
+		const size_t had = eng->packed.cap + eng->lens.cap + eng->blk_rows.cap;
+		if (int rc = ngm::engine_reserve(eng, (int) cnt)) { ngm::pipeline_set_error("%s", ngm_hip_last_error(eng)); return rc; }
+		if (count && eng->packed.cap + eng->lens.cap + eng->blk_rows.cap != had) ++regrown;
+		return 0;
+	};
+	if (int rc = reserve_for_candidates(std::min<uint64_t>(std::max<uint64_t>((uint64_t) n, m->np_seen_max + m->np_seen_max / 4), 0x7FFFFFFFull), true, false)) return rc;
+	uint32_t *h_winner = m->p_winner.p, *h_loc = nullptr, *h_sv = nullptr;
 	int32_t *h_mapq = m->p_mapq.p, *h_nbest = m->p_nbest.p;
-	float *h_best = m->p_best.p, *h_scores = m->p_scores.p;
-	if (np == 0) { if (int rc = cs_host_arrays(m)) return rc; for (int i = 0; i < n; ++i) { h_winner[i] = 0xFFFFFFFFu; h_mapq[i] = 0; h_nbest[i] = 0; h_best[i] = 0.f; } }
+	float *h_best = m->p_best.p, *h_scores = nullptr;
 	std::vector<int> pair_flags(n, 0);
 	auto reference_buffer_walk = [&]() {   // inside the batch's turn (sequential state)
 		// A pair the reference LOSES (round 5; the "early top1SE" earlier rounds described does not exist -- MappedRead::Calculated
@@ -752,11 +757,26 @@ static int map_impl(ngm_mapper *m, int n, const char *reads, const void *d_reads
 		}
 		m->scores_so_far = tot; m->reads_so_far = at;
 	};
+	GpuStage stage_cs(m, 0, false);   // the turn begins at the search's first enqueue (run_cs takes it)
+	m->cs_paired = paired;
+	m->turn_dbg[2] = 0;
+	if (int rc = run_cs(m, n, &stage_cs, true)) return rc;
+	MAP_HIP_TRY(hipEventRecord(m->ev[1], m->st));
+	const uint64_t np = m->n_cand;
+	m->np_seen_max = std::max(m->np_seen_max, np);
+	lap(0);
+	if (const char *dump = getenv("NGM_HIP_DUMP_COUNTS")) {  // diagnostics: candidates per read, appended batch after batch
+		if (int rc = cs_host_arrays(m)) return rc;
+		if (FILE *f = fopen(dump, "ab")) { fwrite(m->h_count.data(), 4, (size_t) n, f); fclose(f); }
+	}
+
+	if (int rc = reserve_for_candidates(np, np > 0, true)) return rc;
+	m->turn_dbg[2] = regrown;
+	h_loc = m->p_loc.p; h_sv = m->p_sv.p; h_scores = m->p_scores.p;
+	if (np == 0) { if (int rc = cs_host_arrays(m)) return rc; for (int i = 0; i < n; ++i) { h_winner[i] = 0xFFFFFFFFu; h_mapq[i] = 0; h_nbest[i] = 0; h_best[i] = 0.f; } }
 	if (np > 0) {
 		// ---- score stage: all candidates of the batch in one BatchScore -------------------------------------
-		if (m->d_pair_read.reserve(np) || m->d_scores.reserve(np) || m->d_winner.reserve(n) || m->d_mapq.reserve(n) || m->d_nbest.reserve(n) ||
-				m->d_best.reserve(n)) { ngm::pipeline_set_error("out of device memory (score stage)"); return -12; }
-		if (int rc = ngm::engine_reserve(eng, (int) np)) { ngm::pipeline_set_error("%s", ngm_hip_last_error(eng)); return rc; }
+		// (its buffers: reserve_for_candidates above)
 		stage_cs.acquire();
 		if (int rc = ngm::score_candidates(m, n, np, alt_dir)) return rc;
 		hipLaunchKernelGGL(ngm::select_top1_kernel, dim3((n + 255) / 256), dim3(256), 0, m->st, n, m->d_cand_base.p, m->d_cand_count.p,
@@ -795,6 +815,7 @@ static int map_impl(ngm_mapper *m, int n, const char *reads, const void *d_reads
 		MAP_HIP_TRY(hipMemcpyAsync(h_loc, m->d_out_loc.p, np * 4, hipMemcpyDeviceToHost, m->st));
 		MAP_HIP_TRY(hipMemcpyAsync(h_sv, m->d_out_sv.p, np * 4, hipMemcpyDeviceToHost, m->st));
 		if (paired) MAP_HIP_TRY(hipMemcpyAsync(h_scores, m->d_scores.p, np * 4, hipMemcpyDeviceToHost, m->st));
+		if (int rc = ngm::cs_enqueue_host_arrays(m)) return rc;   // the search's per-read arrays, deferred to here: they travel under the next instance's kernels
 		stage_cs.done_after(m->ev[4]);
 		MAP_HIP_TRY(hipStreamSynchronize(m->st));
 		if (int rc = cs_host_arrays(m)) return rc;
@@ -1198,6 +1219,13 @@ static int map_impl(ngm_mapper *m, int n, const char *reads, const void *d_reads
 		MAP_HIP_TRY(hipMemcpyAsync(m->d_a_read.p, a_read.data(), (size_t) na * 4, hipMemcpyHostToDevice, m->st));
 		MAP_HIP_TRY(hipMemcpyAsync(m->d_a_loc.p, a_loc.data(), (size_t) na * 4, hipMemcpyHostToDevice, m->st));
 		MAP_HIP_TRY(hipMemcpyAsync(m->d_a_sv.p, a_sv.data(), (size_t) na * 4, hipMemcpyHostToDevice, m->st));
+		// (what the turn needs besides: the string buffers, and the finishing kernel's two counters cleared -- in front of the turn, not in it)
+		static const bool tail_split = getenv("NGM_HIP_ALIGN_TAIL_SPLIT") != nullptr;
+		const bool affine = m->prm.personality == NGM_PERSONALITY_AFFINE;
+		const bool finish = affine && dev_strings && topn == 1 && !tail_split;
+		const unsigned long long scap = (unsigned long long) na * 96ull + 4096ull;
+		if (dev_strings && (m->d_cigout.reserve(na) || m->d_str.reserve(scap) || m->p_cigout.reserve(na))) { ngm::pipeline_set_error("out of memory (CIGAR strings)"); return -12; }
+		if (finish) MAP_HIP_TRY(hipMemsetAsync(m->d_total.p + 8, 0, 16, m->st));   // the stage's one memset: stream cursor + fall-back counter
 		MAP_HIP_TRY(hipStreamSynchronize(m->st));   // (the uploads travel outside the stage lock)
 		stage_align.acquire();
 		MAP_HIP_TRY(hipEventRecord(m->ev[5], m->st));
@@ -1207,18 +1235,12 @@ static int map_impl(ngm_mapper *m, int n, const char *reads, const void *d_reads
 		MAP_HIP_TRY(hipGetLastError());
 		MAP_HIP_TRY(hipEventRecord(m->ev[6], m->st));
 		const bool was_prof = eng->profiling;
-		const bool affine = m->prm.personality == NGM_PERSONALITY_AFFINE;
 		// affine, strings on the GPU, one alignment per read: DP, then ONE finishing kernel from the trace matrix to the strings
 		// (affine_finish_kernel, cigar_device.h).  NGM_HIP_ALIGN_TAIL_SPLIT=1 keeps the three kernels traceback / compact_runs / cigar_strings
 		// and their downloads (tests); they also serve every other mode, and the alignments the finishing kernel leaves to the host.
-		static const bool tail_split = getenv("NGM_HIP_ALIGN_TAIL_SPLIT") != nullptr;
-		const bool finish = affine && dev_strings && topn == 1 && !tail_split;
-		const unsigned long long scap = (unsigned long long) na * 96ull + 4096ull;
 		unsigned long long n_runs_total = 0, n_str_total = 0;
-		if (dev_strings && (m->d_cigout.reserve(na) || m->d_str.reserve(scap) || m->p_cigout.reserve(na))) { ngm::pipeline_set_error("out of memory (CIGAR strings)"); return -12; }
 		if (finish) {
 			unsigned long long ctr[2] = {0, 0};   // [0] bytes of the string stream, [1] alignments left to the host
-			MAP_HIP_TRY(hipMemsetAsync(m->d_total.p + 8, 0, 16, m->st));   // the stage's one memset: stream cursor + fall-back counter
 			const ngm::AlignFinish fin{m->d_cigout.p, m->d_str.p, scap, m->d_total.p + 8};
 			eng->profiling = true;  // brackets DP vs finishing kernel with eng->ev[2]
 			if (int rc = ngm::engine_align_packed(eng, mode, na, m->d_records.p, m->d_runs.p, rs, m->st, &fin)) { eng->profiling = was_prof; ngm::pipeline_set_error("%s", ngm_hip_last_error(eng)); return rc; }
@@ -1823,6 +1845,12 @@ int ngm_mapper_heavy_counters(ngm_mapper *m, uint64_t out[4]) {
 int ngm_mapper_order_table_reads(ngm_mapper *m, uint64_t *out) {
 	if (!m || !out) return -22;
 	*out = m->st_order_table;
+	return 0;
+}
+
+int ngm_mapper_search_turn_counters(ngm_mapper *m, uint64_t out[3]) {
+	if (!m || !out) return -22;
+	out[0] = m->turn_dbg[0]; out[1] = m->turn_dbg[1]; out[2] = m->turn_dbg[2];
 	return 0;
 }
 

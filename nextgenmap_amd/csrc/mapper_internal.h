@@ -99,7 +99,7 @@ struct ngm_mapper {
 	ngm::DevBuf<uint8_t> d_reads;
 	ngm::DevBuf<uint16_t> d_read_len;
 	ngm::DevBuf<uint32_t> d_cand_base, d_cand_count, d_out_loc, d_out_sv, d_status, d_ovf_read, d_ovf_read2, d_ovf_hits, d_ovf_hits2, d_ovf_log2;
-	ngm::PinnedBuf<uint32_t> p_cs_status;   // the status and control blocks of a search, as downloaded (cs_queue_device.h)
+	ngm::PinnedBuf<uint32_t> p_cs_status;   // what a search's one synchronisation waits for, as downloaded: status and control blocks (cs_queue_device.h), candidate count, counters
 	ngm::DevBuf<uint64_t> d_ovf_off;
 	ngm::DevBuf<uint32_t> d_gt_keys, d_gt_votes, d_heavy_list, d_heavy_ctr;
 	ngm::DevBuf<float> d_max_votes, d_max_both, d_scores, d_best;
@@ -179,6 +179,16 @@ struct ngm_mapper {
 	HostArr<uint32_t> h_base, h_count;
 	HostArr<float> h_maxv;
 	uint64_t n_cand = 0;
+	// The three arrays above travel either in front of the search's one synchronisation (cs_eager_arrays: NGM_HIP_CS_EAGER_ARRAYS=1 when
+	// the mapper was created, and every run_cs without defer_host_arrays) or behind the score stage's last kernel, outside the turn
+	// (cs_enqueue_host_arrays); cs_host_arrays is the guarantee that they have arrived.
+	bool cs_eager_arrays = false;
+	int cs_arrays_state = 0;          // 0 complete on the host, 1 deferred and not yet enqueued, 2 enqueued on `st`, not yet waited for
+	int canon_per_cu = 0;             // workgroups of the canonical fast path a CU holds, for (canon_fn, canon_lds) -- as heavy_per_cu
+	const void *canon_fn = nullptr;
+	size_t canon_lds = 0;
+	uint64_t np_seen_max = 0;         // most candidates of a batch so far: the score stage's buffers are reserved for 5/4 of it in front of the search
+	uint64_t turn_dbg[3] = {0, 0, 0}; // ngm_mapper_search_turn_counters, of the last map call: arrays deferred (0/1), search attempts, buffers regrown after the synchronisation
 	hipEvent_t ev[10] = {};   // [8]: behind the last kernel of the align stage
 	float ms[8] = {};
 };
@@ -238,8 +248,11 @@ struct GpuStage {
 int cs_configure(ngm_mapper *m, const ngm_mapper_params *p);
 // candidate search for the reads already in m->d_reads; leaves per-read base/count/max votes and the candidate arrays in HBM (and
 // base/count/max votes on the host)
-int run_cs(ngm_mapper *m, int n, GpuStage *stage = nullptr);
-int cs_host_arrays(ngm_mapper *m);
+// defer_host_arrays: the per-read arrays are NOT enqueued (the search's synchronisation waits for the status / control blocks, the
+// counters and the candidate count only); the caller enqueues them later with cs_enqueue_host_arrays, or cs_host_arrays does
+int run_cs(ngm_mapper *m, int n, GpuStage *stage = nullptr, bool defer_host_arrays = false);
+int cs_enqueue_host_arrays(ngm_mapper *m);   // the deferred copies of h_base / h_count / h_maxv, on m->st (nothing to do when they are not pending)
+int cs_host_arrays(ngm_mapper *m);           // returns when h_base / h_count / h_maxv of the last search are complete (enqueues them if nobody has)
 // Reference order of the candidates of the listed reads (cs_order_kernel): h_rank[c] for every candidate c of those
 // reads, kCsOrderUnknown where it could not be determined.  Only called for reads where the order decides something.
 // wait = false: only enqueue (the list must stay alive until candidate_order_wait)

@@ -49,6 +49,7 @@ size_t cs_lds_bytes(const CsArgs &A, int mode) {
 }
 
 constexpr size_t kLdsLimit = 160 * 1024;      // of a CU (gfx950)
+constexpr int kCsHostLast = 16 + kCsqWords, kCsHostCtr = (kCsHostLast + 2 + 1) / 2 * 2;   // words of ngm_mapper::p_cs_status: candidate count (2), counters (64-bit: at an even word)
 constexpr int kLdsAttr = 150 * 1024;          // what hipFuncAttributeMaxDynamicSharedMemorySize is set to for the kernels sized at run time
 
 }  // namespace
@@ -213,20 +214,25 @@ void cs_release(ngm_mapper *m) {
 
 // candidate search for the reads already in m->d_reads; leaves per-read base/count/max votes and the
 // candidate arrays in HBM (and base/count/max votes on the host)
-int run_cs(ngm_mapper *m, int n, GpuStage *stage) {
+int run_cs(ngm_mapper *m, int n, GpuStage *stage, bool defer_host_arrays) {
 	const ngm_ref *r = m->ref;
 	auto hold = [&] { if (stage) stage->acquire(); };       // before kernels are enqueued
 	const int q = m->prm.qry_max_len;
+	m->cs_arrays_state = 0;
+	m->turn_dbg[0] = m->turn_dbg[1] = 0;
 	if (n <= 0) { m->n_reads = 0; m->n_cand = 0; return 0; }
+	const bool defer = defer_host_arrays && !m->cs_eager_arrays;
 	const size_t ctr_words = (size_t) kCsRegions * kCsCursorStride;
 	if (m->d_read_len.reserve(n) || m->d_cand_base.reserve(n) || m->d_cand_count.reserve(n) || m->d_max_votes.reserve(n) || m->d_max_both.reserve(n) ||
 			m->d_status.reserve(16) || m->d_total.reserve(ctr_words + 16) || m->d_counters.reserve(ctr_words + 32) || m->d_new_base.reserve(n) || m->d_ovf_read.reserve(n) || m->d_ovf_read2.reserve(n) ||
-			m->d_ovf_hits.reserve(n) || m->d_ovf_hits2.reserve(n) || m->d_heavy_ctr.reserve(kCsqWords) || m->p_cs_status.reserve(16 + kCsqWords + 2) ||
+			m->d_ovf_hits.reserve(n) || m->d_ovf_hits2.reserve(n) || m->d_heavy_ctr.reserve(kCsqWords) || m->p_cs_status.reserve(kCsHostCtr + 2 * (ctr_words + 16)) ||
 			m->h_base.b.reserve(n) || m->h_count.b.reserve(n) || m->h_maxv.b.reserve(n)) {
 		pipeline_set_error("out of memory (candidate search, %d reads)", n);
 		return -12;
 	}
 	size_t cap = std::max<size_t>(m->cs_region_cap, (size_t) n * 4 + 64 * kCsRegions);
+	// NGM_HIP_TEST_LIMITS=cs_cap=N: a mapper's FIRST capacity is at most N slots, so that the grow-and-redo loop below runs on a test genome
+	if (const long lim = test_limit("cs_cap", 0); lim > 0 && m->cs_region_cap == 0) cap = std::min<size_t>(cap, (size_t) std::max<long>(lim, kCsRegions));
 	cap = (cap + kCsRegions - 1) / kCsRegions * kCsRegions;
 	const size_t fixed_slots = getenv("NGM_HIP_CS_NO_FIXED_SLOTS") ? 0 : (size_t) n * kCsFixedSlots;
 	static const bool host_timing = getenv("NGM_HIP_HOST_TIMING") != nullptr;
@@ -234,18 +240,17 @@ int run_cs(ngm_mapper *m, int n, GpuStage *stage) {
 	const bool bs = m->prm.bs_mapping != 0;
 	const bool slamw = (m->prm.slam_seq & 4) != 0;
 	for (int attempt = 0; attempt < 8; ++attempt) {
+		m->turn_dbg[1] = (uint64_t) attempt + 1;
 		// candidate offsets are 32-bit (base = region * capacity + cursor; the prefix sums over the counts)
 		if (cap + fixed_slots >= 0xFFFFFFFFull) { pipeline_set_error("more than 2^32 candidate slots needed for %d reads: use smaller batches or a higher sensitivity", n); return -75; }
 		if (m->d_out_loc.reserve(cap + fixed_slots) || m->d_out_sv.reserve(cap + fixed_slots) || m->d_out_loc2.reserve(cap + fixed_slots) || m->d_out_sv2.reserve(cap + fixed_slots)) { pipeline_set_error("out of device memory (candidates)"); return -12; }
 		size_t tmp_bytes = 0;
 		(void) rocprim::exclusive_scan(nullptr, tmp_bytes, m->d_cand_count.p, m->d_new_base.p, 0u, (size_t) n, rocprim::plus<uint32_t>(), m->st);
 		if (m->d_scan_tmp.reserve(tmp_bytes + 16)) { pipeline_set_error("out of device memory (scan)"); return -12; }
-		hold();
-		MAP_HIP_TRY(hipMemsetAsync(m->d_status.p, 0, 64, m->st));
-		MAP_HIP_TRY(hipMemsetAsync(m->d_total.p, 0, (ctr_words + 16) * 8, m->st));
-		MAP_HIP_TRY(hipMemsetAsync(m->d_counters.p, 0, (ctr_words + 32) * 8, m->st));
-		MAP_HIP_TRY(hipMemsetAsync(m->d_heavy_ctr.p, 0, kCsqWords * 4, m->st));
-		MAP_HIP_TRY(hipMemsetAsync(m->d_cand_count.p, 0, (size_t) n * 4, m->st));   // (a read no pass has finished -- a pass skipped for want of pool room -- has no candidates yet)
+		hold();   // the turn begins at the first enqueue: everything above is host work
+		hipLaunchKernelGGL(cs_reset_kernel, dim3(std::min((n + 255) / 256, 4 * m->cus)), dim3(256), 0, m->st, m->d_status.p, 16, m->d_total.p, (int) (ctr_words + 16),
+				m->d_counters.p, (int) (ctr_words + 32), m->d_heavy_ctr.p, (int) kCsqWords, m->d_cand_count.p, n);
+		MAP_HIP_TRY(hipGetLastError());
 		CsArgs A{};
 		A.reads = m->d_reads.p; A.n = n; A.q = q; A.k = r->prm.kmer; A.bin_shift = r->prm.bin_size;
 		A.max_kfreq = m->max_kfreq; A.sensitivity = m->prm.sensitivity; A.kmer_min = m->prm.kmer_min; A.max_cmrs = m->prm.max_cmrs;
@@ -256,9 +261,15 @@ int run_cs(ngm_mapper *m, int n, GpuStage *stage) {
 		A.fixed_base = fixed_slots ? (uint32_t) cap : 0u;
 		A.status = m->d_status.p; A.ovf_read = m->d_ovf_read.p; A.ovf_hits = m->d_ovf_hits.p; A.counters = m->d_counters.p;
 		A.phase_cycles = phases ? m->d_counters.p + ctr_words : nullptr;
-		uint32_t *const status = m->p_cs_status.p;           // [0..15] the status block, [16..] the control block, as downloaded
+		// everything the search's one synchronisation waits for lands in ONE pinned block: [0..15] the status block, [16..] the control block,
+		// then the two words that make up the candidate count, then the counters.  (Counters and count went to pageable memory before: a
+		// device-to-host copy to pageable memory is not asynchronous -- the host waited for each of the three in turn, the GPU idle.)
+		uint32_t *const status = m->p_cs_status.p;
 		uint32_t *const ctl = status + 16;
-		memset(status, 0, (16 + kCsqWords + 2) * 4);
+		uint32_t *const last = status + kCsHostLast;
+		unsigned long long *const ctr = (unsigned long long *) (status + kCsHostCtr);
+		const size_t ctr_n = ctr_words + 16;
+		memset(status, 0, (size_t) kCsHostCtr * 4 + ctr_n * 8);
 		m->cs_kernel_ms = 0;
 		float pass_ms[3] = {0, 0, 0};
 		auto timed = [&](int e) { float t = 0; if (hipEventElapsedTime(&t, m->cev[e], m->cev[e + 1]) == hipSuccess) { m->cs_kernel_ms += t; pass_ms[e / 2] = t; } };
@@ -287,8 +298,6 @@ int run_cs(ngm_mapper *m, int n, GpuStage *stage) {
 			return 0;
 		};
 		// regions -> one dense candidate array in read order, the per-read arrays and the counters -> host
-		std::vector<unsigned long long> ctr(ctr_words + 16);
-		uint32_t last[2] = {0, 0};
 		auto enqueue_finish = [&]() -> int {
 			MAP_HIP_TRY(rocprim::exclusive_scan(m->d_scan_tmp.p, tmp_bytes, m->d_cand_count.p, m->d_new_base.p, 0u, (size_t) n, rocprim::plus<uint32_t>(), m->st));
 			hipLaunchKernelGGL(compact_candidates_kernel, dim3((n + 255) / 256), dim3(256), 0, m->st, n, (const uint32_t *) m->d_status.p, m->d_cand_base.p, m->d_new_base.p, m->d_cand_count.p,
@@ -296,10 +305,11 @@ int run_cs(ngm_mapper *m, int n, GpuStage *stage) {
 			MAP_HIP_TRY(hipGetLastError());
 			MAP_HIP_TRY(hipMemcpyAsync(status, m->d_status.p, 64, hipMemcpyDeviceToHost, m->st));
 			MAP_HIP_TRY(hipMemcpyAsync(ctl, m->d_heavy_ctr.p, kCsqWords * 4, hipMemcpyDeviceToHost, m->st));
-			MAP_HIP_TRY(hipMemcpyAsync(ctr.data(), m->d_counters.p, ctr.size() * 8, hipMemcpyDeviceToHost, m->st));
+			MAP_HIP_TRY(hipMemcpyAsync(ctr, m->d_counters.p, ctr_n * 8, hipMemcpyDeviceToHost, m->st));
 			// the host needs the number of candidates now (it sizes the score stage); the per-read arrays (12 bytes per read) only after the score stage
 			MAP_HIP_TRY(hipMemcpyAsync(&last[0], m->d_new_base.p + (n - 1), 4, hipMemcpyDeviceToHost, m->st));
 			MAP_HIP_TRY(hipMemcpyAsync(&last[1], m->d_cand_count.p + (n - 1), 4, hipMemcpyDeviceToHost, m->st));
+			if (defer) return 0;   // (cs_enqueue_host_arrays / cs_host_arrays: for the attempt that succeeds only)
 			MAP_HIP_TRY(hipMemcpyAsync(m->h_base.data(), m->d_new_base.p, (size_t) n * 4, hipMemcpyDeviceToHost, m->st));
 			MAP_HIP_TRY(hipMemcpyAsync(m->h_count.data(), m->d_cand_count.p, (size_t) n * 4, hipMemcpyDeviceToHost, m->st));
 			MAP_HIP_TRY(hipMemcpyAsync(m->h_maxv.data(), m->d_max_votes.p, (size_t) n * 4, hipMemcpyDeviceToHost, m->st));
@@ -413,8 +423,11 @@ int run_cs(ngm_mapper *m, int n, GpuStage *stage) {
 				const size_t lds = cs_canon_lds_bytes(A, m->cs_canon) - 96;  // (the kernel has no static LDS: its shared variables are the last 160 bytes of this)
 				// persistent workgroups: as many as the GPU holds at once, each walking the reads with that stride
 				const void *fn = cs_canon_fn(m->cs_canon, A.bin_shift);
-				int per_cu = 0;
-				if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kCanonT[m->cs_canon] * 64, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+				int &per_cu = m->canon_per_cu;   // (a query per launch before: host time at the head of the turn)
+				if (per_cu <= 0 || m->canon_fn != fn || m->canon_lds != lds) {
+					if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kCanonT[m->cs_canon] * 64, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+					m->canon_fn = fn; m->canon_lds = lds;
+				}
 				const int grid = std::min(n, per_cu * m->cus);
 				void *kargs[] = {(void *) &A};
 				MAP_HIP_TRY(hipLaunchKernel(fn, dim3(grid), dim3(kCanonT[m->cs_canon] * 64), kargs, lds, m->st));
@@ -544,6 +557,7 @@ int run_cs(ngm_mapper *m, int n, GpuStage *stage) {
 			m->cs_region_cap = cap;
 			m->n_reads = n;
 			m->n_cand = (uint64_t) last[0] + last[1];
+			if (defer) { m->cs_arrays_state = 1; m->turn_dbg[0] = 1; }
 			{
 				// the 32-bit prefix sums wrap silently: cross-check the total against the 64-bit candidate counters
 				unsigned long long sum = 0;
@@ -553,7 +567,7 @@ int run_cs(ngm_mapper *m, int n, GpuStage *stage) {
 			m->st_heavy += n_heavy; m->st_reads += (uint64_t) n; m->st_cands += m->n_cand; m->st_exact_lds += n_exact_lds; m->st_exact_global += n_exact_global;
 			m->cs_kmers = m->cs_hits = 0;
 			for (int g = 0; g < kCsRegions; ++g) { m->cs_kmers += ctr[(size_t) g * kCsCursorStride]; m->cs_hits += ctr[(size_t) g * kCsCursorStride + 1]; }
-			const unsigned long long *ph = ctr.data() + ctr_words;
+			const unsigned long long *ph = ctr + ctr_words;
 			if (A.phase_cycles)
 				fprintf(stderr, "[ngm-hip] cs fast path, 100 MHz ticks per read: lists %.1f sweep1 %.1f sweep2 %.1f candidates %.1f; %u of %d reads re-run by the exact path; kernels %.2f + %.2f + %.2f ms\n",
 						(double) ph[0] * 256 / n, (double) ph[1] * 256 / n, (double) ph[2] * 256 / n, (double) ph[3] * 256 / n, m->cs_queued_exact, n, pass_ms[0], pass_ms[1], pass_ms[2]);
@@ -568,8 +582,26 @@ int run_cs(ngm_mapper *m, int n, GpuStage *stage) {
 	return -75;
 }
 
-// h_base / h_count / h_maxv of the last search are complete when run_cs returns (they travel with its one synchronisation)
-int cs_host_arrays(ngm_mapper *) { return 0; }
+// h_base / h_count / h_maxv of the last search: complete when run_cs returns (they travel with its one synchronisation) unless it was
+// told to defer them.  Then they are read from where the search left them (d_cand_base holds the compacted bases since the swap at its
+// end; no later stage writes the three device arrays), behind whatever the caller has enqueued on the stream in between.
+int cs_enqueue_host_arrays(ngm_mapper *m) {
+	if (m->cs_arrays_state != 1) return 0;
+	const size_t n = (size_t) m->n_reads;
+	MAP_HIP_TRY(hipMemcpyAsync(m->h_base.data(), m->d_cand_base.p, n * 4, hipMemcpyDeviceToHost, m->st));
+	MAP_HIP_TRY(hipMemcpyAsync(m->h_count.data(), m->d_cand_count.p, n * 4, hipMemcpyDeviceToHost, m->st));
+	MAP_HIP_TRY(hipMemcpyAsync(m->h_maxv.data(), m->d_max_votes.p, n * 4, hipMemcpyDeviceToHost, m->st));
+	m->cs_arrays_state = 2;
+	return 0;
+}
+
+int cs_host_arrays(ngm_mapper *m) {
+	if (m->cs_arrays_state == 0) return 0;
+	if (int rc = cs_enqueue_host_arrays(m)) return rc;
+	MAP_HIP_TRY(hipStreamSynchronize(m->st));
+	m->cs_arrays_state = 0;
+	return 0;
+}
 
 // ---- candidate ORDER ----------------------------------------------------------------------------------------------------------------
 namespace {
@@ -749,6 +781,7 @@ int candidate_order_wait(ngm_mapper *m, uint32_t **h_rank) {
 
 int candidate_order(ngm_mapper *m, const std::vector<uint32_t> &list, uint64_t np, uint32_t **h_rank, bool wait) {
 	const uint32_t nl = (uint32_t) list.size();
+	if (int rc = cs_host_arrays(m)) return rc;   // (the replay reads bases and counts on the host)
 	if (m->prm.slam_seq & 4) {
 		// the weighted SLAM-seq search replays the votes in the reference's order anyway: its candidates leave in rList order
 		if (m->p_rank.reserve(np + 1)) { pipeline_set_error("out of memory (candidate order)"); return -12; }

@@ -92,6 +92,7 @@ def _lib():
         lib.ngm_mapper_path_counters.argtypes = [C.c_void_p, C.c_void_p]
         lib.ngm_mapper_order_table_reads.argtypes = [C.c_void_p, C.c_void_p]
         lib.ngm_mapper_heavy_counters.argtypes = [C.c_void_p, C.c_void_p]
+        lib.ngm_mapper_search_turn_counters.argtypes = [C.c_void_p, C.c_void_p]
         lib.ngm_mapper_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         lib.ngm_mapper_last_order_replay_ms.restype = C.c_float
         lib.ngm_mapper_last_order_replay_ms.argtypes = [C.c_void_p]
@@ -699,6 +700,12 @@ class Mapper:
         out = np.zeros(4, np.uint64)
         self.lib.ngm_mapper_heavy_counters(self.h, out.ctypes.data)
         return dict(zip(("second_passes", "table_pass_restarts", "sent_on", "pool_regrown"), (int(x) for x in out)))
+
+    def search_turn_counters(self):
+        """of the last map call: per-read search arrays deferred behind the score stage (0/1), search attempts, buffers regrown inside the turn"""
+        out = np.zeros(3, np.uint64)
+        self.lib.ngm_mapper_search_turn_counters(self.h, out.ctypes.data)
+        return dict(zip(("arrays_deferred", "search_attempts", "buffers_regrown"), (int(x) for x in out)))
 
     def order_table_reads(self):
         """of path_counters()["order_exact_global"]: the reads the bucket replay left to the replay with a table in global memory"""
