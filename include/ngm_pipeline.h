@@ -387,6 +387,60 @@ int ngm_snp_stats(const ngm_snp *s, uint64_t counts[5], float ms[4]);
  * ngm_snp_add. */
 int ngm_mapper_set_snp(ngm_mapper *m, ngm_snp *s);
 
+/* ---- `ngm-hip --count` (csrc/count.cpp): per-region T>C conversion counts of a run ("--count", holds the definition).
+ * Counters exist only for the bases some region covers: the regions of a contig are merged into disjoint intervals, and every base of
+ * their union has two uint32 (cov, conv) in the device's memory for the whole run -- 8 bytes per base of the union, about 0.5 GB for all
+ * human 3' UTRs -- plus two uint64 (reads, tc_reads) per region.  The records that count are ngm_coverage's.  An M, = or X column inside
+ * the contig is eligible when the reference base (case folded) is T under a forward record or A under a reverse one, the read base is one
+ * of ACGT, and the record has no quality text or the column's Phred quality is at least min_qual; it adds 1 to cov, and 1 to conv when the
+ * read base is C (forward) or G (reverse).  A region of strand '+' takes forward records, '-' reverse ones, '.' both: reads counts the
+ * records it takes with an M / = / X column inside it, tc_reads those of them with a conversion inside it.  The finish sums cov and conv
+ * over every region's positions whose reference base is T ('+'), A ('-') or either ('.') and that are not in the mask; tc_reads is taken
+ * at add time and ignores the mask.  All sums are integers: the result depends on the set of alignments, the regions, the reference and
+ * the mask only.  Errors: < 0 with ngm_pipeline_last_error(); the object stays destroyable after every error. */
+typedef struct ngm_count ngm_count;
+typedef struct ngm_count_params {
+	int device;
+	int n_ref;
+	const uint32_t *ref_len;
+	const char *const *ref_name;     /* not read by the object (the caller prints the names) */
+	const char *const *ref_seq;      /* one ASCII string of ref_len[c] letters per contig (ngm_count_create only) */
+	int min_qual;                    /* Q, 0..93 (slamdunk count's default: 27) */
+	size_t n_regions;                /* at least 1; regions may overlap, nest, repeat and come in any order */
+	const int32_t *region_ref;       /* [n_regions] contig index */
+	const uint32_t *region_start;    /* [n_regions] 0-based */
+	const uint32_t *region_end;      /* [n_regions] exclusive, start < end <= ref_len */
+	const char *region_strand;       /* [n_regions] '+', '-' or '.' */
+} ngm_count_params;
+/* allocates and zeroes 8 bytes per base of the regions' union (and one bit per base for the mask) plus 64 bytes per region on the device
+ * and uploads the reference packed to 4 bits per base; NULL with the error set ("out of device memory ...") when that fails */
+ngm_count *ngm_count_create(const ngm_count_params *p);
+/* the same over the contigs of r, on r's device, reading r's resident packed genome instead of a copy (n_ref, ref_len, ref_name, ref_seq
+ * and device of p are not read); r must outlive the object */
+ngm_count *ngm_count_create_for_ref(const ngm_ref *r, const ngm_count_params *p);
+void ngm_count_destroy(ngm_count *c);
+/* n alignments as ngm_snp_add takes them, and reverse[i] != 0 for a record with flag bit 0x10.  Thread-safe.  Validated on the host as
+ * ngm_snp_add validates: -22 with "ngm_count_add: alignment <i>: ..." names the first one refused, and nothing of the call is added.
+ * -22 after ngm_count_finish. */
+int ngm_count_add(ngm_count *c, const int32_t *ref_id, const int32_t *pos0, const uint32_t *cigar_off /* [n + 1] */, const char *cigar_text,
+                  const uint32_t *seq_off /* [n + 1] */, const char *seq_text, const char *qual_text, const uint8_t *reverse /* [n] */, size_t n);
+/* n positions (contig, 0-based) join the mask; any time before ngm_count_finish, thread-safe.  Positions outside every region are
+ * ignored; -22 for a ref_id outside [0, n_ref) or a position outside its contig, and then nothing of the call is taken. */
+int ngm_count_mask(ngm_count *c, const int32_t *ref_id, const int32_t *pos0, size_t n);
+/* no add after this; waits for the adds in flight, uploads the mask and sums every region (one wave per region) */
+int ngm_count_finish(ngm_count *c);
+/* after the finish: six numbers per region, regions in the order given -- t_bases, masked, cov_on_ts, conv_on_ts, reads, tc_reads.
+ * Returns the number of regions (out NULL: only that); -22 when n_regions is another number. */
+long long ngm_count_read(ngm_count *c, int64_t *out /* [n_regions][6] */, size_t n_regions);
+/* counts: alignments added, alignments that some region took, eligible columns and conversions inside the regions' union, distinct mask
+ * positions inside it; ms: kernel ms of add / reduce (HIP events).  Thread-safe beside add and mask; the four device counters are those
+ * of the adds that have returned. */
+int ngm_count_stats(const ngm_count *c, uint64_t counts[5], float ms[2]);
+/* every batch ngm_mapper_map_sam* finishes adds the records ngm_mapper_set_coverage would add to c, in place from the batch's arrays in
+ * device memory, on the mapper's stream; NULL detaches.  When c lives on another device, the batch's arrays are downloaded and go through
+ * ngm_count_add. */
+int ngm_mapper_set_count(ngm_mapper *m, ngm_count *c);
+
 /* page-locked host memory for read batches (the H2D copy then runs at PCIe rate without a staging copy) */
 void *ngm_host_alloc(size_t bytes);
 void ngm_host_free(void *p);

@@ -1,7 +1,7 @@
 // cli_format.h -- the host formatter of `ngm-hip`: mapping results -> SAM lines or BAM records, the output filter, the pair writer.
 // It is what the GPU writers (csrc/sam_device.h) are compared against, and it is the route of -n > 1, --broken-pairs,
 // NGM_HIP_HOST_SAM=1 and NGM_HIP_BAM_HOST_RECORDS=1.  Plain host code: the types of the C ABI, no call into the library -- what it
-// needs from outside (reference classes for the SLAM-seq tags, where the --coverage / --snp records go) comes through callbacks.
+// needs from outside (reference classes for the SLAM-seq tags, where the --coverage / --snp / --count records go) comes through callbacks.
 //   output filter                    src/writer/GenericReadWriter.h:190-254 (min_identity, min_residues), min_mq
 //   SAM records                      src/writer/SAMWriter.cpp:98-228, :230-373
 //   BAM records                      src/writer/BAMWriter.cpp:147-375, :428-433
@@ -47,9 +47,10 @@ inline void put_identity(std::string &s, float identity) {
 	s.append(b, k);
 }
 
-// what one format_range call hands to --coverage and --snp: its records without 0x100, as the arrays ngm_coverage_add / ngm_snp_add take
+// what one format_range call hands to --coverage, --snp and --count: its records without 0x100, as the arrays ngm_coverage_add / ngm_snp_add /
+// ngm_count_add take (rev: flag bit 0x10 of each record)
 struct CovAcc { std::vector<int32_t> ref, pos; std::vector<uint32_t> off; std::string text; };
-struct SnpAcc { std::vector<int32_t> ref, pos; std::vector<uint32_t> off, seq_off; std::string text, seq, qual; };
+struct SnpAcc { std::vector<int32_t> ref, pos; std::vector<uint32_t> off, seq_off; std::vector<uint8_t> rev; std::string text, seq, qual; };
 
 struct HostFormatter {
 	// ---- set once per run ----
@@ -62,9 +63,10 @@ struct HostFormatter {
 	size_t stride = 0;     // bytes per CIGAR / MD row
 	int min_insert = 0, max_insert = 2147483647;
 	std::function<void(int contig, uint64_t pos, int span, uint8_t *out)> ref_classes;   // --slam-seq: the classes of `span` reference bases (ngm_ref_host_classes)
-	// --coverage / --snp: set = wanted.  Called once per range that has such records (snp: once for those without a quality string, once for those with)
+	// --coverage / --snp / --count: set = wanted.  Called once per range that has such records (snp, count: once for those without a quality
+	// string, once for those with)
 	std::function<void(const CovAcc &)> add_coverage;
-	std::function<void(const SnpAcc &, bool has_qual)> add_snp;
+	std::function<void(const SnpAcc &, bool has_qual)> add_snp, add_count;
 
 	void set_read_group(const std::string &id) {
 		rg_id = id;
@@ -171,9 +173,10 @@ struct HostFormatter {
 			a.ref.push_back(h.contig); a.pos.push_back((int32_t) h.pos); a.off.push_back((uint32_t) a.text.size());
 			a.text += v.cigar;
 		}
-		if (side && add_snp && !(flags & 0x100)) {   // the sequence and the qualities as the record prints them
+		if (side && (add_snp || add_count) && !(flags & 0x100)) {   // the sequence and the qualities as the record prints them
 			SnpAcc &a = side->snp[noq ? 0 : 1];
 			a.ref.push_back(h.contig); a.pos.push_back((int32_t) h.pos); a.off.push_back((uint32_t) a.text.size()); a.seq_off.push_back((uint32_t) a.seq.size());
+			a.rev.push_back(h.reverse ? 1 : 0);
 			a.text += v.cigar;
 			a.seq.resize(a.seq.size() + sl);
 			oriented_seq(v, s0, sl, &a.seq[a.seq.size() - sl]);
@@ -352,17 +355,18 @@ struct HostFormatter {
 		}
 	}
 	// records [lo, hi) of a batch (paired: lo and hi even) -> SAM text or BAM records appended to s, the counters added to c; the range's
-	// records without 0x100 go to --coverage and --snp in one call each when the range is done
+	// records without 0x100 go to --coverage, --snp and --count in one call each when the range is done
 	void format_range(const Input &in, int lo, int hi, std::string &s, Counts &c) const {
 		Side side;
-		Side *sp = (add_coverage || add_snp) ? &side : nullptr;
+		Side *sp = (add_coverage || add_snp || add_count) ? &side : nullptr;
 		s.reserve((size_t) (hi - lo) * (size_t) (2 * q + 160));
 		if (paired) format_pairs(in, lo, hi, s, c, sp); else format_single_end(in, lo, hi, s, c, sp);
-		for (int k = 0; add_snp && k < 2; ++k) {
+		for (int k = 0; (add_snp || add_count) && k < 2; ++k) {
 			SnpAcc &a = side.snp[k];
 			if (a.ref.empty()) continue;
 			a.off.push_back((uint32_t) a.text.size()); a.seq_off.push_back((uint32_t) a.seq.size());
-			add_snp(a, k == 1);
+			if (add_snp) add_snp(a, k == 1);
+			if (add_count) add_count(a, k == 1);
 		}
 		if (add_coverage && !side.cov.ref.empty()) {
 			side.cov.off.push_back((uint32_t) side.cov.text.size());

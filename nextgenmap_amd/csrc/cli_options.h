@@ -30,6 +30,8 @@ struct Opts {
 	std::string snp, snp_frac_text = "0.8";   // --snp FILE (ours): SNP calls of the mapped primary records as VCF, made on the GPU (csrc/snp.cpp); --snp-min-frac as given
 	long snp_min_cov = 10, snp_min_qual = 15;   // --snp-min-cov, --snp-min-qual
 	double snp_min_frac = 0.8;
+	std::string count, count_out;   // --count FILE, --count-out FILE (ours): T>C conversion counts per region of the BED file, made on the GPU (csrc/count.cpp)
+	long count_min_qual = 27;       // --count-min-qual (slamdunk count's -q)
 	ngm::trim::Options trim;   // -5/--trim5, --max-polya (Options.h:103-104)
 	float argos_min = 0.f;   // --argos-min-score (Default(ARGOS_MINSCORE, 0), Config.cpp:505)
 	int bs_mapping = 0, bs_cutoff = 6, match_tt = -1, match_tc = -1, match_set = 0, mismatch_set = 0, slam_seq = 0;
@@ -52,7 +54,7 @@ inline Opts parse(int argc, char **argv) {
 	Opts o;
 	for (int i = 1; i < argc; ++i) { if (i > 1) o.cmdline += " "; o.cmdline += argv[i]; }  // Config.cpp:565-574
 	enum { KSKIP = 1000, HARD, SILENT, KMIN, MB, MMP, GRP, GFP, MAXCMRS, NOUNAL, NOPROG, MAXRL, BINSZ, MAXKF, VFAST, FAST, SENS, VSENS, DEVICE,
-		SKIPSAVE, BATCH, VARIANT, SHARD, SHARDOUT, KEEPSHARDS, BAMOUT, WORKERS, SERIAL, AFFINE, GEP, PEDELIM, STRATA, BSMAP, BSCUT, MBTT, MBTC, SLAM, FASTPAIR, BROKENPAIRS, REFSCOREBUF, STATSFD, MAXPOLYA, RG0, RG_LAST = RG0 + 11, ARGOS, ARGOSMIN, VCF, KEEPTAGS, PARSEALL, SORTOUT, COVERAGE, SNP, SNPCOV, SNPFRAC, SNPQUAL, UNSUPPORTED };
+		SKIPSAVE, BATCH, VARIANT, SHARD, SHARDOUT, KEEPSHARDS, BAMOUT, WORKERS, SERIAL, AFFINE, GEP, PEDELIM, STRATA, BSMAP, BSCUT, MBTT, MBTC, SLAM, FASTPAIR, BROKENPAIRS, REFSCOREBUF, STATSFD, MAXPOLYA, RG0, RG_LAST = RG0 + 11, ARGOS, ARGOSMIN, VCF, KEEPTAGS, PARSEALL, SORTOUT, COVERAGE, SNP, SNPCOV, SNPFRAC, SNPQUAL, COUNT, COUNTOUT, COUNTQUAL, UNSUPPORTED };
 	static const option lo[] = {
 		{"ref", required_argument, 0, 'r'}, {"qry", required_argument, 0, 'q'}, {"output", required_argument, 0, 'o'},
 		{"cpu-threads", required_argument, 0, 't'}, {"gpu", no_argument, 0, 'g'}, {"sensitivity", required_argument, 0, 's'},
@@ -80,6 +82,7 @@ inline Opts parse(int argc, char **argv) {
 		{"argos", no_argument, 0, ARGOS}, {"argos-min-score", required_argument, 0, ARGOSMIN}, {"vcf", required_argument, 0, VCF},
 		{"keep-tags", no_argument, 0, KEEPTAGS}, {"parse-all", no_argument, 0, PARSEALL}, {"sort", no_argument, 0, SORTOUT}, {"coverage", required_argument, 0, COVERAGE},
 		{"snp", required_argument, 0, SNP}, {"snp-min-cov", required_argument, 0, SNPCOV}, {"snp-min-frac", required_argument, 0, SNPFRAC}, {"snp-min-qual", required_argument, 0, SNPQUAL},
+		{"count", required_argument, 0, COUNT}, {"count-out", required_argument, 0, COUNTOUT}, {"count-min-qual", required_argument, 0, COUNTQUAL},
 		{"trim5", required_argument, 0, '5'}, {"max-polya", required_argument, 0, MAXPOLYA}, {"config", required_argument, 0, UNSUPPORTED},
 		{0, 0, 0, 0}};
 	int c, idx = 0;
@@ -171,6 +174,9 @@ inline Opts parse(int argc, char **argv) {
 		case SNPCOV: { char *e = nullptr; o.snp_min_cov = strtol(optarg, &e, 10); if (e == optarg || *e || o.snp_min_cov < 0 || o.snp_min_cov > 2147483647L) die("--snp-min-cov expects a count of 0 or more"); break; }
 		case SNPFRAC: { char *e = nullptr; o.snp_min_frac = strtod(optarg, &e); o.snp_frac_text = optarg; if (e == optarg || *e || !(o.snp_min_frac > 0.0 && o.snp_min_frac <= 1.0)) die("--snp-min-frac expects a fraction in (0, 1]"); break; }
 		case SNPQUAL: { char *e = nullptr; o.snp_min_qual = strtol(optarg, &e, 10); if (e == optarg || *e || o.snp_min_qual < 0 || o.snp_min_qual > 93) die("--snp-min-qual expects a Phred quality in 0..93"); break; }
+		case COUNT: o.count = optarg; if (o.count.empty()) die("--count expects a BED file name"); break;
+		case COUNTOUT: o.count_out = optarg; if (o.count_out.empty()) die("--count-out expects a file name"); break;
+		case COUNTQUAL: { char *e = nullptr; o.count_min_qual = strtol(optarg, &e, 10); if (e == optarg || *e || o.count_min_qual < 0 || o.count_min_qual > 93) die("--count-min-qual expects a Phred quality in 0..93"); break; }
 		case UNSUPPORTED: die(std::string("option --") + lo[idx].name + " is not supported by the HIP backend yet");
 		default: die("unknown option (see src/config/Options.h of NextGenMap for the option set)");
 		}
@@ -200,6 +206,18 @@ inline Opts parse(int argc, char **argv) {
 		if (!o.vcf.empty()) die("--snp cannot be combined with --vcf: calling over an index built with known variants is not checked");
 		if (o.snp == o.out) die("--snp cannot be combined with -o " + o.out + ": the calls and the records need a file each");
 		if (o.snp == o.coverage) die("--snp cannot be combined with --coverage " + o.coverage + ": the calls and the depth need a file each");
+	}
+	if (!o.count.empty() || !o.count_out.empty()) {
+		// the counts are over the records of the whole run, kept in the first GPU's memory; refused before any GPU work
+		if (o.count.empty()) die("--count-out needs --count FILE: the BED file of the regions to count in");
+		if (o.count_out.empty()) die("--count needs --count-out FILE: where the counts are written");
+		if (o.argos) die("--count cannot be combined with --argos: argos scores candidates, no alignments are made");
+		if (o.shard_n > 1) die("--count cannot be combined with --shard: the counts are over the whole run, not over one shard of it");
+		if (o.shard_output) die("--count cannot be combined with --shard-output: the counts are over the whole run, in one process");
+		if (o.bs_mapping) die("--count cannot be combined with --bs-mapping: bisulfite conversions are not SLAM-seq labelling, and they are not told apart");
+		if (o.count_out == o.out) die("--count cannot be combined with -o " + o.out + ": the counts and the records need a file each");
+		if (o.count_out == o.coverage) die("--count cannot be combined with --coverage " + o.coverage + ": the counts and the depth need a file each");
+		if (o.count_out == o.snp) die("--count cannot be combined with --snp " + o.snp + ": the counts and the calls need a file each");
 	}
 	if (o.argos) {
 		// ScoreWriter has no paired or binary form (DoWritePair throws, src/writer/ScoreWriter.cpp:75-77); refused before any GPU work

@@ -9,6 +9,7 @@
 #define NGM_COV_BATCH_KERNELS
 #include "coverage_device.h"
 #include "snp_device.h"
+#include "count_device.h"
 #include <rocprim/rocprim.hpp>
 #include "align_device.h"
 #include "gather_device.h"
@@ -1495,8 +1496,19 @@ static int map_impl(ngm_mapper *m, int n, const char *reads, const void *d_reads
 			MAP_HIP_TRY(hipGetLastError());
 			MAP_HIP_TRY(hipEventRecord(m->cev[5], m->st));
 		}
-		const bool cov_away = m->coverage && units > 0 && !cov_here, snp_away = m->snp && units > 0 && !snp_here;
-		if (cov_away || snp_away) {
+		// --count: the same records add their eligible columns and their regions' read counts to the run's conversion counters (count_device.h)
+		const bool count_here = m->count && units > 0 && ngm::count_device(m->count) == r->device;
+		if (count_here) {
+			ngm::cnt::Layout count_tab{};
+			ngm::cnt::Counters count_to{};
+			if (int rc = ngm::count_target(m->count, &count_tab, &count_to)) return rc;
+			MAP_HIP_TRY(hipEventRecord(m->cev[6], m->st));
+			hipLaunchKernelGGL(ngm::cnt::count_add_kernel<ngm::cnt::CountBatch>, dim3((units + 255) / 256), dim3(256), 0, m->st, ngm::cnt::CountBatch{ngm::snp::SnpBatch{S, units}}, count_tab, count_to);
+			MAP_HIP_TRY(hipGetLastError());
+			MAP_HIP_TRY(hipEventRecord(m->cev[7], m->st));
+		}
+		const bool cov_away = m->coverage && units > 0 && !cov_here, snp_away = m->snp && units > 0 && !snp_here, count_away = m->count && units > 0 && !count_here;
+		if (cov_away || snp_away || count_away) {
 			if (m->d_cov_mask.reserve((size_t) units)) { ngm::pipeline_set_error("out of device memory (coverage)"); return -12; }
 			hipLaunchKernelGGL(ngm::cov::cov_mask_kernel, dim3((units + 255) / 256), dim3(256), 0, m->st, S, units, m->d_cov_mask.p);
 			MAP_HIP_TRY(hipGetLastError());
@@ -1511,7 +1523,8 @@ static int map_impl(ngm_mapper *m, int n, const char *reads, const void *d_reads
 		sam->text_bytes = (long long) total;
 		if (cov_here) { float t = 0; if (hipEventElapsedTime(&t, m->cev[2], m->cev[3]) == hipSuccess) ngm::coverage_note_add_ms(m->coverage, t); }
 		if (snp_here) { float t = 0; if (hipEventElapsedTime(&t, m->cev[4], m->cev[5]) == hipSuccess) ngm::snp_note_add_ms(m->snp, t); }
-		if (cov_away || snp_away) {
+		if (count_here) { float t = 0; if (hipEventElapsedTime(&t, m->cev[6], m->cev[7]) == hipSuccess) ngm::count_note_add_ms(m->count, t); }
+		if (cov_away || snp_away || count_away) {
 			// the object lives on another device: which reads count and the CIGAR texts come down
 			const size_t str_bytes = (size_t) str_base + extra.size();
 			m->cov_mask.resize((size_t) units); m->cov_text.resize(str_bytes + 1);
@@ -1532,9 +1545,10 @@ static int map_impl(ngm_mapper *m, int n, const char *reads, const void *d_reads
 			m->cov_off.push_back((uint32_t) packed.size());
 			if (int rc = ngm_coverage_add(m->coverage, m->cov_ref.data(), m->cov_pos.data(), m->cov_off.data(), packed.data(), m->cov_ref.size())) return rc;
 		}
-		if (snp_away) {
+		if (snp_away || count_away) {
 			// ... with the read rows; the sequences and qualities are put as the records print them (bam_mapped, sam_device.h) and the arrays
-			// go through ngm_snp_add -- the records with a quality string and those without one in a call each
+			// go through ngm_snp_add and ngm_count_add (with the records' strands) -- the records with a quality string and those without one in
+			// a call each
 			m->snp_rows.resize((size_t) n * q);
 			MAP_HIP_TRY(hipMemcpy(m->snp_rows.data(), m->d_reads.p, (size_t) n * q, hipMemcpyDeviceToHost));
 			const ngm::SamMeta *meta = (const ngm::SamMeta *) sam->meta;
@@ -1544,6 +1558,7 @@ static int map_impl(ngm_mapper *m, int n, const char *reads, const void *d_reads
 			for (int with_q = 0; with_q < 2; ++with_q) {
 				std::vector<int32_t> s_ref, s_pos;
 				std::vector<uint32_t> c_off, s_off;
+				std::vector<uint8_t> s_rev;
 				std::string c_text, s_text, q_text;
 				for (int u = 0; u < units; ++u) for (int k = 0; k < per; ++k) {
 					if (!((m->cov_mask[u] >> k) & 1)) continue;
@@ -1556,6 +1571,7 @@ static int map_impl(ngm_mapper *m, int n, const char *reads, const void *d_reads
 					const int sl = std::max(0, std::min(clip ? L - hits[i].qstart - hits[i].qend : L, L - s0));
 					const int QL = std::min(qlen, L);
 					s_ref.push_back(hits[i].contig); s_pos.push_back((int32_t) hits[i].pos); c_off.push_back((uint32_t) c_text.size()); s_off.push_back((uint32_t) s_text.size());
+					s_rev.push_back(hits[i].reverse ? 1 : 0);
 					c_text.append(m->cov_text.data() + sam_refs[i].cig_off, sam_refs[i].cig_len);
 					for (int t = 0; t < sl; ++t) {
 						if (!hits[i].reverse) { s_text.push_back((char) row[s0 + t]); if (with_q) q_text.push_back(s0 + t < QL ? (char) qrow[s0 + t] : ':'); }
@@ -1568,7 +1584,8 @@ static int map_impl(ngm_mapper *m, int n, const char *reads, const void *d_reads
 				}
 				c_off.push_back((uint32_t) c_text.size()); s_off.push_back((uint32_t) s_text.size());
 				if (s_ref.empty()) continue;
-				if (int rc = ngm_snp_add(m->snp, s_ref.data(), s_pos.data(), c_off.data(), c_text.data(), s_off.data(), s_text.data(), with_q ? q_text.c_str() : nullptr, s_ref.size())) return rc;
+				if (snp_away) if (int rc = ngm_snp_add(m->snp, s_ref.data(), s_pos.data(), c_off.data(), c_text.data(), s_off.data(), s_text.data(), with_q ? q_text.c_str() : nullptr, s_ref.size())) return rc;
+				if (count_away) if (int rc = ngm_count_add(m->count, s_ref.data(), s_pos.data(), c_off.data(), c_text.data(), s_off.data(), s_text.data(), with_q ? q_text.c_str() : nullptr, s_rev.data(), s_ref.size())) return rc;
 			}
 		}
 		float bgzf_ms = 0.f;
@@ -1627,6 +1644,7 @@ int ngm_mapper_set_fast_pairing(ngm_mapper *m, int on) { if (!m) return -22; m->
 int ngm_mapper_set_bam_sorter(ngm_mapper *m, ngm_bam_sort *s) { if (!m) return -22; m->sorter = s; return 0; }
 int ngm_mapper_set_coverage(ngm_mapper *m, ngm_coverage *c) { if (!m) return -22; m->coverage = c; return 0; }
 int ngm_mapper_set_snp(ngm_mapper *m, ngm_snp *s) { if (!m) return -22; m->snp = s; return 0; }
+int ngm_mapper_set_count(ngm_mapper *m, ngm_count *c) { if (!m) return -22; m->count = c; return 0; }
 
 void *ngm_host_alloc(size_t bytes) {
 	void *p = nullptr;

@@ -17,7 +17,9 @@
 // contig above 2^29 bases), and --coverage FILE (ours: the per-base depth of the run's mapped primary records as bedGraph, counted and turned into text on the
 // GPU, csrc/coverage.cpp; not with --argos, --shard, --shard-output, nor FILE = the output), and --snp FILE with --snp-min-cov / --snp-min-frac /
 // --snp-min-qual (ours: the mismatch pileup of the same records and its single-base substitution calls as VCF, counted and turned into text on the GPU,
-// csrc/snp.cpp; not with --argos, --shard, --shard-output, --bs-mapping, --vcf, nor FILE = the output or the --coverage file).  Not supported (rejected loudly): --vcf with --bs-mapping, --max-polya with --argos or --vcf, --config.
+// csrc/snp.cpp; not with --argos, --shard, --shard-output, --bs-mapping, --vcf, nor FILE = the output or the --coverage file), and --count BED --count-out FILE
+// with --count-min-qual (ours: T>C conversion counts of the same records per region of the BED file, counted and summed on the GPU, the positions --snp calls
+// left out, csrc/count.cpp; not with --argos, --shard, --shard-output, --bs-mapping, nor FILE = another output).  Not supported (rejected loudly): --vcf with --bs-mapping, --max-polya with --argos or --vcf, --config.
 //
 // Pass 2 is a pipeline, not a loop:
 //   splitter (1 thread)   cuts the input into batches: for plain 4-line FASTQ it only counts line ends in the mapped file
@@ -49,6 +51,7 @@
 #include "cli_format.h"
 #include "cli_input.h"
 #include "cli_options.h"
+#include "count.h"
 
 using namespace ngm::cli;
 
@@ -352,10 +355,14 @@ struct Run {
 	ngm_bam_sort *sorter = nullptr;
 	ngm_coverage *coverage = nullptr;
 	ngm_snp *snp = nullptr;
-	FILE *coverage_file = nullptr, *snp_file = nullptr;
+	ngm_count *counter = nullptr;
+	std::vector<ngm::cnt::Region> count_regions;   // --count: the BED file's regions, read before any GPU work
+	std::vector<std::string> count_names;          // ... and the contigs they were checked against (the FASTA's, as the reference will hold them)
+	std::vector<uint32_t> count_lens;
+	FILE *coverage_file = nullptr, *snp_file = nullptr, *count_file = nullptr;
 	HostFormatter fmt;
 	std::atomic<uint64_t> pair_stat[3];   // AlignmentBuffer::WriteRead's pair counters, summed over the run (the GPU formatter counts the same: ngm_mapper_last_pair_stats)
-	std::atomic<bool> cov_failed{false}, snp_failed{false};   // an ngm_coverage_add / ngm_snp_add of a formatted range failed: the run fails behind its batch
+	std::atomic<bool> cov_failed{false}, snp_failed{false}, count_failed{false};   // an ngm_coverage_add / ngm_snp_add / ngm_count_add of a formatted range failed: the run fails behind its batch
 	// the pipeline
 	std::unique_ptr<BoundedQueue<std::unique_ptr<Batch>>> q_in;
 	std::mutex out_mu, fail_mu, text_mu, spare_mu;
@@ -383,7 +390,7 @@ struct Run {
 	Run() { for (auto &x : pair_stat) x = 0; }
 	~Run() { if (estimate_thread.joinable()) estimate_thread.join(); }
 	// before the pipeline
-	void refuse_by_input_format(); void join_communicator(); void request_pinned_early(); void load_reference(); void scan_input();
+	void read_count_regions(); void refuse_by_input_format(); void join_communicator(); void request_pinned_early(); void load_reference(); void scan_input();
 	void run_estimate(ngm_mapper_params ep, float &sens, bool &estimated, bool logged_only); void estimate_sensitivity();
 	void write_header(); void create_mappers_and_side_outputs(); void setup_formatter(); void take_pinned();
 	// the pipeline's threads
@@ -394,7 +401,7 @@ struct Run {
 	bool gpu_bgzf_chunks(Worker &w, Batch &b); void recycle_input(Batch &b); void hand_to_writer(std::unique_ptr<Batch> &b, bool wait);
 	// behind it
 	void finish_sort(); void drain_side_outputs(); void report(double secs); void report_search_paths(); void teardown();
-	template <class Finish, class Next> void drain(Finish finish, Next next, FILE *&file, const std::string &path, const char *tag);
+	template <class Finish, class Next> void drain(Finish finish, Next next, FILE *&file, const std::string &path, const char *tag, const std::function<void(const char *, size_t)> &tap = nullptr);
 
 	// (every waiter looks at `failed`: wake them all -- ADVICE r3)
 	void fail(const std::string &m2) {
@@ -428,6 +435,42 @@ struct Run {
 		if (len >= 2 && name[len - 2] == o.pe_delimiter) len -= 2;
 	}
 };
+
+// --count: the BED file is read and checked against the contigs of the FASTA (names up to the first blank, 100 characters at most, contigs of
+// 10 bases or fewer dropped: what refindex.cpp keeps) before any GPU work, so that a bad line costs no index build
+void Run::read_count_regions() {
+	if (o.count.empty()) return;
+	gzFile f = gzopen(o.ref.c_str(), "rb");
+	if (!f) die("--count: cannot open reference " + o.ref);
+	std::string name;
+	uint64_t len = 0;
+	bool have = false, in_name = false, name_done = false, line_start = true;
+	auto flush = [&]() { if (have && len > 10) { count_names.push_back(name.substr(0, 100)); count_lens.push_back((uint32_t) std::min<uint64_t>(len, 0xffffffffull)); } };
+	std::vector<char> buf(1 << 20);
+	int got;
+	while ((got = gzread(f, buf.data(), (unsigned) buf.size())) > 0) {
+		for (int i = 0; i < got; ++i) {
+			const char ch = buf[i];
+			if (ch == '\n') { line_start = true; in_name = false; continue; }
+			if (line_start && ch == '>') { flush(); name.clear(); len = 0; have = true; in_name = true; name_done = false; line_start = false; continue; }
+			line_start = false;
+			if (in_name) { if (ch == ' ' || ch == '\t') name_done = true; else if (!name_done && ch != '\r') name.push_back(ch); }
+			else if (have && ch != ' ' && ch != '\t' && ch != '\r') ++len;
+		}
+	}
+	flush();
+	gzclose(f);
+	FILE *b = fopen(o.count.c_str(), "rb");
+	if (!b) die("--count: cannot read " + o.count);
+	std::string text;
+	char chunk[65536];
+	for (size_t k; (k = fread(chunk, 1, sizeof(chunk), b)) > 0;) text.append(chunk, k);
+	fclose(b);
+	std::vector<const char *> names;
+	for (const std::string &n : count_names) names.push_back(n.c_str());
+	std::string err;
+	if (!ngm::cnt::parse_bed(text, (int) names.size(), names.data(), count_lens.data(), count_regions, &err)) die("--count: " + o.count + " " + err);
+}
 
 // SAM / BAM input (ReadProvider::DetermineParser): known from the first bytes, so that what it does not go with is refused before any GPU work
 void Run::refuse_by_input_format() {
@@ -783,6 +826,28 @@ void Run::create_mappers_and_side_outputs() {
 		infof("MAIN", "SNP counters: %.1f MiB on GPU %d (16 bytes per base of the reference, held for the whole run)", (double) (bases + contig_lens.size()) * 16.0 / (double) (1 << 20), o.devices[0]);
 		if (route.gpu_sam) for (Worker &w : workers) if (ngm_mapper_set_snp(w.m, snp) < 0) die(ngm_pipeline_last_error());
 	}
+	if (!o.count.empty()) {   // two counters per base of the union of the regions and two per region, beside that GPU's resident reference
+		// (the regions were checked against the FASTA's contigs: they must be the reference's, whether it was built or loaded from its cache)
+		bool same = count_names.size() == contig_names.size();
+		for (size_t i = 0; same && i < contig_names.size(); ++i) same = count_names[i] == contig_names[i] && count_lens[i] == contig_lens[i];
+		if (!same) die("--count: the contigs read from " + o.ref + " for the BED file (" + std::to_string(count_names.size()) + ") are not the reference's (" + std::to_string(contig_names.size()) +
+				"): either the index cache next to it was built from another FASTA (delete it to rebuild it), or the file has a form the two readers take differently");
+		count_file = fopen(o.count_out.c_str(), "wb");   // (before the run, not after it)
+		if (!count_file) die("cannot write " + o.count_out);
+		std::vector<int32_t> r_ref;
+		std::vector<uint32_t> r_start, r_end;
+		std::string r_strand;
+		for (const ngm::cnt::Region &r : count_regions) { r_ref.push_back(r.contig); r_start.push_back(r.start); r_end.push_back(r.end); r_strand.push_back(r.strand); }
+		ngm_count_params cp{};
+		cp.min_qual = (int) o.count_min_qual; cp.n_regions = count_regions.size(); cp.region_ref = r_ref.data(); cp.region_start = r_start.data(); cp.region_end = r_end.data(); cp.region_strand = r_strand.data();
+		counter = ngm_count_create_for_ref(refs[0], &cp);
+		if (!counter) die(std::string("--count: ") + ngm_pipeline_last_error());
+		ngm::cnt::Tables tab;
+		tab.build(count_regions, (int) contig_names.size());
+		infof("MAIN", "Conversion counters: %zu regions over %llu bases, %.1f MiB on GPU %d (8 bytes per base of the regions' union, held for the whole run)", count_regions.size(),
+				(unsigned long long) tab.slots, (double) tab.slots * 8.0 / (double) (1 << 20), o.devices[0]);
+		if (route.gpu_sam) for (Worker &w : workers) if (ngm_mapper_set_count(w.m, counter) < 0) die(ngm_pipeline_last_error());
+	}
 }
 
 // the host formatter (cli_format.h), built once from plain values
@@ -798,6 +863,9 @@ void Run::setup_formatter() {
 	if (coverage) fmt.add_coverage = [this](const CovAcc &a) { if (ngm_coverage_add(coverage, a.ref.data(), a.pos.data(), a.off.data(), a.text.data(), a.ref.size()) < 0) cov_failed = true; };
 	if (snp) fmt.add_snp = [this](const SnpAcc &a, bool has_qual) {
 		if (ngm_snp_add(snp, a.ref.data(), a.pos.data(), a.off.data(), a.text.data(), a.seq_off.data(), a.seq.data(), has_qual ? a.qual.c_str() : nullptr, a.ref.size()) < 0) snp_failed = true;
+	};
+	if (counter) fmt.add_count = [this](const SnpAcc &a, bool has_qual) {
+		if (ngm_count_add(counter, a.ref.data(), a.pos.data(), a.off.data(), a.text.data(), a.seq_off.data(), a.seq.data(), has_qual ? a.qual.c_str() : nullptr, a.rev.data(), a.ref.size()) < 0) count_failed = true;
 	};
 }
 
@@ -1169,6 +1237,7 @@ void Run::host_format_route(Worker &w, std::unique_ptr<Batch> &b, PairTurn &turn
 	}
 	if (cov_failed) { fail(std::string("--coverage: ") + ngm_pipeline_last_error()); return; }
 	if (snp_failed) { fail(std::string("--snp: ") + ngm_pipeline_last_error()); return; }
+	if (count_failed) { fail(std::string("--count: ") + ngm_pipeline_last_error()); return; }
 	if (route.gpu_bgzf && !gpu_bgzf_chunks(w, *b)) return;
 	recycle_input(*b);
 	t_format_us += us_since(tf);
@@ -1315,7 +1384,7 @@ void Run::finish_sort() {
 
 // --coverage, --snp: every batch has added its records.  The counters become text chunk by chunk on the GPU (finish, then next until it
 // returns 0; more than the buffer holds: nothing was copied, ask again with a larger one); the text is streamed into the file
-template <class Finish, class Next> void Run::drain(Finish finish, Next next, FILE *&file, const std::string &path, const char *tag) {
+template <class Finish, class Next> void Run::drain(Finish finish, Next next, FILE *&file, const std::string &path, const char *tag, const std::function<void(const char *, size_t)> &tap) {
 	FILE *f = file;
 	size_t cap = (size_t) 8 << 20;
 	std::vector<char> buf(cap);
@@ -1326,6 +1395,7 @@ template <class Finish, class Next> void Run::drain(Finish finish, Next next, FI
 		if (got == 0) break;
 		if ((size_t) got > cap) { cap = (size_t) got; buf.resize(cap); continue; }
 		if (fwrite(buf.data(), 1, (size_t) got, f) != (size_t) got) { fail("write error on " + path); break; }
+		if (tap) tap(buf.data(), (size_t) got);   // (whole lines)
 	}
 	file = nullptr;
 	if (fclose(f) != 0) fail("write error on " + path);
@@ -1345,7 +1415,36 @@ void Run::drain_side_outputs() {
 	}
 	if (snp && !failed) {
 		const auto t_snp = Clock::now();
-		drain([&] { return ngm_snp_finish(snp); }, [&](char *p, size_t n) { return ngm_snp_next(snp, p, n); }, snp_file, o.snp, "--snp: ");
+		// --count with --snp: every position the VCF calls, whatever the ALT, joins the count's mask -- read off the lines as they are written
+		std::vector<int32_t> m_ref, m_pos;
+		std::map<std::string, int32_t> by_name;
+		if (counter) for (size_t i = 0; i < contig_names.size(); ++i) by_name.emplace(contig_names[i], (int32_t) i);
+		std::function<void(const char *, size_t)> tap;
+		// (the pieces are cut wherever they are cut: a line is taken when its end has come, so nothing rests on how the text is framed; a data
+		// line that does not give a contig of the reference and a position fails the run instead of leaving a hole in the mask)
+		std::string pending, bad_line;
+		auto take_line = [&](const char *p, const char *end) {
+			if (p == end || *p == '#') return;
+			const char *t1 = (const char *) memchr(p, '\t', (size_t) (end - p));
+			const auto it = t1 ? by_name.find(std::string(p, t1)) : by_name.end();
+			long long pos1 = 0;
+			for (const char *d = t1 ? t1 + 1 : end; d < end && *d >= '0' && *d <= '9' && pos1 < (1ll << 40); ++d) pos1 = pos1 * 10 + (*d - '0');
+			if (it == by_name.end() || pos1 <= 0 || pos1 > 2147483647ll) { if (bad_line.empty()) bad_line.assign(p, end); return; }
+			m_ref.push_back(it->second); m_pos.push_back((int32_t) (pos1 - 1));
+		};
+		if (counter) tap = [&](const char *p, size_t n) {
+			for (const char *e = p + n; p < e;) {
+				const char *nl = (const char *) memchr(p, '\n', (size_t) (e - p));
+				if (!nl) { pending.append(p, e); break; }
+				if (pending.empty()) take_line(p, nl);
+				else { pending.append(p, nl); take_line(pending.data(), pending.data() + pending.size()); pending.clear(); }
+				p = nl + 1;
+			}
+		};
+		drain([&] { return ngm_snp_finish(snp); }, [&](char *p, size_t n) { return ngm_snp_next(snp, p, n); }, snp_file, o.snp, "--snp: ", tap);
+		if (counter && !pending.empty()) take_line(pending.data(), pending.data() + pending.size());   // (a last line without its newline)
+		if (counter && !failed && !bad_line.empty()) fail("--count: a line of " + o.snp + " gives no position of the reference for the mask: " + bad_line.substr(0, 80));
+		if (counter && !failed && ngm_count_mask(counter, m_ref.data(), m_pos.data(), m_ref.size()) < 0) fail(std::string("--count: ") + ngm_pipeline_last_error());
 		if (!failed) {
 			uint64_t sc[5] = {0, 0, 0, 0, 0};
 			float sms[4] = {0, 0, 0, 0};
@@ -1353,6 +1452,28 @@ void Run::drain_side_outputs() {
 			infof("MAIN", "SNPs on the GPU: %llu alignments, %llu mismatching bases counted, %llu calls, %llu bytes of VCF; kernels: add %.2f ms, scan %.2f ms, flag %.2f ms, text %.2f ms; "
 					"%llu covered bases; %.3f s after the last batch", (unsigned long long) sc[0], (unsigned long long) sc[1], (unsigned long long) sc[2], (unsigned long long) sc[3], sms[0], sms[1], sms[2], sms[3],
 					(unsigned long long) sc[4], span_s(t_snp));
+		}
+	}
+	if (counter && !failed) {   // (behind --snp: its calls are the mask)
+		const auto t_count = Clock::now();
+		std::vector<int64_t> six(count_regions.size() * 6, 0);
+		if (ngm_count_finish(counter) < 0 || ngm_count_read(counter, six.data(), count_regions.size()) < 0) fail(std::string("--count: ") + ngm_pipeline_last_error());
+		else {
+			std::vector<const char *> names;
+			for (const std::string &n : contig_names) names.push_back(n.c_str());
+			const std::string text = ngm::cnt::serialise(count_regions, names.data(), six.data());
+			if (fwrite(text.data(), 1, text.size(), count_file) != text.size()) fail("write error on " + o.count_out);
+		}
+		FILE *f = count_file;
+		count_file = nullptr;
+		if (fclose(f) != 0) fail("write error on " + o.count_out);
+		if (!failed) {
+			uint64_t kc[5] = {0, 0, 0, 0, 0};
+			float kms[2] = {0, 0};
+			(void) ngm_count_stats(counter, kc, kms);
+			infof("MAIN", "Conversions on the GPU: %llu alignments, %llu of them in a region, %llu eligible columns, %llu conversions, %llu masked positions in %zu regions; "
+					"kernels: add %.2f ms, reduce %.2f ms; %.3f s after the last batch", (unsigned long long) kc[0], (unsigned long long) kc[1], (unsigned long long) kc[2], (unsigned long long) kc[3],
+					(unsigned long long) kc[4], count_regions.size(), kms[0], kms[1], span_s(t_count));
 		}
 	}
 }
@@ -1466,6 +1587,8 @@ void Run::teardown() {
 	if (coverage_file) fclose(coverage_file);
 	ngm_snp_destroy(snp);
 	if (snp_file) fclose(snp_file);
+	ngm_count_destroy(counter);
+	if (count_file) fclose(count_file);
 	for (TextBuf &t : text_free) ngm_host_free(t.p);
 	ngm_pair_state_destroy(pair_state);
 	for (ngm_ref *r2 : refs) ngm_ref_destroy(r2);
@@ -1485,6 +1608,7 @@ int main(int argc, char **argv) {
 	R.o = parse(argc, argv);
 	const Opts &o = R.o;
 	R.refuse_by_input_format();
+	R.read_count_regions();
 	if (o.shard_output && (o.devices.size() > 1 || getenv("NGM_HIP_SHARD_SINGLE")) && o.shard_n == 1 && o.stats_fd < 0 && !o.out.empty() && !(o.qry.empty() && o.qry1.empty())) return run_sharded(argc, argv, o);   // (a shard process has its parent's --stats-fd)
 	R.join_communicator();
 	// bisulfite mapping: the index holds every reference k-mer, the run's kmer_skip applies to the reads (src/PrefixTable.cpp:199-207, src/CS.cpp:556-560)

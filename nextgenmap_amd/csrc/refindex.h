@@ -133,6 +133,12 @@ namespace snp { struct Target; }
 int snp_device(const struct ::ngm_snp *c);
 int snp_target(struct ::ngm_snp *c, snp::Target *t);
 void snp_note_add_ms(struct ::ngm_snp *c, float ms);
+// count.cpp, the same three for a conversion counter: the tables and counters a count_add_kernel on its device works with (count.h's Layout,
+// count_device.h's Counters)
+namespace cnt { struct Layout; struct Counters; }
+int count_device(const struct ::ngm_count *c);
+int count_target(struct ::ngm_count *c, cnt::Layout *l, cnt::Counters *t);
+void count_note_add_ms(struct ::ngm_count *c, float ms);
 // k-mer integer as the reference builds it: 2 bits per base, A0 C1 T2 G3 ((c >> 1) & 3, CSstatic.cpp:20-22)
 inline uint32_t kmer_code_of_class(uint32_t cls) { return cls == 2 ? 3u : (cls == 3 ? 2u : cls); }
 // reverse complement of a k-mer integer (PrefixTable.cpp:94-108), valid for 2k <= 32

@@ -47,6 +47,11 @@ class SnpParams(C.Structure):   # ngm_snp_params
                 ("min_cov", C.c_uint32), ("min_frac", C.c_double), ("min_qual", C.c_int), ("min_frac_text", C.c_char_p), ("scan_chunk", C.c_size_t)]
 
 
+class CountParams(C.Structure):   # ngm_count_params
+    _fields_ = [("device", C.c_int), ("n_ref", C.c_int), ("ref_len", C.POINTER(C.c_uint32)), ("ref_name", C.POINTER(C.c_char_p)), ("ref_seq", C.POINTER(C.c_char_p)),
+                ("min_qual", C.c_int), ("n_regions", C.c_size_t), ("region_ref", C.c_void_p), ("region_start", C.c_void_p), ("region_end", C.c_void_p), ("region_strand", C.c_char_p)]
+
+
 def _lib():
     global _bound
     lib = load_library()
@@ -153,6 +158,18 @@ def _lib():
         lib.ngm_snp_next.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         lib.ngm_snp_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.ngm_mapper_set_snp.argtypes = [C.c_void_p, C.c_void_p]
+        lib.ngm_count_create.restype = C.c_void_p
+        lib.ngm_count_create.argtypes = [C.POINTER(CountParams)]
+        lib.ngm_count_create_for_ref.restype = C.c_void_p
+        lib.ngm_count_create_for_ref.argtypes = [C.c_void_p, C.POINTER(CountParams)]
+        lib.ngm_count_destroy.argtypes = [C.c_void_p]
+        lib.ngm_count_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t]
+        lib.ngm_count_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.ngm_count_finish.argtypes = [C.c_void_p]
+        lib.ngm_count_read.restype = C.c_longlong
+        lib.ngm_count_read.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.ngm_count_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.ngm_mapper_set_count.argtypes = [C.c_void_p, C.c_void_p]
         _bound = True
     return lib
 
@@ -345,6 +362,118 @@ class Coverage:
     def close(self):
         if self._h:
             _lib().ngm_coverage_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ConversionCounter:
+    """T>C conversion counts per region, counted in GPU memory (include/ngm_pipeline.h, ngm_count_*): what `ngm-hip --count` writes.
+    contigs: [(name, sequence)]; regions: [(contig index, start, end, name, strand)], start 0-based, end exclusive, strand '+', '-' or '.';
+    reference: a Reference whose resident genome is read instead (contigs then only names the contigs for tsv())."""
+
+    HEADER = "#chrom\tstart\tend\tname\tstrand\tt_bases\tmasked\tcov_on_ts\tconv_on_ts\treads\ttc_reads\n"
+
+    def __init__(self, contigs, regions, device=0, min_qual=27, reference=None):
+        b = lambda x: x.encode() if isinstance(x, str) else bytes(x)
+        self._regions = [(int(c), int(s), int(e), name, strand) for c, s, e, name, strand in regions]
+        self._names = [nm.decode() if isinstance(nm, bytes) else nm for nm, _ in contigs]
+        self._r_ref = np.array([r[0] for r in self._regions], dtype=np.int32)
+        self._r_start = np.array([r[1] for r in self._regions], dtype=np.uint32)
+        self._r_end = np.array([r[2] for r in self._regions], dtype=np.uint32)
+        self._r_strand = b("".join(r[4] if r[4] else "?" for r in self._regions))
+        p = CountParams()
+        p.device, p.min_qual, p.n_regions = device, min_qual, len(self._regions)
+        p.region_ref, p.region_start, p.region_end, p.region_strand = self._r_ref.ctypes.data, self._r_start.ctypes.data, self._r_end.ctypes.data, self._r_strand
+        if reference is not None:
+            self._ref = reference   # (it must outlive this object)
+            self._h = _lib().ngm_count_create_for_ref(reference.h, C.byref(p))
+        else:
+            n = len(contigs)
+            self._seq_bytes = [b(sq) for _, sq in contigs]
+            self._len = (C.c_uint32 * max(1, n))(*[len(sq) for sq in self._seq_bytes])
+            self._name = (C.c_char_p * max(1, n))(*[b(nm) for nm, _ in contigs])
+            self._seq = (C.c_char_p * max(1, n))(*self._seq_bytes)
+            p.n_ref, p.ref_len, p.ref_name, p.ref_seq = n, self._len, self._name, self._seq
+            self._h = _lib().ngm_count_create(C.byref(p))
+        if not self._h:
+            raise _err()
+
+    def add(self, records):
+        """[(contig index, 0-based position, CIGAR text, sequence, qualities or None, reverse)]: all with qualities or all without; raises
+        on the first record the validator refuses, adding nothing"""
+        records = list(records)
+        b = lambda x: x.encode() if isinstance(x, str) else bytes(x)
+        cig = [b(r[2]) for r in records]
+        seq = [b(r[3]) for r in records]
+        with_q = [r[4] is not None for r in records]
+        if any(with_q) and not all(with_q):
+            raise ValueError("records with and without qualities go into separate calls")
+        qual = None
+        if records and all(with_q):
+            if any(len(r[4]) != len(sq) for r, sq in zip(records, seq)):
+                raise ValueError("a quality string has another length than its sequence")
+            qual = b"".join(b(r[4]) for r in records)
+        off = np.zeros(len(cig) + 1, dtype=np.uint32)
+        off[1:] = np.cumsum([len(c) for c in cig], dtype=np.uint64)
+        soff = np.zeros(len(seq) + 1, dtype=np.uint32)
+        soff[1:] = np.cumsum([len(c) for c in seq], dtype=np.uint64)
+        self.add_arrays(np.array([r[0] for r in records], dtype=np.int32), np.array([r[1] for r in records], dtype=np.int32), off, b"".join(cig), soff, b"".join(seq), qual,
+                        np.array([1 if r[5] else 0 for r in records], dtype=np.uint8))
+
+    def add_arrays(self, ref_id, pos0, cigar_off, cigar_text, seq_off, seq_text, qual_text, reverse):
+        ref_id = np.ascontiguousarray(ref_id, dtype=np.int32)
+        pos0 = np.ascontiguousarray(pos0, dtype=np.int32)
+        cigar_off = np.ascontiguousarray(cigar_off, dtype=np.uint32)
+        seq_off = np.ascontiguousarray(seq_off, dtype=np.uint32)
+        reverse = np.ascontiguousarray(reverse, dtype=np.uint8)
+        if len(pos0) != len(ref_id) or len(reverse) != len(ref_id) or len(cigar_off) != len(ref_id) + 1 or len(seq_off) != len(ref_id) + 1:
+            raise ValueError("ref_id, pos0, reverse of n entries and cigar_off, seq_off of n + 1")
+        if _lib().ngm_count_add(self._h, ref_id.ctypes.data, pos0.ctypes.data, cigar_off.ctypes.data, bytes(cigar_text), seq_off.ctypes.data, bytes(seq_text),
+                                None if qual_text is None else bytes(qual_text), reverse.ctypes.data, len(ref_id)) < 0:
+            raise _err()
+
+    def mask(self, positions):
+        """[(contig index, 0-based position)] join the mask; positions outside every region are ignored"""
+        positions = list(positions)
+        ref_id = np.array([c for c, _ in positions], dtype=np.int32)
+        pos0 = np.array([p for _, p in positions], dtype=np.int32)
+        if _lib().ngm_count_mask(self._h, ref_id.ctypes.data, pos0.ctypes.data, len(positions)) < 0:
+            raise _err()
+
+    def finish(self):
+        if _lib().ngm_count_finish(self._h) < 0:
+            raise _err()
+
+    def read(self):
+        """after finish(): int64[n_regions, 6] -- t_bases, masked, cov_on_ts, conv_on_ts, reads, tc_reads"""
+        out = np.zeros((len(self._regions), 6), dtype=np.int64)
+        if _lib().ngm_count_read(self._h, out.ctypes.data, len(self._regions)) < 0:
+            raise _err()
+        return out
+
+    def tsv(self):
+        """after finish(): the file `ngm-hip --count-out` writes, as bytes"""
+        rows = self.read().tolist()
+        return (self.HEADER + "".join("%s\t%d\t%d\t%s\t%s\t%s\n" % (self._names[c], s, e, name, strand, "\t".join(str(x) for x in row))
+                                      for (c, s, e, name, strand), row in zip(self._regions, rows))).encode()
+
+    def stats(self):
+        counts = (C.c_uint64 * 5)()
+        ms = (C.c_float * 2)()
+        if _lib().ngm_count_stats(self._h, counts, ms) < 0:
+            raise _err()
+        d = dict(zip(("alignments", "met_a_region", "eligible_columns", "conversions", "masked_positions"), (int(x) for x in counts)))
+        d.update(zip(("add_ms", "reduce_ms"), (float(x) for x in ms)))
+        return d
+
+    def close(self):
+        if self._h:
+            _lib().ngm_count_destroy(self._h)
             self._h = None
 
     def __del__(self):
@@ -668,6 +797,12 @@ class Mapper:
         """every batch map_sam finishes adds its mapped primary records to `coverage` (a Coverage, or None to detach)"""
         if self.lib.ngm_mapper_set_coverage(self.h, coverage._h if coverage is not None else None) < 0:
             raise _err()
+
+    def set_count(self, count):
+        """every batch map_sam finishes adds its mapped primary records to `count` (a ConversionCounter, or None to detach)"""
+        if self.lib.ngm_mapper_set_count(self.h, count._h if count is not None else None) < 0:
+            raise _err()
+        self._count = count
 
     def set_snp(self, snp):
         """every batch map_sam finishes adds its mapped primary records to `snp` (a SnpCaller, or None to detach)"""
