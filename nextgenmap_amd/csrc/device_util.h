@@ -1,9 +1,11 @@
-// device_util.h -- what the host sides of the run-long side outputs (bam_sort.cpp, coverage.cpp, snp.cpp) share: device memory that frees
-// itself, a guard for the calling thread's device, the launch grid of the 256-thread kernels, and the HIP error check of the C ABI.
+// device_util.h -- what the host sides of the run-long side outputs (bam_sort.cpp, and through side_output.h coverage.cpp, snp.cpp and
+// count.cpp) share: device memory that frees itself and takes a host vector, a guard for the calling thread's device, the launch grid of
+// the 256-thread kernels, and the HIP error check of the C ABI.
 #pragma once
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 #include <hip/hip_runtime.h>
 
@@ -38,6 +40,11 @@ struct Buf {   // device memory: alloc() of exactly the size asked for, grow() w
 	Buf(const Buf &) = delete;
 	Buf &operator=(const Buf &) = delete;
 };
+
+// a host vector into a buffer of exactly its size (true: placed; the copy is through once st is synchronised)
+template <typename T> bool put(Buf<T> &b, const std::vector<T> &v, hipStream_t st) {
+	return !b.alloc(v.size()) && (v.empty() || hipMemcpyAsync(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, st) == hipSuccess);
+}
 
 struct DeviceGuard {   // a call from a thread that works on another GPU leaves that thread's device as it was
 	int prev = -1;

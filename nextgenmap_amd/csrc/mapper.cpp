@@ -10,6 +10,7 @@
 #include "coverage_device.h"
 #include "snp_device.h"
 #include "count_device.h"
+#include "side_output.h"
 #include <rocprim/rocprim.hpp>
 #include "align_device.h"
 #include "gather_device.h"
@@ -636,6 +637,74 @@ static int launch_pair_select(hipStream_t st, size_t npairs, const uint32_t *can
 			(const uint32_t *) huge_list, (const uint32_t *) huge_count, cand_base, cand_count, scores, loc, read_len, min_d, max_d, cutoff,
 			out + npairs, tops, tied_n, (uint32_t) npairs, (uint32_t *) nullptr, (uint32_t *) nullptr, (const uint32_t *) (list + npairs));
 	MAP_HIP_TRY(hipGetLastError());
+	return 0;
+}
+
+// The side outputs (--coverage, --snp, --count) of a SAM batch whose object lives on another device than the mapper: cov_mask_kernel has said
+// which records count; they, the CIGAR texts and, for --snp and --count, the read rows come down and go through ngm_*_add.
+static int side_outputs_away(ngm_mapper *m, bool cov_away, bool snp_away, bool count_away, int n, int q, int units, bool paired, const ngm_hit *hits, const ngm::SamRef *sam_refs,
+		size_t str_bytes, const SamCall *sam) {
+	// the object lives on another device: which reads count and the CIGAR texts come down
+	m->cov_mask.resize((size_t) units); m->cov_text.resize(str_bytes + 1);
+	MAP_HIP_TRY(hipMemcpy(m->cov_mask.data(), m->d_cov_mask.p, (size_t) units, hipMemcpyDeviceToHost));
+	if (str_bytes) MAP_HIP_TRY(hipMemcpy(m->cov_text.data(), m->d_str.p, str_bytes, hipMemcpyDeviceToHost));
+	if (cov_away) {
+		// ... and the arrays go through ngm_coverage_add
+		m->cov_ref.clear(); m->cov_pos.clear(); m->cov_off.clear();
+		std::vector<char> packed;
+		const int per = paired ? 2 : 1;
+		for (int u = 0; u < units; ++u) for (int k = 0; k < per; ++k) {
+			if (!((m->cov_mask[u] >> k) & 1)) continue;
+			const int i = per * u + k;
+			m->cov_ref.push_back(hits[i].contig); m->cov_pos.push_back((int32_t) hits[i].pos); m->cov_off.push_back((uint32_t) packed.size());
+			packed.insert(packed.end(), m->cov_text.data() + sam_refs[i].cig_off, m->cov_text.data() + sam_refs[i].cig_off + sam_refs[i].cig_len);
+		}
+		m->cov_off.push_back((uint32_t) packed.size());
+		if (int rc = ngm_coverage_add(m->coverage, m->cov_ref.data(), m->cov_pos.data(), m->cov_off.data(), packed.data(), m->cov_ref.size())) return rc;
+	}
+	if (snp_away || count_away) {
+		// ... with the read rows; the sequences and qualities are put as the records print them (bam_mapped, sam_device.h) and the arrays
+		// go through ngm_snp_add and ngm_count_add (with the records' strands) -- the records with a quality string and those without one in
+		// a call each
+		m->snp_rows.resize((size_t) n * q);
+		MAP_HIP_TRY(hipMemcpy(m->snp_rows.data(), m->d_reads.p, (size_t) n * q, hipMemcpyDeviceToHost));
+		const ngm::SamMeta *meta = (const ngm::SamMeta *) sam->meta;
+		const uint8_t *quals = (const uint8_t *) sam->quals;
+		const int per = paired ? 2 : 1;
+		const bool clip = m->prm.hard_clip || m->prm.silent_clip;
+		for (int with_q = 0; with_q < 2; ++with_q) {
+			std::vector<int32_t> s_ref, s_pos;
+			std::vector<uint32_t> c_off, s_off;
+			std::vector<uint8_t> s_rev;
+			std::string c_text, s_text, q_text;
+			for (int u = 0; u < units; ++u) for (int k = 0; k < per; ++k) {
+				if (!((m->cov_mask[u] >> k) & 1)) continue;
+				const int i = per * u + k;
+				const int qlen = meta[i].qual_len & 0x7FFF;
+				if ((qlen != 0) != (with_q != 0)) continue;
+				const uint8_t *row = m->snp_rows.data() + (size_t) i * q, *qrow = quals + (size_t) i * q;
+				const int L = (int) strnlen((const char *) row, (size_t) q);
+				const int s0 = std::max(0, std::min(clip ? hits[i].qstart : 0, L));
+				const int sl = std::max(0, std::min(clip ? L - hits[i].qstart - hits[i].qend : L, L - s0));
+				const int QL = std::min(qlen, L);
+				s_ref.push_back(hits[i].contig); s_pos.push_back((int32_t) hits[i].pos); c_off.push_back((uint32_t) c_text.size()); s_off.push_back((uint32_t) s_text.size());
+				s_rev.push_back(hits[i].reverse ? 1 : 0);
+				c_text.append(m->cov_text.data() + sam_refs[i].cig_off, sam_refs[i].cig_len);
+				for (int t = 0; t < sl; ++t) {
+					if (!hits[i].reverse) { s_text.push_back((char) row[s0 + t]); if (with_q) q_text.push_back(s0 + t < QL ? (char) qrow[s0 + t] : ':'); }
+					else {
+						const char ch = (char) row[L - 1 - (s0 + t)];
+						s_text.push_back(ch == 'A' ? 'T' : ch == 'T' ? 'A' : ch == 'C' ? 'G' : ch == 'G' ? 'C' : ch);
+						if (with_q) q_text.push_back(QL - 1 - (s0 + t) >= 0 ? (char) qrow[QL - 1 - (s0 + t)] : ':');
+					}
+				}
+			}
+			c_off.push_back((uint32_t) c_text.size()); s_off.push_back((uint32_t) s_text.size());
+			if (s_ref.empty()) continue;
+			if (snp_away) if (int rc = ngm_snp_add(m->snp, s_ref.data(), s_pos.data(), c_off.data(), c_text.data(), s_off.data(), s_text.data(), with_q ? q_text.c_str() : nullptr, s_ref.size())) return rc;
+			if (count_away) if (int rc = ngm_count_add(m->count, s_ref.data(), s_pos.data(), c_off.data(), c_text.data(), s_off.data(), s_text.data(), with_q ? q_text.c_str() : nullptr, s_rev.data(), s_ref.size())) return rc;
+		}
+	}
 	return 0;
 }
 
@@ -1472,42 +1541,37 @@ static int map_impl(ngm_mapper *m, int n, const char *reads, const void *d_reads
 			MAP_HIP_TRY(hipGetLastError());
 		}
 		MAP_HIP_TRY(hipEventRecord(e1, m->st));
-		// --coverage: the records just written as mapped ones add their blocks to the run's counters, from the same arrays, before the batch's
-		// buffers are reused (behind e1: not part of the SAM stage's time)
-		const bool cov_here = m->coverage && units > 0 && ngm::coverage_device(m->coverage) == r->device;
-		if (cov_here) {
-			int32_t *cov_counters = nullptr;
-			const uint64_t *cov_off = nullptr;
-			unsigned long long *cov_n = nullptr;
-			int cov_n_ref = 0;
-			if (int rc = ngm::coverage_target(m->coverage, &cov_counters, &cov_off, &cov_n_ref, &cov_n)) return rc;
-			MAP_HIP_TRY(hipEventRecord(m->cev[2], m->st));
-			hipLaunchKernelGGL(ngm::cov::cov_add_kernel<ngm::cov::CovBatch>, dim3((units + 255) / 256), dim3(256), 0, m->st, ngm::cov::CovBatch{S, units, cov_off}, cov_counters, cov_off, cov_n_ref, cov_n);
+		// --coverage, --snp, --count: the records just written as mapped ones add to the run's counters on this device (coverage_device.h:
+		// their blocks; snp_device.h: their depth blocks and their mismatching, qualifying columns; count_device.h: their eligible columns and
+		// their regions' read counts), from the same arrays, before the batch's buffers are reused (behind e1: not part of the SAM stage's time)
+		ngm::side::Base *const cov_b = ngm::side::base(m->coverage), *const snp_b = ngm::side::base(m->snp), *const count_b = ngm::side::base(m->count);
+		auto here = [&](const ngm::side::Base *b) { return b && units > 0 && ngm::side::device(b) == r->device; };
+		auto add_here = [&](ngm::side::Base *b, hipEvent_t *ev, auto launch) -> int {   // (nothing for an object that is elsewhere)
+			if (!here(b)) return 0;
+			MAP_HIP_TRY(hipEventRecord(ev[0], m->st));
+			launch();
 			MAP_HIP_TRY(hipGetLastError());
-			MAP_HIP_TRY(hipEventRecord(m->cev[3], m->st));
-		}
-		// --snp: the same records add their depth blocks and their mismatching, qualifying columns to the run's SNP counters (snp_device.h)
-		const bool snp_here = m->snp && units > 0 && ngm::snp_device(m->snp) == r->device;
-		if (snp_here) {
-			ngm::snp::Target snp_to{};
-			if (int rc = ngm::snp_target(m->snp, &snp_to)) return rc;
-			MAP_HIP_TRY(hipEventRecord(m->cev[4], m->st));
+			MAP_HIP_TRY(hipEventRecord(ev[1], m->st));
+			return 0;
+		};
+		auto note_here = [&](ngm::side::Base *b, hipEvent_t *ev) { float t = 0; if (here(b) && hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) ngm::side::note_add_ms(b, t); };
+		ngm::cov::Target cov_to{};
+		if (here(cov_b)) if (int rc = ngm::coverage_target(m->coverage, &cov_to)) return rc;
+		if (int rc = add_here(cov_b, m->cev + 2, [&] {
+			hipLaunchKernelGGL(ngm::cov::cov_add_kernel<ngm::cov::CovBatch>, dim3((units + 255) / 256), dim3(256), 0, m->st, ngm::cov::CovBatch{S, units, cov_to.off}, cov_to.counters, cov_to.off, cov_to.n_ref, cov_to.n_aln);
+		})) return rc;
+		ngm::snp::Target snp_to{};
+		if (here(snp_b)) if (int rc = ngm::snp_target(m->snp, &snp_to)) return rc;
+		if (int rc = add_here(snp_b, m->cev + 4, [&] {
 			hipLaunchKernelGGL(ngm::snp::snp_add_kernel<ngm::snp::SnpBatch>, dim3((units + 255) / 256), dim3(256), 0, m->st, ngm::snp::SnpBatch{S, units}, snp_to);
-			MAP_HIP_TRY(hipGetLastError());
-			MAP_HIP_TRY(hipEventRecord(m->cev[5], m->st));
-		}
-		// --count: the same records add their eligible columns and their regions' read counts to the run's conversion counters (count_device.h)
-		const bool count_here = m->count && units > 0 && ngm::count_device(m->count) == r->device;
-		if (count_here) {
-			ngm::cnt::Layout count_tab{};
-			ngm::cnt::Counters count_to{};
-			if (int rc = ngm::count_target(m->count, &count_tab, &count_to)) return rc;
-			MAP_HIP_TRY(hipEventRecord(m->cev[6], m->st));
+		})) return rc;
+		ngm::cnt::Layout count_tab{};
+		ngm::cnt::Counters count_to{};
+		if (here(count_b)) if (int rc = ngm::count_target(m->count, &count_tab, &count_to)) return rc;
+		if (int rc = add_here(count_b, m->cev + 6, [&] {
 			hipLaunchKernelGGL(ngm::cnt::count_add_kernel<ngm::cnt::CountBatch>, dim3((units + 255) / 256), dim3(256), 0, m->st, ngm::cnt::CountBatch{ngm::snp::SnpBatch{S, units}}, count_tab, count_to);
-			MAP_HIP_TRY(hipGetLastError());
-			MAP_HIP_TRY(hipEventRecord(m->cev[7], m->st));
-		}
-		const bool cov_away = m->coverage && units > 0 && !cov_here, snp_away = m->snp && units > 0 && !snp_here, count_away = m->count && units > 0 && !count_here;
+		})) return rc;
+		const bool cov_away = cov_b && units > 0 && !here(cov_b), snp_away = snp_b && units > 0 && !here(snp_b), count_away = count_b && units > 0 && !here(count_b);
 		if (cov_away || snp_away || count_away) {
 			if (m->d_cov_mask.reserve((size_t) units)) { ngm::pipeline_set_error("out of device memory (coverage)"); return -12; }
 			hipLaunchKernelGGL(ngm::cov::cov_mask_kernel, dim3((units + 255) / 256), dim3(256), 0, m->st, S, units, m->d_cov_mask.p);
@@ -1521,73 +1585,9 @@ static int map_impl(ngm_mapper *m, int n, const char *reads, const void *d_reads
 		stage_sam.done_after(e1);   // the text (~420 bytes per read) travels while the next instance's kernels run
 		MAP_HIP_TRY(hipStreamSynchronize(m->st));
 		sam->text_bytes = (long long) total;
-		if (cov_here) { float t = 0; if (hipEventElapsedTime(&t, m->cev[2], m->cev[3]) == hipSuccess) ngm::coverage_note_add_ms(m->coverage, t); }
-		if (snp_here) { float t = 0; if (hipEventElapsedTime(&t, m->cev[4], m->cev[5]) == hipSuccess) ngm::snp_note_add_ms(m->snp, t); }
-		if (count_here) { float t = 0; if (hipEventElapsedTime(&t, m->cev[6], m->cev[7]) == hipSuccess) ngm::count_note_add_ms(m->count, t); }
-		if (cov_away || snp_away || count_away) {
-			// the object lives on another device: which reads count and the CIGAR texts come down
-			const size_t str_bytes = (size_t) str_base + extra.size();
-			m->cov_mask.resize((size_t) units); m->cov_text.resize(str_bytes + 1);
-			MAP_HIP_TRY(hipMemcpy(m->cov_mask.data(), m->d_cov_mask.p, (size_t) units, hipMemcpyDeviceToHost));
-			if (str_bytes) MAP_HIP_TRY(hipMemcpy(m->cov_text.data(), m->d_str.p, str_bytes, hipMemcpyDeviceToHost));
-		}
-		if (cov_away) {
-			// ... and the arrays go through ngm_coverage_add
-			m->cov_ref.clear(); m->cov_pos.clear(); m->cov_off.clear();
-			std::vector<char> packed;
-			const int per = paired ? 2 : 1;
-			for (int u = 0; u < units; ++u) for (int k = 0; k < per; ++k) {
-				if (!((m->cov_mask[u] >> k) & 1)) continue;
-				const int i = per * u + k;
-				m->cov_ref.push_back(hits[i].contig); m->cov_pos.push_back((int32_t) hits[i].pos); m->cov_off.push_back((uint32_t) packed.size());
-				packed.insert(packed.end(), m->cov_text.data() + sam_refs[i].cig_off, m->cov_text.data() + sam_refs[i].cig_off + sam_refs[i].cig_len);
-			}
-			m->cov_off.push_back((uint32_t) packed.size());
-			if (int rc = ngm_coverage_add(m->coverage, m->cov_ref.data(), m->cov_pos.data(), m->cov_off.data(), packed.data(), m->cov_ref.size())) return rc;
-		}
-		if (snp_away || count_away) {
-			// ... with the read rows; the sequences and qualities are put as the records print them (bam_mapped, sam_device.h) and the arrays
-			// go through ngm_snp_add and ngm_count_add (with the records' strands) -- the records with a quality string and those without one in
-			// a call each
-			m->snp_rows.resize((size_t) n * q);
-			MAP_HIP_TRY(hipMemcpy(m->snp_rows.data(), m->d_reads.p, (size_t) n * q, hipMemcpyDeviceToHost));
-			const ngm::SamMeta *meta = (const ngm::SamMeta *) sam->meta;
-			const uint8_t *quals = (const uint8_t *) sam->quals;
-			const int per = paired ? 2 : 1;
-			const bool clip = m->prm.hard_clip || m->prm.silent_clip;
-			for (int with_q = 0; with_q < 2; ++with_q) {
-				std::vector<int32_t> s_ref, s_pos;
-				std::vector<uint32_t> c_off, s_off;
-				std::vector<uint8_t> s_rev;
-				std::string c_text, s_text, q_text;
-				for (int u = 0; u < units; ++u) for (int k = 0; k < per; ++k) {
-					if (!((m->cov_mask[u] >> k) & 1)) continue;
-					const int i = per * u + k;
-					const int qlen = meta[i].qual_len & 0x7FFF;
-					if ((qlen != 0) != (with_q != 0)) continue;
-					const uint8_t *row = m->snp_rows.data() + (size_t) i * q, *qrow = quals + (size_t) i * q;
-					const int L = (int) strnlen((const char *) row, (size_t) q);
-					const int s0 = std::max(0, std::min(clip ? hits[i].qstart : 0, L));
-					const int sl = std::max(0, std::min(clip ? L - hits[i].qstart - hits[i].qend : L, L - s0));
-					const int QL = std::min(qlen, L);
-					s_ref.push_back(hits[i].contig); s_pos.push_back((int32_t) hits[i].pos); c_off.push_back((uint32_t) c_text.size()); s_off.push_back((uint32_t) s_text.size());
-					s_rev.push_back(hits[i].reverse ? 1 : 0);
-					c_text.append(m->cov_text.data() + sam_refs[i].cig_off, sam_refs[i].cig_len);
-					for (int t = 0; t < sl; ++t) {
-						if (!hits[i].reverse) { s_text.push_back((char) row[s0 + t]); if (with_q) q_text.push_back(s0 + t < QL ? (char) qrow[s0 + t] : ':'); }
-						else {
-							const char ch = (char) row[L - 1 - (s0 + t)];
-							s_text.push_back(ch == 'A' ? 'T' : ch == 'T' ? 'A' : ch == 'C' ? 'G' : ch == 'G' ? 'C' : ch);
-							if (with_q) q_text.push_back(QL - 1 - (s0 + t) >= 0 ? (char) qrow[QL - 1 - (s0 + t)] : ':');
-						}
-					}
-				}
-				c_off.push_back((uint32_t) c_text.size()); s_off.push_back((uint32_t) s_text.size());
-				if (s_ref.empty()) continue;
-				if (snp_away) if (int rc = ngm_snp_add(m->snp, s_ref.data(), s_pos.data(), c_off.data(), c_text.data(), s_off.data(), s_text.data(), with_q ? q_text.c_str() : nullptr, s_ref.size())) return rc;
-				if (count_away) if (int rc = ngm_count_add(m->count, s_ref.data(), s_pos.data(), c_off.data(), c_text.data(), s_off.data(), s_text.data(), with_q ? q_text.c_str() : nullptr, s_rev.data(), s_ref.size())) return rc;
-			}
-		}
+		note_here(cov_b, m->cev + 2); note_here(snp_b, m->cev + 4); note_here(count_b, m->cev + 6);
+		if (cov_away || snp_away || count_away)
+			if (int rc = side_outputs_away(m, cov_away, snp_away, count_away, n, q, units, paired, hits, sam_refs, (size_t) str_base + extra.size(), sam)) return rc;
 		float bgzf_ms = 0.f;
 		if (bam && total > 0) {
 			// the records stay in HBM: their BGZF blocks are written there too (bgzf_device.h, the compressor's own stream -- beside the next

@@ -438,6 +438,13 @@ struct Run {
 
 // --count: the BED file is read and checked against the contigs of the FASTA (names up to the first blank, 100 characters at most, contigs of
 // 10 bases or fewer dropped: what refindex.cpp keeps) before any GPU work, so that a bad line costs no index build
+// a side output's file is opened before the run, not after it
+static FILE *open_before_run(const std::string &path) {
+	FILE *f = fopen(path.c_str(), "wb");
+	if (!f) die("cannot write " + path);
+	return f;
+}
+
 void Run::read_count_regions() {
 	if (o.count.empty()) return;
 	gzFile f = gzopen(o.ref.c_str(), "rb");
@@ -804,8 +811,7 @@ void Run::create_mappers_and_side_outputs() {
 	uint64_t bases = 0;
 	for (size_t i = 0; i < contig_lens.size(); ++i) bases += contig_lens[i];
 	if (!o.coverage.empty()) {
-		coverage_file = fopen(o.coverage.c_str(), "wb");   // (before the run, not after it)
-		if (!coverage_file) die("cannot write " + o.coverage);
+		coverage_file = open_before_run(o.coverage);
 		std::vector<uint32_t> lens32;
 		std::vector<const char *> names;
 		for (size_t i = 0; i < contig_lens.size(); ++i) { lens32.push_back((uint32_t) contig_lens[i]); names.push_back(contig_names[i].c_str()); }
@@ -817,8 +823,7 @@ void Run::create_mappers_and_side_outputs() {
 		if (route.gpu_sam) for (Worker &w : workers) if (ngm_mapper_set_coverage(w.m, coverage) < 0) die(ngm_pipeline_last_error());
 	}
 	if (!o.snp.empty()) {   // coverage's counters and three mismatch counters per base, beside that GPU's resident reference
-		snp_file = fopen(o.snp.c_str(), "wb");   // (before the run, not after it)
-		if (!snp_file) die("cannot write " + o.snp);
+		snp_file = open_before_run(o.snp);
 		ngm_snp_params sp{};
 		sp.min_cov = (uint32_t) o.snp_min_cov; sp.min_frac = o.snp_min_frac; sp.min_qual = (int) o.snp_min_qual; sp.min_frac_text = o.snp_frac_text.c_str();
 		snp = ngm_snp_create_for_ref(refs[0], &sp);
@@ -832,8 +837,7 @@ void Run::create_mappers_and_side_outputs() {
 		for (size_t i = 0; same && i < contig_names.size(); ++i) same = count_names[i] == contig_names[i] && count_lens[i] == contig_lens[i];
 		if (!same) die("--count: the contigs read from " + o.ref + " for the BED file (" + std::to_string(count_names.size()) + ") are not the reference's (" + std::to_string(contig_names.size()) +
 				"): either the index cache next to it was built from another FASTA (delete it to rebuild it), or the file has a form the two readers take differently");
-		count_file = fopen(o.count_out.c_str(), "wb");   // (before the run, not after it)
-		if (!count_file) die("cannot write " + o.count_out);
+		count_file = open_before_run(o.count_out);
 		std::vector<int32_t> r_ref;
 		std::vector<uint32_t> r_start, r_end;
 		std::string r_strand;
@@ -1235,9 +1239,8 @@ void Run::host_format_route(Worker &w, std::unique_ptr<Batch> &b, PairTurn &turn
 		b->n_total += c.total; b->n_mapped += c.mapped; b->n_written += c.written;
 		for (int k = 0; k < 3; ++k) if (c.pair[k]) pair_stat[k] += c.pair[k];
 	}
-	if (cov_failed) { fail(std::string("--coverage: ") + ngm_pipeline_last_error()); return; }
-	if (snp_failed) { fail(std::string("--snp: ") + ngm_pipeline_last_error()); return; }
-	if (count_failed) { fail(std::string("--count: ") + ngm_pipeline_last_error()); return; }
+	auto add_failed = [&](const std::atomic<bool> &flag, const char *option) { if (flag) fail(std::string(option) + ngm_pipeline_last_error()); return (bool) flag; };
+	if (add_failed(cov_failed, "--coverage: ") || add_failed(snp_failed, "--snp: ") || add_failed(count_failed, "--count: ")) return;
 	if (route.gpu_bgzf && !gpu_bgzf_chunks(w, *b)) return;
 	recycle_input(*b);
 	t_format_us += us_since(tf);
@@ -1583,12 +1586,8 @@ void Run::teardown() {
 	for (Worker &w : workers) { ngm_mapper_destroy(w.m); ngm_host_free(w.rows); ngm_host_free(w.qrows); ngm_host_free(w.names); ngm_host_free(w.meta); ngm_host_free(w.polya);
 		ngm_bgzf_destroy(w.bz); ngm_host_free(w.bam_raw); ngm_host_free(w.bam_out); }
 	ngm_bam_sort_destroy(sorter);
-	ngm_coverage_destroy(coverage);
-	if (coverage_file) fclose(coverage_file);
-	ngm_snp_destroy(snp);
-	if (snp_file) fclose(snp_file);
-	ngm_count_destroy(counter);
-	if (count_file) fclose(count_file);
+	ngm_coverage_destroy(coverage); ngm_snp_destroy(snp); ngm_count_destroy(counter);
+	for (FILE *f : {coverage_file, snp_file, count_file}) if (f) fclose(f);
 	for (TextBuf &t : text_free) ngm_host_free(t.p);
 	ngm_pair_state_destroy(pair_state);
 	for (ngm_ref *r2 : refs) ngm_ref_destroy(r2);

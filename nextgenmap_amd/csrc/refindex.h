@@ -123,22 +123,20 @@ void pipeline_set_error(const char *fmt, ...);
 // units + 1 offsets into d_records, the last one n_bytes; both complete), and the device a sorter lives on
 int bam_sort_add_device(struct ::ngm_bam_sort *s, uint64_t seq, const void *d_records, size_t n_bytes, const uint32_t *d_unit_off, size_t units);
 int bam_sort_device(const struct ::ngm_bam_sort *s);
-// coverage.cpp, for the mapper's SAM stage: the device a coverage object lives on, where a cov_add_kernel on that device adds (the counters,
-// the contigs' offsets, the count of alignments; -22 after the finish), and the time such a kernel took
-int coverage_device(const struct ::ngm_coverage *c);
-int coverage_target(struct ::ngm_coverage *c, int32_t **counters, const uint64_t **d_off, int *n_ref, unsigned long long **d_n_aln);
-void coverage_note_add_ms(struct ::ngm_coverage *c, float ms);
-// snp.cpp, the same three for an SNP object: where a snp_add_kernel on its device adds (snp_device.h's Target)
-namespace snp { struct Target; }
-int snp_device(const struct ::ngm_snp *c);
+// for the mapper's SAM stage: a side output (--coverage, --snp, --count) as what the three share (side_output.h: its device, the time an
+// add kernel of the mapper's took), and per object where such a kernel on its device adds (-22 and the message after the object's finish)
+namespace side {
+struct Base;
+Base *base(struct ::ngm_coverage *c);
+Base *base(struct ::ngm_snp *c);
+Base *base(struct ::ngm_count *c);
+}
+namespace cov { struct Target { int32_t *counters; const uint64_t *off; int n_ref; unsigned long long *n_aln; }; }   // (off: the contigs' offsets)
+namespace snp { struct Target; }                     // snp_device.h
+namespace cnt { struct Layout; struct Counters; }    // count.h, count_device.h
+int coverage_target(struct ::ngm_coverage *c, cov::Target *t);
 int snp_target(struct ::ngm_snp *c, snp::Target *t);
-void snp_note_add_ms(struct ::ngm_snp *c, float ms);
-// count.cpp, the same three for a conversion counter: the tables and counters a count_add_kernel on its device works with (count.h's Layout,
-// count_device.h's Counters)
-namespace cnt { struct Layout; struct Counters; }
-int count_device(const struct ::ngm_count *c);
 int count_target(struct ::ngm_count *c, cnt::Layout *l, cnt::Counters *t);
-void count_note_add_ms(struct ::ngm_count *c, float ms);
 // k-mer integer as the reference builds it: 2 bits per base, A0 C1 T2 G3 ((c >> 1) & 3, CSstatic.cpp:20-22)
 inline uint32_t kmer_code_of_class(uint32_t cls) { return cls == 2 ? 3u : (cls == 3 ? 2u : cls); }
 // reverse complement of a k-mer integer (PrefixTable.cpp:94-108), valid for 2k <= 32

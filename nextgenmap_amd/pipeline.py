@@ -225,9 +225,84 @@ class Bgzf:
             pass
 
 
-class BamSorter:
+class _Handle:
+    """A run-long object of the library behind self._h; _prefix names its functions (ngm_<prefix>_finish, ngm_<prefix>_destroy)."""
+    _prefix = None
+    _h = None
+
+    def _fn(self, name):
+        return getattr(_lib(), "ngm_%s_%s" % (self._prefix, name))
+
+    def finish(self):
+        if self._fn("finish")(self._h) < 0:
+            raise _err()
+
+    def close(self):
+        if self._h:
+            self._fn("destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _LineStream(_Handle):
+    """... whose file comes back as text, in pieces of whole lines (ngm_<prefix>_next)."""
+
+    def next(self, cap, out=None):
+        """one ngm_<prefix>_next call with a buffer of cap bytes: (return value, the bytes copied)"""
+        if out is None:
+            out = C.create_string_buffer(max(1, cap))
+        n = self._fn("next")(self._h, out, cap)
+        if n < 0:
+            raise _err()
+        return n, (C.string_at(out, n) if n <= cap else b"")
+
+    def pieces(self, cap=1 << 20):
+        """the file, in pieces of whole lines (an SnpCaller's header is the first)"""
+        out = C.create_string_buffer(cap)
+        while True:
+            n, data = self.next(cap, out)
+            if n == 0:
+                return
+            if n > cap:
+                cap = n
+                out = C.create_string_buffer(cap)
+                continue
+            yield data
+
+
+def _pack_records(records, with_reverse):
+    """the arrays of ngm_snp_add (and, with the strands, of ngm_count_add) from [(contig index, position, CIGAR, sequence, qualities or None
+    [, reverse])]"""
+    records = list(records)
+    b = lambda x: x.encode() if isinstance(x, str) else bytes(x)
+    cig = [b(r[2]) for r in records]
+    seq = [b(r[3]) for r in records]
+    with_q = [r[4] is not None for r in records]
+    if any(with_q) and not all(with_q):
+        raise ValueError("records with and without qualities go into separate calls")
+    qual = None
+    if records and all(with_q):
+        if any(len(r[4]) != len(sq) for r, sq in zip(records, seq)):
+            raise ValueError("a quality string has another length than its sequence")
+        qual = b"".join(b(r[4]) for r in records)
+    off = np.zeros(len(cig) + 1, dtype=np.uint32)
+    off[1:] = np.cumsum([len(c) for c in cig], dtype=np.uint64)
+    soff = np.zeros(len(seq) + 1, dtype=np.uint32)
+    soff[1:] = np.cumsum([len(c) for c in seq], dtype=np.uint64)
+    arrays = (np.array([r[0] for r in records], dtype=np.int32), np.array([r[1] for r in records], dtype=np.int32), off, b"".join(cig), soff, b"".join(seq), qual)
+    return arrays + ((np.array([1 if r[5] else 0 for r in records], dtype=np.uint8),) if with_reverse else ())
+
+
+class BamSorter(_Handle):
     """The BAM records of a run kept in GPU memory, sorted there into coordinate order and handed back as the BGZF members of the sorted
     file plus its BAI index (include/ngm_pipeline.h, ngm_bam_sort_*): what `ngm-hip --sort` writes."""
+
+    _prefix = "bam_sort"
 
     def __init__(self, device=0, chunk_bytes=0, max_bytes=0):
         p = BamSortParams(device, chunk_bytes, max_bytes)
@@ -282,21 +357,12 @@ class BamSorter:
         d.update(zip(("keys_ms", "sort_ms", "gather_ms", "deflate_ms", "index_ms"), (float(x) for x in ms)))
         return d
 
-    def close(self):
-        if self._h:
-            _lib().ngm_bam_sort_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Coverage:
+class Coverage(_LineStream):
     """The per-base read depth of a run, counted in GPU memory and handed back as bedGraph text (include/ngm_pipeline.h, ngm_coverage_*):
     what `ngm-hip --coverage` writes.  contigs: [(name, length)]."""
+
+    _prefix = "coverage"
 
     def __init__(self, contigs, device=0, scan_chunk=0):
         n = len(contigs)
@@ -324,32 +390,6 @@ class Coverage:
         if _lib().ngm_coverage_add(self._h, ref_id.ctypes.data, pos0.ctypes.data, cigar_off.ctypes.data, bytes(cigar_text), len(ref_id)) < 0:
             raise _err()
 
-    def finish(self):
-        if _lib().ngm_coverage_finish(self._h) < 0:
-            raise _err()
-
-    def next(self, cap, out=None):
-        """one ngm_coverage_next call with a buffer of cap bytes: (return value, the bytes copied)"""
-        if out is None:
-            out = C.create_string_buffer(max(1, cap))
-        n = _lib().ngm_coverage_next(self._h, out, cap)
-        if n < 0:
-            raise _err()
-        return n, (C.string_at(out, n) if n <= cap else b"")
-
-    def pieces(self, cap=1 << 20):
-        """the file, in pieces of whole lines"""
-        out = C.create_string_buffer(cap)
-        while True:
-            n, data = self.next(cap, out)
-            if n == 0:
-                return
-            if n > cap:
-                cap = n
-                out = C.create_string_buffer(cap)
-                continue
-            yield data
-
     def stats(self):
         counts = (C.c_uint64 * 4)()
         ms = (C.c_float * 4)()
@@ -359,23 +399,13 @@ class Coverage:
         d.update(zip(("add_ms", "scan_ms", "runs_ms", "text_ms"), (float(x) for x in ms)))
         return d
 
-    def close(self):
-        if self._h:
-            _lib().ngm_coverage_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class ConversionCounter:
+class ConversionCounter(_Handle):
     """T>C conversion counts per region, counted in GPU memory (include/ngm_pipeline.h, ngm_count_*): what `ngm-hip --count` writes.
     contigs: [(name, sequence)]; regions: [(contig index, start, end, name, strand)], start 0-based, end exclusive, strand '+', '-' or '.';
     reference: a Reference whose resident genome is read instead (contigs then only names the contigs for tsv())."""
 
+    _prefix = "count"
     HEADER = "#chrom\tstart\tend\tname\tstrand\tt_bases\tmasked\tcov_on_ts\tconv_on_ts\treads\ttc_reads\n"
 
     def __init__(self, contigs, regions, device=0, min_qual=27, reference=None):
@@ -406,24 +436,7 @@ class ConversionCounter:
     def add(self, records):
         """[(contig index, 0-based position, CIGAR text, sequence, qualities or None, reverse)]: all with qualities or all without; raises
         on the first record the validator refuses, adding nothing"""
-        records = list(records)
-        b = lambda x: x.encode() if isinstance(x, str) else bytes(x)
-        cig = [b(r[2]) for r in records]
-        seq = [b(r[3]) for r in records]
-        with_q = [r[4] is not None for r in records]
-        if any(with_q) and not all(with_q):
-            raise ValueError("records with and without qualities go into separate calls")
-        qual = None
-        if records and all(with_q):
-            if any(len(r[4]) != len(sq) for r, sq in zip(records, seq)):
-                raise ValueError("a quality string has another length than its sequence")
-            qual = b"".join(b(r[4]) for r in records)
-        off = np.zeros(len(cig) + 1, dtype=np.uint32)
-        off[1:] = np.cumsum([len(c) for c in cig], dtype=np.uint64)
-        soff = np.zeros(len(seq) + 1, dtype=np.uint32)
-        soff[1:] = np.cumsum([len(c) for c in seq], dtype=np.uint64)
-        self.add_arrays(np.array([r[0] for r in records], dtype=np.int32), np.array([r[1] for r in records], dtype=np.int32), off, b"".join(cig), soff, b"".join(seq), qual,
-                        np.array([1 if r[5] else 0 for r in records], dtype=np.uint8))
+        self.add_arrays(*_pack_records(records, True))
 
     def add_arrays(self, ref_id, pos0, cigar_off, cigar_text, seq_off, seq_text, qual_text, reverse):
         ref_id = np.ascontiguousarray(ref_id, dtype=np.int32)
@@ -443,10 +456,6 @@ class ConversionCounter:
         ref_id = np.array([c for c, _ in positions], dtype=np.int32)
         pos0 = np.array([p for _, p in positions], dtype=np.int32)
         if _lib().ngm_count_mask(self._h, ref_id.ctypes.data, pos0.ctypes.data, len(positions)) < 0:
-            raise _err()
-
-    def finish(self):
-        if _lib().ngm_count_finish(self._h) < 0:
             raise _err()
 
     def read(self):
@@ -471,22 +480,13 @@ class ConversionCounter:
         d.update(zip(("add_ms", "reduce_ms"), (float(x) for x in ms)))
         return d
 
-    def close(self):
-        if self._h:
-            _lib().ngm_count_destroy(self._h)
-            self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class SnpCaller:
+class SnpCaller(_LineStream):
     """The mismatch pileup of a run, counted in GPU memory, and its single-base substitution calls handed back as VCF text
     (include/ngm_pipeline.h, ngm_snp_*): what `ngm-hip --snp` writes.  contigs: [(name, sequence)]; min_frac: a number, or the text the
     header prints (its float() is the threshold); reference: a Reference whose resident genome is read instead (contigs is then not used)."""
+
+    _prefix = "snp"
 
     def __init__(self, contigs, device=0, min_cov=10, min_frac="0.8", min_qual=15, scan_chunk=0, reference=None):
         b = lambda x: x.encode() if isinstance(x, str) else bytes(x)
@@ -510,23 +510,7 @@ class SnpCaller:
     def add(self, records):
         """[(contig index, 0-based position, CIGAR text, sequence, qualities or None)]: all with qualities or all without; raises on the
         first record the validator refuses, adding nothing"""
-        records = list(records)
-        b = lambda x: x.encode() if isinstance(x, str) else bytes(x)
-        cig = [b(r[2]) for r in records]
-        seq = [b(r[3]) for r in records]
-        with_q = [r[4] is not None for r in records]
-        if any(with_q) and not all(with_q):
-            raise ValueError("records with and without qualities go into separate calls")
-        qual = None
-        if records and all(with_q):
-            if any(len(r[4]) != len(sq) for r, sq in zip(records, seq)):
-                raise ValueError("a quality string has another length than its sequence")
-            qual = b"".join(b(r[4]) for r in records)
-        off = np.zeros(len(cig) + 1, dtype=np.uint32)
-        off[1:] = np.cumsum([len(c) for c in cig], dtype=np.uint64)
-        soff = np.zeros(len(seq) + 1, dtype=np.uint32)
-        soff[1:] = np.cumsum([len(c) for c in seq], dtype=np.uint64)
-        self.add_arrays(np.array([r[0] for r in records], dtype=np.int32), np.array([r[1] for r in records], dtype=np.int32), off, b"".join(cig), soff, b"".join(seq), qual)
+        self.add_arrays(*_pack_records(records, False))
 
     def add_arrays(self, ref_id, pos0, cigar_off, cigar_text, seq_off, seq_text, qual_text=None):
         ref_id = np.ascontiguousarray(ref_id, dtype=np.int32)
@@ -539,32 +523,6 @@ class SnpCaller:
                               None if qual_text is None else bytes(qual_text), len(ref_id)) < 0:
             raise _err()
 
-    def finish(self):
-        if _lib().ngm_snp_finish(self._h) < 0:
-            raise _err()
-
-    def next(self, cap, out=None):
-        """one ngm_snp_next call with a buffer of cap bytes: (return value, the bytes copied)"""
-        if out is None:
-            out = C.create_string_buffer(max(1, cap))
-        n = _lib().ngm_snp_next(self._h, out, cap)
-        if n < 0:
-            raise _err()
-        return n, (C.string_at(out, n) if n <= cap else b"")
-
-    def pieces(self, cap=1 << 20):
-        """the file, in pieces of whole lines; the header is the first"""
-        out = C.create_string_buffer(cap)
-        while True:
-            n, data = self.next(cap, out)
-            if n == 0:
-                return
-            if n > cap:
-                cap = n
-                out = C.create_string_buffer(cap)
-                continue
-            yield data
-
     def stats(self):
         counts = (C.c_uint64 * 5)()
         ms = (C.c_float * 4)()
@@ -573,17 +531,6 @@ class SnpCaller:
         d = dict(zip(("alignments", "alt_bases", "calls", "text_bytes", "covered_bases"), (int(x) for x in counts)))
         d.update(zip(("add_ms", "scan_ms", "flag_ms", "text_ms"), (float(x) for x in ms)))
         return d
-
-    def close(self):
-        if self._h:
-            _lib().ngm_snp_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class Reference:

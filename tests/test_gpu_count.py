@@ -272,3 +272,26 @@ def test_output_is_the_same_with_and_without_the_option(world):
     without, _, _, log0 = _run(world, "se", [], {}, False, count=False)
     assert body(with_count) == body(without) and len(body(without)) > 6000
     assert "Conversion" not in log0
+
+
+def test_side_outputs_fed_from_a_second_device_equal_a_one_device_run(tmp_path):
+    """the objects live on the first device; with -g 0,1 the second device's mapper hands its records to them through ngm_*_add"""
+    import nextgenmap_amd
+    if nextgenmap_amd.load_library().ngm_hip_device_count() < 2:
+        pytest.skip("one visible GPU: the route from another device needs two")
+    contigs = S.make_genome([30000, 20000], seed=77)
+    fa, fq, bed = str(tmp_path / "ref.fa"), str(tmp_path / "reads.fq"), str(tmp_path / "r.bed")
+    S.write_fasta(fa, contigs)
+    with open(fq, "wb") as f:
+        f.write(b"".join(b"@" + n.encode() + b"\n" + s.tobytes() + b"\n+\n" + bytes(33 + 20 + (7 * j + i) % 21 for j in range(len(s))) + b"\n"
+                         for i, (n, s, _) in enumerate(S.make_reads(contigs, 2000, 100, seed=78, sub_rate=0.02, indel_rate=0.002))))
+    with open(bed, "w") as f:
+        f.write("".join("chr%d\t%d\t%d\tr%d\t0\t%s\n" % (1 + k % 2, 500 + 900 * k, 1200 + 900 * k, k, "+-"[k % 2]) for k in range(20)))
+    files = {}
+    for tag, gpus in (("one", "0"), ("two", "0,1")):
+        names = [str(tmp_path / (tag + ext)) for ext in (".bedgraph", ".vcf", ".tsv")]
+        _hip(["-r", fa, "-q", fq, "-o", str(tmp_path / (tag + ".sam")), "-g", gpus, "--batch-size", "500", "--coverage", names[0], "--snp", names[1], "--snp-min-cov", "2",
+              "--count", bed, "--count-out", names[2]])
+        files[tag] = [open(n, "rb").read() for n in names]
+    assert all(len(t) > 200 for t in files["one"])
+    assert files["two"] == files["one"]

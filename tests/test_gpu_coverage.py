@@ -142,6 +142,50 @@ def test_add_refuses_a_bad_alignment_by_its_index_and_adds_nothing(k):
     c.close()
 
 
+def _stats_beside_adds(obj, batch):
+    """stats() 200 times on a second thread while this one makes 50 add calls: the last statistics"""
+    seen, errors = [], []
+
+    def watch():
+        try:
+            for _ in range(200):
+                seen.append(obj.stats())
+        except Exception as e:
+            errors.append(e)
+
+    t = threading.Thread(target=watch)
+    t.start()
+    for _ in range(50):
+        obj.add(batch)
+    t.join()
+    assert not errors and len(seen) == 200
+    assert all(0 <= st["alignments"] <= 50 * len(batch) and np.isfinite(st["add_ms"]) and st["add_ms"] >= 0 for st in seen)
+    assert [st["alignments"] for st in seen] == sorted(st["alignments"] for st in seen)
+    return obj.stats()
+
+
+def test_stats_from_a_second_thread_while_the_first_adds():
+    c = _coverage([("a", 200), ("b", 100)])
+    st = _stats_beside_adds(c, [(0, 10, "50M"), (1, 0, "20M5D20M"), (0, 150, "60M"), (1, 90, "10M")])
+    assert st["alignments"] == 200 and np.isfinite(st["add_ms"]) and st["add_ms"] >= 0
+    c.close()
+
+
+def test_next_before_the_finish_is_refused_with_its_message():
+    from nextgenmap_amd.engine import NgmHipError
+    c = _coverage(M.TWO)
+    c.add([(0, 10, "20M")])
+    with pytest.raises(NgmHipError) as e:
+        c.next(100)
+    assert str(e.value) == "ngm_coverage_next: ngm_coverage_finish has not been called"
+    c.finish()
+    with pytest.raises(NgmHipError) as e:
+        c.finish()
+    assert str(e.value) == "ngm_coverage_finish: called twice"
+    assert b"".join(c.pieces()) == M.bedgraph(M.TWO, [(0, 10, "20M")])   # (the refused calls changed nothing)
+    c.close()
+
+
 # ---- the command line ---------------------------------------------------------------------------------------------------------------
 def _hip(args, env=None):
     c = subprocess.run([CLI] + args, capture_output=True, text=True, env=dict(os.environ, **(env or {})))

@@ -189,6 +189,33 @@ def test_thresholds_out_of_range_are_refused():
             SnpCaller(contigs, 0, **kw)
 
 
+def test_stats_from_a_second_thread_while_the_first_adds():
+    from nextgenmap_amd.pipeline import SnpCaller
+    from test_gpu_coverage import _stats_beside_adds
+    rnd = random.Random(3)
+    contigs = [("a", "".join(rnd.choice("ACGT") for _ in range(200))), ("b", "".join(rnd.choice("ACGT") for _ in range(100)))]
+    c = SnpCaller(contigs, 0, 1, "0.5", 0)
+    st = _stats_beside_adds(c, [(0, 10, "50M", "A" * 50, None), (1, 0, "20M5D20M", "C" * 40, None), (0, 150, "60M", "G" * 60, None), (1, 90, "10M", "T" * 10, None)])
+    assert st["alignments"] == 200 and np.isfinite(st["add_ms"]) and st["add_ms"] >= 0
+    c.close()
+
+
+def test_next_before_the_finish_is_refused_with_its_message():
+    from nextgenmap_amd.engine import NgmHipError
+    case = M.UNIT_CASES[next(iter(M.UNIT_CASES))]
+    c = _caller(case)
+    with pytest.raises(NgmHipError) as e:
+        c.next(100)
+    assert str(e.value) == "ngm_snp_next: ngm_snp_finish has not been called"
+    _add(c, case[1])
+    c.finish()
+    with pytest.raises(NgmHipError) as e:
+        c.finish()
+    assert str(e.value) == "ngm_snp_finish: called twice"
+    assert b"".join(c.pieces()) == M.vcf(*case)   # (the refused calls changed nothing)
+    c.close()
+
+
 # ---- the command line ---------------------------------------------------------------------------------------------------------------
 def _hip(args, env=None):
     c = subprocess.run([CLI] + args, capture_output=True, text=True, env=dict(os.environ, **(env or {})))
