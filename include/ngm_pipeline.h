@@ -126,6 +126,9 @@ typedef struct ngm_mapper_params {
 	int slam_seq;
 } ngm_mapper_params;
 
+/* Refused (NULL, ngm_pipeline_last_error): a combination in which one (bin, strand) of a read could collect more than 65 535 votes, which
+ * the search's vote tables do not hold -- (qry_max_len - kmer) * min(max_kfreq - 1, 2^(bin_size - 1)) > 65535, i.e. bin_size 8 with
+ * qry_max_len - kmer of 512 or more (unless max_kfreq is below 129).  The reference program counts such bins; use a smaller bin_size. */
 ngm_mapper *ngm_mapper_create(const ngm_ref *ref, const ngm_mapper_params *p);
 void ngm_mapper_destroy(ngm_mapper *m);
 
@@ -532,6 +535,11 @@ int ngm_mapper_heavy_counters(ngm_mapper *m, uint64_t out[4]);
  * the batch was searched again with four times the room), [2] score-stage buffers that had to grow behind the synchronisation, inside
  * the turn, because the count predicted in front of the search was too small.  tests/test_gpu_search_turn.py */
 int ngm_mapper_search_turn_counters(ngm_mapper *m, uint64_t out[3]);
+
+/* which first-pass kernel the last candidate search launched (read only; tests/test_gpu_cs_shapes.py): [0] 0 = one bucket per k-mer,
+ * 1-3 = the shape of cs_canon_kernel over canonical pair buckets, [1] waves per read of cs_fast2_kernel (1: cs_fast_kernel) when [0] is 0,
+ * [2] work items per lane (12 / 24), [3] 1 = 16-bit work items, 0 = 32-bit ones */
+int ngm_mapper_cs_dispatch(ngm_mapper *m, uint64_t out[4]);
 
 /* work counters of the last candidate search: [0] k-mers looked up, [1] index hits voted, [2] candidates emitted
  * (algorithmic bytes of the search = 20 * kmers + 4 * hits + 16 * candidates) */

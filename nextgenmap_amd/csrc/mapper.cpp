@@ -135,6 +135,25 @@ ngm_mapper *ngm_mapper_create(const ngm_ref *ref, const ngm_mapper_params *p) {
 	if (!ref || !p) { ngm::pipeline_set_error("ngm_mapper_create: null argument"); return nullptr; }
 	DevGuard g(ref->device);
 	if (p->qry_max_len < ref->prm.kmer + 1 || p->qry_max_len > 1024) { ngm::pipeline_set_error("ngm_mapper_create: qry_max_len %d out of range", p->qry_max_len); return nullptr; }
+	{
+		// Every vote table of the search keeps a bin's forward and reverse votes in 16-bit halves of one word (cs_device.h).  A read of up
+		// to qry_max_len - 1 bases has qry_max_len - k k-mers; the hits of one list for one (bin, strand) lie within 2^bin_size genome
+		// positions, and a k-mer with max_kfreq hits or more is not voted (CS.cpp:122).  Two occurrences of a k-mer that is no homopolymer
+		// are two positions apart or more: 2^(bin_size - 1) hits per list and bin.  A homopolymer's k-mer is stored twice per run and once
+		// per bin border (PrefixTable.cpp:641-709), with k + 1 positions or more between two runs: up to 3 hits among 4 positions, so the
+		// half is no bound for narrow bins -- but it is one from 128 positions on (2 * ceil(128 / 5) + 1 = 53 <= 64 at k = 4), and with at
+		// most 1 020 k-mers per read the product passes 65 535 only at --bin-size 8, where the half is 128.  So the test below is exact
+		// where it refuses: bins of 256 bases with 512 k-mers or more per read (an AC repeat gets there).  There a count would carry into
+		// the other strand's half: refuse it here and not there.
+		const long max_kfreq = p->max_kfreq > 0 ? p->max_kfreq : ref->auto_max_kfreq;
+		const long per_kmer = std::min<long>(std::max<long>(1, max_kfreq - 1), std::max<long>(1, (1l << ref->prm.bin_size) >> 1));
+		const long votes = (long) (p->qry_max_len - ref->prm.kmer) * per_kmer;
+		if (votes > 65535) {
+			ngm::pipeline_set_error("ngm_mapper_create: reads of up to %d bases with --bin-size %d and --max-kfreq %ld could collect %ld votes in one bin, and the search counts up to 65535 votes: use a smaller --bin-size",
+									p->qry_max_len - 1, ref->prm.bin_size, max_kfreq, votes);
+			return nullptr;
+		}
+	}
 	ngm_hip_params ep{};
 	ep.abi_version = NGM_HIP_ABI_VERSION;
 	ep.qry_max_len = p->qry_max_len; ep.corridor = p->corridor;
@@ -1869,6 +1888,12 @@ int ngm_mapper_order_table_reads(ngm_mapper *m, uint64_t *out) {
 int ngm_mapper_search_turn_counters(ngm_mapper *m, uint64_t out[3]) {
 	if (!m || !out) return -22;
 	out[0] = m->turn_dbg[0]; out[1] = m->turn_dbg[1]; out[2] = m->turn_dbg[2];
+	return 0;
+}
+
+int ngm_mapper_cs_dispatch(ngm_mapper *m, uint64_t out[4]) {
+	if (!m || !out) return -22;
+	out[0] = (uint64_t) m->cs_canon; out[1] = (uint64_t) m->cs_waves; out[2] = (uint64_t) m->last_cs.fast_items; out[3] = (uint64_t) m->last_cs.items16;
 	return 0;
 }
 

@@ -507,7 +507,8 @@ int run_cs(ngm_mapper *m, int n, GpuStage *stage, bool defer_host_arrays) {
 			MAP_HIP_TRY(hipEventRecord(m->cev[4], m->st));
 			{
 				CsArgs B = A;
-				B.log2_slots = m->cs_log2_slots;
+				// (NGM_HIP_TEST_LIMITS=exact_log2_slots=N: a smaller table, so that reads of a test genome outgrow it and reach cs_global_kernel)
+				B.log2_slots = (int) std::min<long>(m->cs_log2_slots, std::max<long>(8, test_limit("exact_log2_slots", m->cs_log2_slots)));
 				B.hit_cap = (uint32_t) ((1u << B.log2_slots) * 0.66f);
 				B.read_list = m->d_ovf_read.p; B.n_list_dev = m->d_status.p + 1;
 				B.status = m->d_status.p + kCsqStatusExact; B.ovf_read = m->d_ovf_read2.p; B.ovf_hits = m->d_ovf_hits2.p;

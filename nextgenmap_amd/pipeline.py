@@ -98,6 +98,8 @@ def _lib():
         lib.ngm_mapper_order_table_reads.argtypes = [C.c_void_p, C.c_void_p]
         lib.ngm_mapper_heavy_counters.argtypes = [C.c_void_p, C.c_void_p]
         lib.ngm_mapper_search_turn_counters.argtypes = [C.c_void_p, C.c_void_p]
+        lib.ngm_mapper_cs_dispatch.argtypes = [C.c_void_p, C.c_void_p]
+        lib.ngm_mapper_cs_max_combined.argtypes = [C.c_void_p, C.c_void_p]
         lib.ngm_mapper_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         lib.ngm_mapper_last_order_replay_ms.restype = C.c_float
         lib.ngm_mapper_last_order_replay_ms.argtypes = [C.c_void_p]
@@ -788,6 +790,20 @@ class Mapper:
         out = np.zeros(3, np.uint64)
         self.lib.ngm_mapper_search_turn_counters(self.h, out.ctypes.data)
         return dict(zip(("arrays_deferred", "search_attempts", "buffers_regrown"), (int(x) for x in out)))
+
+    def cs_dispatch(self):
+        """which first-pass kernel the last candidate search launched: canonical shape (0: one bucket per k-mer), waves per read of the
+        fast path, work items per lane, 16-bit work items (0/1)"""
+        out = np.zeros(4, np.uint64)
+        self.lib.ngm_mapper_cs_dispatch(self.h, out.ctypes.data)
+        return dict(zip(("cs_canon", "cs_waves", "cs_fast_items", "items16"), (int(x) for x in out)))
+
+    def cs_max_combined(self, n):
+        """after candidate_search of n reads: per read, the largest forward + reverse vote sum of one bin"""
+        out = np.zeros(max(1, n), np.float32)
+        if self.lib.ngm_mapper_cs_max_combined(self.h, out.ctypes.data) < 0:
+            raise _err()
+        return out[:n]
 
     def order_table_reads(self):
         """of path_counters()["order_exact_global"]: the reads the bucket replay left to the replay with a table in global memory"""
