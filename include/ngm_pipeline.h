@@ -295,6 +295,28 @@ long long ngm_bam_sort_index(ngm_bam_sort *s, uint64_t first_member_offset, void
 /* counts: records, record bytes, members written, chunks (ngm_bam_sort_next calls that compressed one), bins of the index (after
  * ngm_bam_sort_index); ms: kernel ms of keys / sort / gather / deflate / index (HIP events) */
 int ngm_bam_sort_stats(const ngm_bam_sort *s, uint64_t counts[5], float ms[5]);
+/* `ngm-hip --sort --markdup` (csrc/markdup.h, csrc/markdup_device.h): with on != 0, ngm_bam_sort_finish sets flag 0x400 on duplicate
+ * records in the device's memory before it sorts them; nothing else about the sorted file changes.  Valid only before the first
+ * ngm_bam_sort_add, -22 afterwards.  Off (the default): finish launches no kernel and holds no byte more than before.
+ * The rules (INTEGRATION.md "Duplicate marking"; the result depends on the records and their run order -- seq, position in the run -- only):
+ *   examined: flag 0x4, 0x100, 0x800 clear and refID >= 0; other records are never marked and never count;
+ *   u5: forward strand pos - leading S/H lengths, reverse strand end - 1 + trailing S/H lengths (end as for the sort key: pos + M/D/N/=/X
+ *     lengths, pos + 1 without any), clamped to [-2^30, 2^30 - 1]; without CIGAR operations u5 = pos;
+ *   end key: ((uint32) refID << 32) | ((u5 + 2^30) << 1) | strand -- (refID, u5, strand) ascending, bit 63 clear;
+ *   mates: records g, g + 1 of the run order, both examined, both 0x1, one with 0x40 and not 0x80, the other with 0x80 and not 0x40, equal
+ *     names.  Mates with the first mate (0x40) in front are a pair; mates with the second mate in front (the order ngm-hip writes) are a
+ *     pair unless one of them is part of a pair of the first kind with its other neighbour, so pairs never overlap.  A pair's first mate
+ *     is the record with 0x40, its index g that of its record in front; every other examined record is a fragment;
+ *   score: sum of the quality bytes >= 15; 0 with absent qualities (first byte 0xFF) or l_seq 0; a pair: both mates; 32 bits, saturating;
+ *   pairs: key = the two end keys ascending (the first mate's first when equal) + one bit "the lower end is the first mate's" that counts
+ *     only when both strands are equal; per key the highest score survives, ties to the lowest g; both mates of the others get 0x400;
+ *   fragments: grouped by end key with both ends of every pair (survivor or not); a group with a pair end marks all its fragments, else the
+ *     highest score survives, ties to the lowest g;
+ *   the marker only ORs: a record that arrives with 0x400 keeps it and takes part like any other. */
+int ngm_bam_sort_set_markdup(ngm_bam_sort *s, int on);
+/* after a successful finish with marking on (-22 before, and when marking is off).  counts: examined records, pairs, fragments, duplicate
+ * pairs, duplicate fragments, records newly marked (0x400 was clear); ms: kernel ms of the marking kernels / of its sorts (HIP events) */
+int ngm_bam_sort_markdup_stats(const ngm_bam_sort *s, uint64_t counts[6], float ms[2]);
 /* with ngm_sam_options::bam set: ngm_mapper_map_sam* hands the batch's records to s under the mapper's batch seq
  * (ngm_mapper_set_batch_seq) and returns 0 bytes instead of BGZF members; NULL detaches.  Same device: a device-to-device copy; another
  * device: the records are downloaded and go through ngm_bam_sort_add.  When the sorter has no device memory left for the batch (its -12),

@@ -1,6 +1,8 @@
 // bam_sort.cpp -- host side of `ngm-hip --sort` (include/ngm_pipeline.h, ngm_bam_sort_*): the records of a whole run stay in HBM in segments,
 // one stable radix sort over their coordinate keys, a byte-granular gather of the sorted stream chunk by chunk into the BGZF compressor,
 // and the arrays of the BAI file.  Kernels: csrc/bam_sort_device.h; the host-only parts (walk, key, serialiser): csrc/bam_sort.h.
+// With ngm_bam_sort_set_markdup: duplicates get flag 0x400 in the segments before the sort reads them (mark_duplicates below; the rules
+// and the keys: csrc/markdup.h, the kernels: csrc/markdup_device.h).
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -16,9 +18,11 @@
 #include "../../include/ngm_pipeline.h"
 #include "bam_sort_device.h"
 #include "device_util.h"
+#include "markdup_device.h"
 #include "refindex.h"
 
 namespace bs = ngm::bamsort;
+namespace md = ngm::markdup;
 
 using ngm::Buf;
 using ngm::DeviceGuard;
@@ -66,6 +70,10 @@ struct ngm_bam_sort {
 	float ms[5] = {0, 0, 0, 0, 0};
 	std::string bai;
 	uint64_t bai_first = ~0ull;
+	// --markdup (ngm_bam_sort_set_markdup): the six counts and the kernel ms of marking / its sorts
+	bool markdup = false;
+	uint64_t md_counts[md::kCounters] = {0, 0, 0, 0, 0, 0};
+	float md_ms[2] = {0, 0};
 };
 
 extern "C" ngm_bam_sort *ngm_bam_sort_create(const ngm_bam_sort_params *p) {
@@ -200,6 +208,149 @@ int ngm::bam_sort_add_device(ngm_bam_sort *s, uint64_t seq, const void *d_record
 }
 int ngm::bam_sort_device(const ngm_bam_sort *s) { return s ? s->device : -1; }
 
+extern "C" int ngm_bam_sort_set_markdup(ngm_bam_sort *s, int on) {
+	if (!s) { ngm::pipeline_set_error("ngm_bam_sort_set_markdup: bad arguments"); return -22; }
+	std::lock_guard<std::mutex> lk(s->mu);
+	if (s->finished || !s->seqs.empty()) { ngm::pipeline_set_error("ngm_bam_sort_set_markdup: duplicate marking is chosen before the first ngm_bam_sort_add"); return -22; }
+	s->markdup = on != 0;
+	return 0;
+}
+
+namespace {
+// --markdup: flag 0x400 into the records of the segments (sorted by seq), by the rules of csrc/markdup.h.  Runs before the sort's own arrays
+// exist and frees its scratch before it returns -- at most 48 bytes per record (the pair round) against the sort's 56 and more.
+// Ends: one kernel over the run order.  Pairs: the pair keys in slots of two records, a stable radix sort by the high half and one by the
+// low half (the 128-bit order), group heads, scores where a group has more than one pair, arg-best by atomicMax on the group head's entry,
+// marks.  Fragments: the same over one sort of all end keys; a group that holds an end of a pair marks its fragments without a score.
+int mark_duplicates(ngm_bam_sort *s) {
+	const uint64_t n = s->n_rec, m = (n + 1) / 2;
+	hipStream_t st = s->st;
+	auto timed = [&](int which, auto &&work) -> int {   // kernel ms by events, as for the sort itself
+		NGM_HIP_TRY(hipEventRecord(s->ev0, st));
+		if (int rc = work()) return rc;
+		NGM_HIP_TRY(hipEventRecord(s->ev1, st));
+		NGM_HIP_TRY(hipStreamSynchronize(st));
+		float t = 0.f;
+		if (hipEventElapsedTime(&t, s->ev0, s->ev1) == hipSuccess) s->md_ms[which] += t;
+		return 0;
+	};
+	Buf<uint8_t> tmp;
+	auto sort64 = [&](auto keys_in, uint64_t *keys_out, auto vals_in, uint32_t *vals_out, uint64_t count) -> int {
+		size_t tb = 0;
+		NGM_HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, keys_in, keys_out, vals_in, vals_out, (size_t) count, 0, 64, st));
+		if (tb + 16 > tmp.n && tmp.alloc(tb + 16)) return out_of_memory(s, "the sort of duplicate marking", tb);
+		return timed(1, [&]() -> int { NGM_HIP_TRY(rocprim::radix_sort_pairs(tmp.p, tb, keys_in, keys_out, vals_in, vals_out, (size_t) count, 0, 64, st)); return 0; });
+	};
+	auto head_places = [&](uint32_t *hp, uint64_t count) -> int {   // in place: hp[r] = the place of r's group head
+		size_t tb = 0;
+		NGM_HIP_TRY(rocprim::inclusive_scan(nullptr, tb, hp, hp, (size_t) count, rocprim::maximum<uint32_t>(), st));
+		if (tb + 16 > tmp.n && tmp.alloc(tb + 16)) return out_of_memory(s, "a scan of duplicate marking", tb);
+		NGM_HIP_TRY(rocprim::inclusive_scan(tmp.p, tb, hp, hp, (size_t) count, rocprim::maximum<uint32_t>(), st));
+		return 0;
+	};
+	const rocprim::counting_iterator<uint32_t> iota(0u);
+	Buf<uint64_t> ptr, ek;
+	Buf<uint8_t> kind, need;
+	Buf<uint32_t> score;
+	Buf<unsigned long long> ctr;
+	if (ptr.alloc(n) || ek.alloc(n) || kind.alloc(n) || need.alloc(n) || score.alloc(n) || ctr.alloc(md::kCounters)) return out_of_memory(s, "duplicate marking", (size_t) n * 22);
+	unsigned long long h_ctr[md::kCounters] = {0, 0, 0, 0, 0, 0};
+	if (int rc = timed(0, [&]() -> int {
+		NGM_HIP_TRY(hipMemsetAsync(ctr.p, 0, sizeof(h_ctr), st));
+		uint64_t g0 = 0;
+		for (const Segment &sg : s->segs) {
+			if (!sg.n_rec) continue;
+			hipLaunchKernelGGL(md::ptrs_kernel, dim3(blocks_of(sg.n_rec)), dim3(256), 0, st, (const uint8_t *) sg.d, (const uint32_t *) sg.d_rec_off, sg.n_rec, g0, ptr.p);
+			NGM_HIP_TRY(hipGetLastError());
+			g0 += sg.n_rec;
+		}
+		hipLaunchKernelGGL(md::ends_kernel, dim3(blocks_of(n)), dim3(256), 0, st, (const uint64_t *) ptr.p, n, ek.p, kind.p, ctr.p);
+		NGM_HIP_TRY(hipGetLastError());
+		NGM_HIP_TRY(hipMemcpyAsync(h_ctr, ctr.p, sizeof(h_ctr), hipMemcpyDeviceToHost, st));
+		return 0;
+	})) return rc;
+	const uint64_t n_exam = h_ctr[md::kExamined], n_pairs = h_ctr[md::kPairs];
+	if (n_pairs > 0) {
+		Buf<uint64_t> hi, lo, k1, k2;
+		Buf<uint32_t> i1, i2;
+		if (hi.alloc(m) || lo.alloc(m) || k1.alloc(m) || k2.alloc(m) || i1.alloc(m) || i2.alloc(m)) return out_of_memory(s, "the pairs of duplicate marking", (size_t) m * 40);
+		if (int rc = timed(0, [&]() -> int {
+			NGM_HIP_TRY(hipMemsetAsync(hi.p, 0xFF, m * 8, st));
+			NGM_HIP_TRY(hipMemsetAsync(lo.p, 0xFF, m * 8, st));
+			NGM_HIP_TRY(hipMemsetAsync(need.p, 0, n, st));
+			hipLaunchKernelGGL(md::pair_keys_kernel, dim3(blocks_of(n)), dim3(256), 0, st, (const uint64_t *) ek.p, (const uint8_t *) kind.p, n, lo.p, hi.p);
+			NGM_HIP_TRY(hipGetLastError());
+			return 0;
+		})) return rc;
+		// stable, the high half first: (lo, hi) ascending, equal keys in run order; the slots without a pair (kNoKey) end up behind the n_pairs pairs
+		if (int rc = sort64((const uint64_t *) hi.p, k1.p, iota, i1.p, m)) return rc;
+		if (int rc = timed(0, [&]() -> int {
+			hipLaunchKernelGGL(md::gather64_kernel, dim3(blocks_of(m)), dim3(256), 0, st, (const uint32_t *) i1.p, m, (const uint64_t *) lo.p, k2.p);
+			NGM_HIP_TRY(hipGetLastError());
+			return 0;
+		})) return rc;
+		if (int rc = sort64((const uint64_t *) k2.p, k1.p, (const uint32_t *) i1.p, i2.p, m)) return rc;
+		// k1: the low halves in their final order, k2: the high halves to match; lo becomes the groups' best, i1 their head places
+		unsigned long long *best = (unsigned long long *) lo.p;
+		uint32_t *hp = i1.p;
+		const dim3 grid(blocks_of(n_pairs));
+		if (int rc = timed(0, [&]() -> int {
+			hipLaunchKernelGGL(md::gather64_kernel, grid, dim3(256), 0, st, (const uint32_t *) i2.p, n_pairs, (const uint64_t *) hi.p, k2.p);
+			NGM_HIP_TRY(hipGetLastError());
+			NGM_HIP_TRY(hipMemsetAsync(best, 0, n_pairs * 8, st));
+			hipLaunchKernelGGL(md::heads_kernel, grid, dim3(256), 0, st, (const uint64_t *) k1.p, (const uint64_t *) k2.p, n_pairs, hp);
+			NGM_HIP_TRY(hipGetLastError());
+			if (int rc = head_places(hp, n_pairs)) return rc;
+			hipLaunchKernelGGL(md::pair_need_kernel, grid, dim3(256), 0, st, (const uint32_t *) i2.p, (const uint32_t *) hp, n_pairs, (const uint8_t *) kind.p, need.p);
+			NGM_HIP_TRY(hipGetLastError());
+			hipLaunchKernelGGL(md::scores_kernel, dim3(blocks_of(n)), dim3(256), 0, st, (const uint64_t *) ptr.p, n, (const uint8_t *) need.p, score.p);
+			NGM_HIP_TRY(hipGetLastError());
+			hipLaunchKernelGGL(md::pair_best_kernel, grid, dim3(256), 0, st, (const uint32_t *) i2.p, (const uint32_t *) hp, n_pairs, (const uint8_t *) kind.p, (const uint32_t *) score.p, best);
+			NGM_HIP_TRY(hipGetLastError());
+			hipLaunchKernelGGL(md::pair_mark_kernel, grid, dim3(256), 0, st, (const uint32_t *) i2.p, (const uint32_t *) hp, n_pairs, (const uint8_t *) kind.p, (const uint32_t *) score.p,
+					(const unsigned long long *) best, (const uint64_t *) ptr.p, ctr.p);
+			NGM_HIP_TRY(hipGetLastError());
+			return 0;
+		})) return rc;
+	}
+	if (n_exam > 0) {
+		Buf<uint64_t> ek_s;
+		Buf<uint32_t> idx, hp;
+		if (ek_s.alloc(n) || idx.alloc(n)) return out_of_memory(s, "the end keys of duplicate marking", (size_t) n * 12);
+		if (int rc = sort64((const uint64_t *) ek.p, ek_s.p, iota, idx.p, n)) return rc;   // (the ignored records, kNoKey, behind the n_exam examined ones)
+		tmp.release();
+		if (hp.alloc(n_exam)) return out_of_memory(s, "the groups of duplicate marking", (size_t) n_exam * 4);
+		unsigned long long *best = (unsigned long long *) ek.p;   // (the unsorted keys are done with)
+		const dim3 grid(blocks_of(n_exam));
+		if (int rc = timed(0, [&]() -> int {
+			NGM_HIP_TRY(hipMemsetAsync(best, 0, n_exam * 8, st));
+			NGM_HIP_TRY(hipMemsetAsync(need.p, 0, n, st));
+			hipLaunchKernelGGL(md::heads_kernel, grid, dim3(256), 0, st, (const uint64_t *) ek_s.p, (const uint64_t *) nullptr, n_exam, hp.p);
+			NGM_HIP_TRY(hipGetLastError());
+			if (int rc = head_places(hp.p, n_exam)) return rc;
+			if (n_pairs > 0) {
+				hipLaunchKernelGGL(md::pair_ends_kernel, grid, dim3(256), 0, st, (const uint32_t *) idx.p, (const uint32_t *) hp.p, n_exam, (const uint8_t *) kind.p, best);
+				NGM_HIP_TRY(hipGetLastError());
+			}
+			hipLaunchKernelGGL(md::frag_need_kernel, grid, dim3(256), 0, st, (const uint32_t *) idx.p, (const uint32_t *) hp.p, n_exam, (const uint8_t *) kind.p, (const unsigned long long *) best, need.p);
+			NGM_HIP_TRY(hipGetLastError());
+			hipLaunchKernelGGL(md::scores_kernel, dim3(blocks_of(n)), dim3(256), 0, st, (const uint64_t *) ptr.p, n, (const uint8_t *) need.p, score.p);
+			NGM_HIP_TRY(hipGetLastError());
+			hipLaunchKernelGGL(md::frag_best_kernel, grid, dim3(256), 0, st, (const uint32_t *) idx.p, (const uint32_t *) hp.p, n_exam, (const uint8_t *) kind.p, (const uint32_t *) score.p, best);
+			NGM_HIP_TRY(hipGetLastError());
+			hipLaunchKernelGGL(md::frag_mark_kernel, grid, dim3(256), 0, st, (const uint32_t *) idx.p, (const uint32_t *) hp.p, n_exam, (const uint8_t *) kind.p, (const uint32_t *) score.p,
+					(const unsigned long long *) best, (const uint64_t *) ptr.p, ctr.p);
+			NGM_HIP_TRY(hipGetLastError());
+			return 0;
+		})) return rc;
+	}
+	NGM_HIP_TRY(hipMemcpyAsync(h_ctr, ctr.p, sizeof(h_ctr), hipMemcpyDeviceToHost, st));
+	NGM_HIP_TRY(hipStreamSynchronize(st));
+	for (int k = 0; k < md::kCounters; ++k) s->md_counts[k] = h_ctr[k];
+	return 0;
+}
+}  // namespace
+
 extern "C" int ngm_bam_sort_finish(ngm_bam_sort *s, int n_ref) {
 	if (!s || n_ref < 0) { ngm::pipeline_set_error("ngm_bam_sort_finish: bad arguments"); return -22; }
 	std::lock_guard<std::mutex> lk(s->mu);
@@ -213,6 +364,7 @@ extern "C" int ngm_bam_sort_finish(ngm_bam_sort *s, int n_ref) {
 	s->n_chunks = (s->total_bytes + s->chunk_bytes - 1) / s->chunk_bytes;
 	s->C.assign(1, 0);
 	if (n == 0) { s->sorted = true; return 0; }
+	if (s->markdup) { if (int rc = mark_duplicates(s)) return rc; }   // (its scratch is free again before the sort's arrays are allocated)
 	Buf<uint64_t> key_in, ptr, s_len;
 	Buf<uint32_t> idx_in, idx, len, end_in, bin_flag;
 	Buf<unsigned long long> ctr;   // [0] the first record to refuse, [1] records without a reference
@@ -429,5 +581,14 @@ extern "C" int ngm_bam_sort_stats(const ngm_bam_sort *s, uint64_t counts[5], flo
 	if (!s) return -22;
 	if (counts) { counts[0] = s->n_rec; counts[1] = s->total_bytes; counts[2] = s->C.empty() ? 0 : s->C.size() - 1; counts[3] = s->next_chunk; counts[4] = s->n_bins; }
 	if (ms) for (int k = 0; k < 5; ++k) ms[k] = s->ms[k];
+	return 0;
+}
+
+extern "C" int ngm_bam_sort_markdup_stats(const ngm_bam_sort *s, uint64_t counts[6], float ms[2]) {
+	if (!s) { ngm::pipeline_set_error("ngm_bam_sort_markdup_stats: bad arguments"); return -22; }
+	if (!s->markdup) { ngm::pipeline_set_error("ngm_bam_sort_markdup_stats: duplicate marking is off (ngm_bam_sort_set_markdup)"); return -22; }
+	if (!s->sorted) { ngm::pipeline_set_error("ngm_bam_sort_markdup_stats: ngm_bam_sort_finish has not succeeded"); return -22; }
+	if (counts) for (int k = 0; k < md::kCounters; ++k) counts[k] = s->md_counts[k];
+	if (ms) { ms[0] = s->md_ms[0]; ms[1] = s->md_ms[1]; }
 	return 0;
 }

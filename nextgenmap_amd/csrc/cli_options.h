@@ -26,6 +26,7 @@ struct Opts {
 	int skip_save = 0, bam = 0, workers = 2, serial_reader = 0, keep_tags = 0;
 	int argos = 0, kmer_min_set = 0;
 	int sort = 0;   // --sort (ours): the BAM coordinate-sorted on the GPU, with its .bai (csrc/bam_sort.cpp)
+	int markdup = 0;   // --markdup (ours, with --sort): duplicates get flag 0x400 in the sorter's memory before the sort (csrc/markdup.h)
 	std::string coverage;   // --coverage FILE (ours): the depth of the mapped primary records as bedGraph, made on the GPU (csrc/coverage.cpp)
 	std::string snp, snp_frac_text = "0.8";   // --snp FILE (ours): SNP calls of the mapped primary records as VCF, made on the GPU (csrc/snp.cpp); --snp-min-frac as given
 	long snp_min_cov = 10, snp_min_qual = 15;   // --snp-min-cov, --snp-min-qual
@@ -54,7 +55,7 @@ inline Opts parse(int argc, char **argv) {
 	Opts o;
 	for (int i = 1; i < argc; ++i) { if (i > 1) o.cmdline += " "; o.cmdline += argv[i]; }  // Config.cpp:565-574
 	enum { KSKIP = 1000, HARD, SILENT, KMIN, MB, MMP, GRP, GFP, MAXCMRS, NOUNAL, NOPROG, MAXRL, BINSZ, MAXKF, VFAST, FAST, SENS, VSENS, DEVICE,
-		SKIPSAVE, BATCH, VARIANT, SHARD, SHARDOUT, KEEPSHARDS, BAMOUT, WORKERS, SERIAL, AFFINE, GEP, PEDELIM, STRATA, BSMAP, BSCUT, MBTT, MBTC, SLAM, FASTPAIR, BROKENPAIRS, REFSCOREBUF, STATSFD, MAXPOLYA, RG0, RG_LAST = RG0 + 11, ARGOS, ARGOSMIN, VCF, KEEPTAGS, PARSEALL, SORTOUT, COVERAGE, SNP, SNPCOV, SNPFRAC, SNPQUAL, COUNT, COUNTOUT, COUNTQUAL, UNSUPPORTED };
+		SKIPSAVE, BATCH, VARIANT, SHARD, SHARDOUT, KEEPSHARDS, BAMOUT, WORKERS, SERIAL, AFFINE, GEP, PEDELIM, STRATA, BSMAP, BSCUT, MBTT, MBTC, SLAM, FASTPAIR, BROKENPAIRS, REFSCOREBUF, STATSFD, MAXPOLYA, RG0, RG_LAST = RG0 + 11, ARGOS, ARGOSMIN, VCF, KEEPTAGS, PARSEALL, SORTOUT, MARKDUP, COVERAGE, SNP, SNPCOV, SNPFRAC, SNPQUAL, COUNT, COUNTOUT, COUNTQUAL, UNSUPPORTED };
 	static const option lo[] = {
 		{"ref", required_argument, 0, 'r'}, {"qry", required_argument, 0, 'q'}, {"output", required_argument, 0, 'o'},
 		{"cpu-threads", required_argument, 0, 't'}, {"gpu", no_argument, 0, 'g'}, {"sensitivity", required_argument, 0, 's'},
@@ -80,7 +81,7 @@ inline Opts parse(int argc, char **argv) {
 		{"bs-cutoff", required_argument, 0, BSCUT}, {"match-bonus-tt", required_argument, 0, MBTT}, {"match-bonus-tc", required_argument, 0, MBTC},
 		{"slam-seq", required_argument, 0, SLAM}, {"topn", required_argument, 0, 'n'}, {"strata", no_argument, 0, STRATA},
 		{"argos", no_argument, 0, ARGOS}, {"argos-min-score", required_argument, 0, ARGOSMIN}, {"vcf", required_argument, 0, VCF},
-		{"keep-tags", no_argument, 0, KEEPTAGS}, {"parse-all", no_argument, 0, PARSEALL}, {"sort", no_argument, 0, SORTOUT}, {"coverage", required_argument, 0, COVERAGE},
+		{"keep-tags", no_argument, 0, KEEPTAGS}, {"parse-all", no_argument, 0, PARSEALL}, {"sort", no_argument, 0, SORTOUT}, {"markdup", no_argument, 0, MARKDUP}, {"coverage", required_argument, 0, COVERAGE},
 		{"snp", required_argument, 0, SNP}, {"snp-min-cov", required_argument, 0, SNPCOV}, {"snp-min-frac", required_argument, 0, SNPFRAC}, {"snp-min-qual", required_argument, 0, SNPQUAL},
 		{"count", required_argument, 0, COUNT}, {"count-out", required_argument, 0, COUNTOUT}, {"count-min-qual", required_argument, 0, COUNTQUAL},
 		{"trim5", required_argument, 0, '5'}, {"max-polya", required_argument, 0, MAXPOLYA}, {"config", required_argument, 0, UNSUPPORTED},
@@ -169,6 +170,7 @@ inline Opts parse(int argc, char **argv) {
 		case PARSEALL: break;                    // every record of a SAM / BAM input is a read: the default (Config.cpp:489)
 		case ARGOSMIN: o.argos_min = (float) atof(optarg); break;
 		case SORTOUT: o.sort = 1; break;
+		case MARKDUP: o.markdup = 1; break;
 		case COVERAGE: o.coverage = optarg; if (o.coverage.empty()) die("--coverage expects a file name"); break;
 		case SNP: o.snp = optarg; if (o.snp.empty()) die("--snp expects a file name"); break;
 		case SNPCOV: { char *e = nullptr; o.snp_min_cov = strtol(optarg, &e, 10); if (e == optarg || *e || o.snp_min_cov < 0 || o.snp_min_cov > 2147483647L) die("--snp-min-cov expects a count of 0 or more"); break; }
@@ -182,6 +184,7 @@ inline Opts parse(int argc, char **argv) {
 		}
 	}
 	if (o.ref.empty()) die("no reference given (-r/--ref)");
+	if (o.markdup && !o.sort) die("--markdup needs --sort: duplicates are found among the records the sorter holds");
 	if (o.sort) {
 		// the sort is over the records of the whole run, kept in the first GPU's memory; refused before any GPU work
 		if (o.argos) die("--sort cannot be combined with --argos: argos output is text lines, not BAM records");

@@ -14,7 +14,7 @@
 // GPU -- single-end only, see ngm_mapper_map_argos), bisulfite (--bs-mapping) and SLAM-seq (--slam-seq) mapping, -5/--trim5 and --max-polya
 // (csrc/read_trim.h), and --sort (ours, with --bam: the records of the whole run stay in GPU memory, are sorted there into coordinate order and
 // written as the sorted BAM plus <output>.bai, csrc/bam_sort.cpp; not with --argos, --shard, --shard-output, NGM_HIP_BAM_ZLIB=1, nor a
-// contig above 2^29 bases), and --coverage FILE (ours: the per-base depth of the run's mapped primary records as bedGraph, counted and turned into text on the
+// contig above 2^29 bases; with --markdup duplicate records get flag 0x400 there before the sort, csrc/markdup.h), and --coverage FILE (ours: the per-base depth of the run's mapped primary records as bedGraph, counted and turned into text on the
 // GPU, csrc/coverage.cpp; not with --argos, --shard, --shard-output, nor FILE = the output), and --snp FILE with --snp-min-cov / --snp-min-frac /
 // --snp-min-qual (ours: the mismatch pileup of the same records and its single-base substitution calls as VCF, counted and turned into text on the GPU,
 // csrc/snp.cpp; not with --argos, --shard, --shard-output, --bs-mapping, --vcf, nor FILE = the output or the --coverage file), and --count BED --count-out FILE
@@ -806,6 +806,7 @@ void Run::create_mappers_and_side_outputs() {
 		sp.device = o.devices[0];
 		sorter = ngm_bam_sort_create(&sp);
 		if (!sorter) die(ngm_pipeline_last_error());
+		if (o.markdup && ngm_bam_sort_set_markdup(sorter, 1) < 0) die(ngm_pipeline_last_error());
 		if (route.gpu_sam) for (Worker &w : workers) if (ngm_mapper_set_bam_sorter(w.m, sorter) < 0) die(ngm_pipeline_last_error());
 	}
 	uint64_t bases = 0;
@@ -1383,6 +1384,14 @@ void Run::finish_sort() {
 	infof("MAIN", "Sorted on the GPU: %llu records (%.1f MiB held in GPU memory); kernels: keys %.2f ms, sort %.2f ms, gather %.2f ms, deflate %.2f ms, index %.2f ms; "
 			"%llu members in %llu chunks, %llu bins; %.3f s after the last batch", (unsigned long long) sc[0], (double) sc[1] / (double) (1 << 20), sm[0], sm[1], sm[2], sm[3], sm[4],
 			(unsigned long long) sc[2], (unsigned long long) sc[3], (unsigned long long) sc[4], span_s(t_sort));
+	if (o.markdup) {
+		uint64_t dc[6] = {0, 0, 0, 0, 0, 0};
+		float dm[2] = {0, 0};
+		if (ngm_bam_sort_markdup_stats(sorter, dc, dm) < 0) { fail(ngm_pipeline_last_error()); return; }
+		infof("SORT", "Duplicates marked on the GPU: %llu records examined, %llu pairs, %llu fragments, %llu duplicate pairs, %llu duplicate fragments, %llu records newly marked; "
+				"kernels: marking %.2f ms, sorts %.2f ms", (unsigned long long) dc[0], (unsigned long long) dc[1], (unsigned long long) dc[2], (unsigned long long) dc[3],
+				(unsigned long long) dc[4], (unsigned long long) dc[5], dm[0], dm[1]);
+	}
 }
 
 // --coverage, --snp: every batch has added its records.  The counters become text chunk by chunk on the GPU (finish, then next until it

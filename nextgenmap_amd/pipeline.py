@@ -139,6 +139,8 @@ def _lib():
         lib.ngm_bam_sort_index.restype = C.c_longlong
         lib.ngm_bam_sort_index.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t]
         lib.ngm_bam_sort_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.ngm_bam_sort_set_markdup.argtypes = [C.c_void_p, C.c_int]
+        lib.ngm_bam_sort_markdup_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.ngm_mapper_set_bam_sorter.argtypes = [C.c_void_p, C.c_void_p]
         lib.ngm_coverage_create.restype = C.c_void_p
         lib.ngm_coverage_create.argtypes = [C.POINTER(CoverageParams)]
@@ -302,15 +304,33 @@ def _pack_records(records, with_reverse):
 
 class BamSorter(_Handle):
     """The BAM records of a run kept in GPU memory, sorted there into coordinate order and handed back as the BGZF members of the sorted
-    file plus its BAI index (include/ngm_pipeline.h, ngm_bam_sort_*): what `ngm-hip --sort` writes."""
+    file plus its BAI index (include/ngm_pipeline.h, ngm_bam_sort_*): what `ngm-hip --sort` writes.  markdup=True: finish() sets flag 0x400
+    on duplicate records before it sorts them (`--markdup`; the rules: INTEGRATION.md)."""
 
     _prefix = "bam_sort"
 
-    def __init__(self, device=0, chunk_bytes=0, max_bytes=0):
+    def __init__(self, device=0, chunk_bytes=0, max_bytes=0, markdup=False):
         p = BamSortParams(device, chunk_bytes, max_bytes)
         self._h = _lib().ngm_bam_sort_create(C.byref(p))
         if not self._h:
             raise _err()
+        if markdup:
+            self.set_markdup(True)
+
+    def set_markdup(self, on):
+        """only before the first add()"""
+        if _lib().ngm_bam_sort_set_markdup(self._h, 1 if on else 0) < 0:
+            raise _err()
+
+    def markdup_stats(self):
+        """after finish() with marking on"""
+        counts = (C.c_uint64 * 6)()
+        ms = (C.c_float * 2)()
+        if _lib().ngm_bam_sort_markdup_stats(self._h, counts, ms) < 0:
+            raise _err()
+        d = dict(zip(("examined", "pairs", "fragments", "duplicate_pairs", "duplicate_fragments", "newly_marked"), (int(x) for x in counts)))
+        d.update(zip(("mark_ms", "sort_ms"), (float(x) for x in ms)))
+        return d
 
     def add(self, seq, records):
         """a run of whole uncompressed BAM records; seq orders the runs"""
