@@ -139,7 +139,7 @@ extern "C" int ngm_count_add(ngm_count *c, const int32_t *ref_id, const int32_t 
 	return c->add_kernel([&] { hipLaunchKernelGGL(ct::count_add_kernel<ct::CountArrays>, dim3(blocks_of(n)), dim3(256), 0, c->st, S, layout_of(c), counters_of(c)); });
 }
 
-// the mapper's in-place route (mapper.cpp): the tables and counters its count_add_kernel works with
+// the mapper's in-place route (mapper_sam.cpp): the tables and counters its count_add_kernel works with
 side::Base *ngm::side::base(ngm_count *c) { return c; }
 int ngm::count_target(ngm_count *c, ngm::cnt::Layout *l, ngm::cnt::Counters *t) {
 	std::unique_lock<std::mutex> lk;

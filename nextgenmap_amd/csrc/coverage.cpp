@@ -70,7 +70,7 @@ extern "C" int ngm_coverage_add(ngm_coverage *c, const int32_t *ref_id, const in
 	return c->add_kernel([&] { hipLaunchKernelGGL(cv::cov_add_kernel<cv::CovArrays>, dim3(blocks_of(n)), dim3(256), 0, c->st, S, c->counters.p, (const uint64_t *) c->d_off.p, c->n_ref, c->d_tot.p); });
 }
 
-// the mapper's in-place route (mapper.cpp): where its cov_add_kernel adds
+// the mapper's in-place route (mapper_sam.cpp): where its cov_add_kernel adds
 side::Base *ngm::side::base(ngm_coverage *c) { return c; }
 int ngm::coverage_target(ngm_coverage *c, cv::Target *t) {
 	std::unique_lock<std::mutex> lk;

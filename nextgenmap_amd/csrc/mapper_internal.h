@@ -1,5 +1,10 @@
-// mapper_internal.h -- what the translation units of the mapping path share (mapper.cpp: score / select / align / SAM stages and the C
-// entry points; mapper_search.cpp: candidate search and the candidate-order replay): the mapper's state, the stage lock, error plumbing.
+// mapper_internal.h -- what the translation units of the mapping path share: the mapper's state, the stage lock, error plumbing, and
+// MapBatch -- one map call's state, which the stages of map_impl hand on.
+//   mapper.cpp         life cycle, C entry points, map_impl and its stages begin / search_and_score / align / finish_hits / kernel_times
+//   mapper_select.cpp  the select stage (host only: single-end ties, top1PE passes 1-4 with the paired-end turn, --strata, topNSE)
+//   mapper_sam.cpp     the write_sam stage (SAM / BAM text, side outputs, sorter and BGZF routes) and the SAM entry points
+//   mapper_search.cpp  candidate search and the candidate-order replay
+//   mapper_argos.cpp   --argos
 #pragma once
 
 #include <algorithm>
@@ -36,6 +41,12 @@
 			ngm::pipeline_set_error("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
 			return -5;                                                                         \
 		}                                                                                      \
+	} while (0)
+
+// a reserve (or several joined with ||) that found no memory: the error text, -12
+#define MAP_OOM_TRY(failed, text)                                                              \
+	do {                                                                                       \
+		if (failed) { ngm::pipeline_set_error(text); return -12; }                             \
 	} while (0)
 
 // ScoreBuffer's running insert-size sum / count (src/ScoreBuffer.h:90) when several mapper instances work on one input:
@@ -265,5 +276,79 @@ long test_limit(const char *key, long dflt);   // NGM_HIP_TEST_LIMITS (mapper_se
 // ---- mapper.cpp / mapper_argos.cpp ---------------------------------------------------------------------------------------------------
 int score_candidates(ngm_mapper *m, int n, uint64_t np, int alt_dir);   // window gather + BatchScore of the batch's candidates into d_scores
 void argos_release(ngm_mapper *m);   // the --argos buffers (ngm_mapper_destroy)
+
+// per-read host loops run on the process-wide persistent pool (thread_pool.h): shared by the mapper instances, sized
+// to this rank's share of the host cores; no threads are started per call
+template <typename F>
+void parallel_for(int n, F f, int min_grain = 0) {
+	ngm::ThreadPool::instance().parallel_for(n, f, min_grain > 0 ? min_grain : 2048);
+}
+
+// ---- one map call (map_impl, mapper.cpp) ---------------------------------------------------------------------------------------------
+// the SAM stage of a call (ngm_mapper_map_sam): inputs the records need beyond the reads, where the text goes
+struct SamCall { const char *quals; const char *names; size_t names_bytes; const ngm::SamMeta *meta; const uint16_t *polya; char *out; size_t out_cap; uint64_t *stats; long long text_bytes; float kernel_ms; };
+
+// shared paired-end state: wait for this batch's turn before the running mean is read, pass it on when the batch is
+// done with it (also on EVERY early return, the argument checks included: with a shared ngm_pair_state a batch that
+// never passes its turn on would block all later ones)
+struct PairTurn {
+	ngm_mapper *m; bool active, held = false;
+	void acquire() {
+		if (!active || held) return;
+		std::unique_lock<std::mutex> lk(m->ps->mu);
+		m->ps->cv.wait(lk, [&] { return m->ps->next == m->batch_seq; });
+		m->pair_dist_sum = m->ps->dist_sum; m->pair_dist_count = m->ps->dist_count; m->scores_so_far = m->ps->scores_so_far; m->reads_so_far = m->ps->reads_so_far;
+		held = true;
+	}
+	void release() {  // the running mean is final for this batch: the next batch may read it (align + CIGAR of this one go on)
+		if (!active || released) return;
+		acquire();
+		{ std::lock_guard<std::mutex> lk(m->ps->mu); m->ps->dist_sum = m->pair_dist_sum; m->ps->dist_count = m->pair_dist_count; m->ps->scores_so_far = m->scores_so_far; m->ps->reads_so_far = m->reads_so_far; m->ps->next = m->batch_seq + 1; }
+		m->ps->cv.notify_all();
+		released = true;
+	}
+	bool released = false;
+	~PairTurn() { release(); }
+};
+
+// What the stages of one map call share.  A local of map_impl: the members with a destructor are its scope objects -- the paired-end
+// turn is passed on, the mapper's own read buffer put back and the search + score turn given up on every return.
+struct MapBatch {
+	ngm_mapper *m; int n; const char *reads; const void *d_reads_ext; ngm_hit *hits; char *cigars, *mds; bool paired; SamCall *sam;
+	// (these three are built before the argument checks and the device guard of map_impl and go after that guard: their constructors
+	// and destructors must stay free of HIP calls -- a mutex, a condition variable, a pointer put back -- and keep this order)
+	PairTurn pair_turn;
+	// reads already in HBM are aliased as the batch (begin); the mapper's own buffer comes back when the call ends
+	struct Restore { ngm_mapper *m; ngm::DevBuf<uint8_t> own; bool on; ~Restore() { if (on) m->d_reads = own; } } restore;
+	GpuStage stage_cs;   // the turn begins at the search's first enqueue (run_cs takes it) and ends in the select stage
+	int q = 0, c = 0, topn = 1, alt_cigar = 0, alt_dir = 0;
+	size_t str_stride = 0;
+	uint64_t np = 0;          // candidates of the batch
+	uint64_t regrown = 0;     // candidate-sized buffers that grew behind the search's synchronisation (turn_dbg[2])
+	bool host_timing = false;
+	bool pe_select = false, simple_on_gpu = false, choice_on_gpu = false;   // which side selects the pairs (search_and_score decides, select reads)
+	uint32_t *h_winner = nullptr, *h_loc = nullptr, *h_sv = nullptr;
+	int32_t *h_mapq = nullptr, *h_nbest = nullptr;
+	float *h_best = nullptr, *h_scores = nullptr;
+	std::vector<int> pair_flags;
+	std::vector<uint32_t> tn_pairs;  // topn > 1: per output entry the candidate (pair index) to align, or none
+	std::vector<uint32_t> a_read, a_loc, a_sv, a_out, a_pair;   // the align stage's lists: one entry per alignment
+	int na = 0;
+	int align_buf_len = 0;      // AlignmentBuffer.h:67: (qry_max_len + corridor) | 1 + 1
+	bool dev_strings = true;    // CIGAR / MD / NM / identity on the GPU (cigar_device.h); NGM_HIP_HOST_CIGAR=1 keeps the host builders (tests)
+	int32_t *h_rec = nullptr;   // the align stage's records and compacted runs on the host (where the host builds strings)
+	uint16_t *h_runs = nullptr;
+	uint64_t str_base = 0;   // bytes of the device's CIGAR / MD stream (host-built strings of the SAM stage go behind them)
+	std::vector<char> extra;   // ... those strings
+	ngm::SamRef *sam_refs = nullptr;
+	std::chrono::steady_clock::time_point tp0;
+	double t_stage[6] = {0, 0, 0, 0, 0, 0};
+	void lap(int k) { auto t = std::chrono::steady_clock::now(); t_stage[k] += std::chrono::duration<double, std::milli>(t - tp0).count(); tp0 = t; }
+	MapBatch(ngm_mapper *m_, int n_, const char *reads_, const void *d_reads_ext_, ngm_hit *hits_, char *cigars_, char *mds_, bool paired_, SamCall *sam_)
+		: m(m_), n(n_), reads(reads_), d_reads_ext(d_reads_ext_), hits(hits_), cigars(cigars_), mds(mds_), paired(paired_), sam(sam_),
+		  pair_turn{m_, paired_ && m_->ps != nullptr}, restore{m_, m_->d_reads, d_reads_ext_ != nullptr}, stage_cs(m_, 0, false) {}
+};
+int select(MapBatch &b);      // mapper_select.cpp: from behind the score stage's synchronisation to the end of the search + score turn
+int write_sam(MapBatch &b);   // mapper_sam.cpp: the batch's records as SAM / BAM text, side outputs, sorter and BGZF routes
 
 }  // namespace ngm

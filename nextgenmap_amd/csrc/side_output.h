@@ -91,7 +91,7 @@ struct Base {
 	}
 };
 
-// the mapper's SAM stage (mapper.cpp): the device an object lives on, and the time an add kernel on the mapper's stream took
+// the mapper's SAM stage (mapper_sam.cpp): the device an object lives on, and the time an add kernel on the mapper's stream took
 inline int device(const Base *b) { return b ? b->device : -1; }
 inline void note_add_ms(Base *b, float t) { if (b) b->note_add_ms(t); }
 

@@ -101,7 +101,7 @@ extern "C" int ngm_snp_add(ngm_snp *c, const int32_t *ref_id, const int32_t *pos
 	return c->add_kernel([&] { hipLaunchKernelGGL(sn::snp_add_kernel<sn::SnpArrays>, dim3(blocks_of(n)), dim3(256), 0, c->st, S, target_of(c)); });
 }
 
-// the mapper's in-place route (mapper.cpp): where its snp_add_kernel adds
+// the mapper's in-place route (mapper_sam.cpp): where its snp_add_kernel adds
 side::Base *ngm::side::base(ngm_snp *c) { return c; }
 int ngm::snp_target(ngm_snp *c, ngm::snp::Target *t) {
 	std::unique_lock<std::mutex> lk;

@@ -191,3 +191,55 @@ def test_host_threads_are_pinned_to_the_gpus_numa_node():
     assert out["n"] >= 0
     if out["n"] > 0:
         assert out["cpus"] == out["n"]
+
+
+def test_a_refused_paired_batch_passes_its_turn_on():
+    """With a shared ngm_pair_state the batches take turns in input order.  A batch that map_impl refuses at its argument checks (an odd
+    number of reads: -22, before any GPU work) must still pass the turn on, or the next batch waits for ever: batch 0 is refused, batch 1
+    of the same mapper then maps -- in a thread with a time limit; the wait in question is a host condition variable, not GPU work -- and
+    gives what a mapper without shared state gives."""
+    import ctypes as C
+    import threading
+    from nextgenmap_amd.pipeline import HIT_DTYPE, Mapper, Reference
+    rng = np.random.default_rng(20261020)
+    genome = np.frombuffer(b"ACGT", np.uint8)[rng.integers(0, 4, 20000)]
+    comp = np.zeros(256, np.uint8)
+    comp[list(b"ACGT")] = list(b"TGCA")
+    reads = []
+    for p in rng.integers(100, 19000, 8):
+        reads += [genome[p:p + 50], comp[genome[p + 250:p + 300]][::-1]]
+    q, c = 52, 10
+    ref = Reference.from_contigs([genome])
+    rows = Mapper.reads_to_rows(reads, q)
+    alone = Mapper(ref, q, c)
+    want, want_cig, want_md = alone.map_pe(rows)
+    assert int(want["mapped"].sum()) >= 12 and int((want["pair_flags"] & 1).sum()) >= 12   # (the batch does go through the pair selection)
+    mp = Mapper(ref, q, c)
+    lib = mp.lib
+    lib.ngm_pair_state_create.restype = C.c_void_p
+    lib.ngm_pair_state_destroy.argtypes = [C.c_void_p]
+    lib.ngm_mapper_set_pair_state.argtypes = [C.c_void_p, C.c_void_p]
+    lib.ngm_mapper_set_batch_seq.argtypes = [C.c_void_p, C.c_uint64]
+    lib.ngm_mapper_map_pe.restype = C.c_int
+    lib.ngm_mapper_map_pe.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
+    ps = lib.ngm_pair_state_create()
+    assert ps and lib.ngm_mapper_set_pair_state(mp.h, ps) == 0
+    stride = 4 * q
+    hits, cig, md = np.zeros(16, HIT_DTYPE), np.zeros((16, stride), np.uint8), np.zeros((16, stride), np.uint8)
+    assert lib.ngm_mapper_set_batch_seq(mp.h, 0) == 0
+    assert lib.ngm_mapper_map_pe(mp.h, 3, rows.ctypes.data, hits.ctypes.data, cig.ctypes.data, md.ctypes.data) == -22
+    assert lib.ngm_mapper_set_batch_seq(mp.h, 1) == 0
+    out = {}
+
+    def second():
+        out["rc"] = lib.ngm_mapper_map_pe(mp.h, 16, rows.ctypes.data, hits.ctypes.data, cig.ctypes.data, md.ctypes.data)
+    t = threading.Thread(target=second, daemon=True)
+    t.start()
+    t.join(60)
+    assert not t.is_alive(), "batch 1 still waits for its turn: the refused batch 0 never passed it on"
+    assert out["rc"] == 16
+    assert hits.tobytes() == want.tobytes()
+    assert [bytes(r).split(b"\0", 1)[0] for r in cig] == want_cig and [bytes(r).split(b"\0", 1)[0] for r in md] == want_md
+    mp.close(); alone.close()
+    lib.ngm_pair_state_destroy(ps)
+    ref.close()

@@ -1,4 +1,4 @@
-"""-m gpu: the search + score turn of a mapper (csrc/mapper_search.cpp run_cs, csrc/mapper.cpp map_impl).
+"""-m gpu: the search + score turn of a mapper (csrc/mapper_search.cpp run_cs, csrc/mapper.cpp begin + search_and_score).
 
 By default the per-read arrays of a search -- candidate offsets, counts, best votes -- travel to the host behind the score stage's last
 kernel, outside the turn (cs_enqueue_host_arrays / cs_host_arrays), and the score stage's buffers are reserved in front of the search

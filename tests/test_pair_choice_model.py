@@ -5,7 +5,7 @@ For every generated pair the kernels may decide themselves (not `host`) the lite
 running means:
   * not tied  -> every evaluation gives the same found / winners / insert size, and no "equal" pair is counted: the kernel may settle it;
   * tied, not dup -> no "equal" pair is counted anywhere, and wherever exactly one best-scoring combination is closest to the running
-    mean that combination wins in every order: what closed_between in map_impl (csrc/mapper.cpp) relies on.
+    mean that combination wins in every order: what closed_between in the select stage (csrc/mapper_select.cpp) relies on.
 The same generator feeds tests/test_gpu_pair_choice.py; its coverage of the edges it is there for is asserted here, before any GPU sees it."""
 import numpy as np
 import pytest

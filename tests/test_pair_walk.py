@@ -1,4 +1,4 @@
-"""Host logic, no GPU: what pass 3 of the pair selection does per tied pair (csrc/mapper.cpp sort_like_reference + walk_pair, through the
+"""Host logic, no GPU: what pass 3 of the pair selection does per tied pair (csrc/pair_host.h sort_like_reference + walk_pair, through the
 host-only C-ABI entry ngm_debug_pair_walk) against a restatement of what the reference does there.
 
 ScoreBuffer::top1PE (src/ScoreBuffer.cpp:368-413) sorts both mates' candidate lists with std::sort(sortLocationScore) -- a comparison by
