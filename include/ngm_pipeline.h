@@ -546,6 +546,23 @@ int ngm_debug_expand_pairs(int device, int n_reads, const uint32_t *base, const 
 int ngm_debug_pair_select(int device, int n_pairs, const uint32_t *base, const uint32_t *count, uint64_t n_cand, const float *scores, const uint32_t *loc,
 		const uint16_t *read_len, int min_insert, int max_insert, float cutoff, int32_t *info, int32_t *mapq, int32_t *n_best, uint32_t counts[4], void *entries, void *tops);
 
+/* test hook: the record writers of the SAM stage (sam_lengths_kernel / sam_write_kernel, csrc/sam_device.h) over constructed results, through
+ * the launch sequence ngm_mapper_map_sam runs (lengths, prefix sums, the 32-bit total checked against the 64-bit one, bytes).  Needs no mapper:
+ * opt as for ngm_mapper_set_sam_options; hard_clip / silent_clip / variant as in ngm_mapper_params; alt_scoring: the mapper ran with bs_mapping or
+ * slam_seq & 2 (how the SLAM-seq tags label a column '='); reads, quals: n rows of q bytes; names, meta as for ngm_mapper_map_sam; cigars, mds: n
+ * NUL-terminated strings (NULL: empty); polya: n values or NULL (no XA:i); the contig table: n_contigs names and lengths; ref: only read with
+ * opt->slam_seq (its packed genome; its contigs must be the table's).  out: the SAM text, or with opt->bam the records as they stand in HBM
+ * (uncompressed, no BGZF); counters: reads counted, reads mapped, lines written, bytes, pairs with both mates mapped, of those broken, insert
+ * sizes of the others.  Returns the length of the text (> out_cap: nothing was copied), or < 0.  -22, before anything is launched, for an
+ * input the kernels would index out of bounds with: a name beyond names_bytes or longer than 254 bytes; and for every hit with `mapped`: a
+ * contig outside the table, qstart / qend negative or together beyond the read, a CIGAR that is malformed or whose M / I operations consume more
+ * bases than follow qstart, with slam_seq an alignment that ends beyond its contig.  tests/test_gpu_sam_records.py compares it with
+ * tests/sam_model.py. */
+long long ngm_debug_sam_records(int device, const ngm_sam_options *opt, int hard_clip, int silent_clip, int variant, int alt_scoring, int n, int q,
+		const char *reads, const char *quals, const char *names, size_t names_bytes, const ngm_sam_read *meta, const ngm_hit *hits, const char *const *cigars,
+		const char *const *mds, const uint16_t *polya, int n_contigs, const char *const *contig_names, const uint64_t *contig_lens, const ngm_ref *ref,
+		char *out, size_t out_cap, unsigned long long counters[7]);
+
 /* of path counter [7] (reads searched by the heavy-read kernel, csrc/cs_heavy_device.h), summed over all batches: [0] reads given a second
  * pass (T from the first pass's maximum), [1] table passes started over with twice the parts, [2] reads a class could not certify and
  * queued again, [3] times the pool of global-memory vote tables had to grow (one more synchronisation in that batch) */

@@ -124,34 +124,35 @@ ngm::SamArgs sam_args(const MapBatch &b) {
 	return S;
 }
 
-// lengths per unit, exclusive prefix sum, bytes: *total bytes of text in d_sam_text
-int sam_text_kernels(MapBatch &b, ngm::SamArgs &S, int units, GpuStage &stage_sam, unsigned long long *total) {
-	ngm_mapper *m = b.m;
-	const int n = b.n;
+// The text kernels' launch sequence, shared by write_sam and the test hook ngm_debug_sam_records: lengths per unit, exclusive prefix sum, the
+// 32-bit total checked against the 64-bit sum, bytes.  S is complete but for `out` (unit_len / unit_off are sc.len / sc.off, reserved for
+// units + 1 elements; counters zeroed); *total: bytes of text in sc.text.  stage: the turn taken again in front of the write kernel, or null.
+struct SamScratch { ngm::DevBuf<uint32_t> &len, &off; ngm::DevBuf<uint8_t> &scan_tmp; ngm::DevBuf<char> &text; };
+int sam_text_kernels(ngm::SamArgs &S, int units, const SamScratch &sc, hipStream_t st, GpuStage *stage, const char *who, unsigned long long *total) {
 	const bool bam_slam = S.bam && S.slam_seq;   // (BAM records with SLAM-seq tags: kernels of their own, sam_device.h)
-	if (bam_slam) hipLaunchKernelGGL(ngm::sam_lengths_kernel<true>, dim3((units + 255) / 256), dim3(256), 0, m->st, S, units);
-	else hipLaunchKernelGGL(ngm::sam_lengths_kernel<false>, dim3((units + 255) / 256), dim3(256), 0, m->st, S, units);
+	if (bam_slam) hipLaunchKernelGGL(ngm::sam_lengths_kernel<true>, dim3((units + 255) / 256), dim3(256), 0, st, S, units);
+	else hipLaunchKernelGGL(ngm::sam_lengths_kernel<false>, dim3((units + 255) / 256), dim3(256), 0, st, S, units);
 	MAP_HIP_TRY(hipGetLastError());
 	size_t tmp_bytes = 0;
-	(void) rocprim::exclusive_scan(nullptr, tmp_bytes, m->d_sam_len.p, m->d_sam_off.p, 0u, (size_t) units + 1, rocprim::plus<uint32_t>(), m->st);
-	MAP_OOM_TRY(m->d_scan_tmp.reserve(tmp_bytes + 16), "out of device memory (scan)");
-	MAP_HIP_TRY(hipMemsetAsync(m->d_sam_len.p + units, 0, 4, m->st));
-	MAP_HIP_TRY(rocprim::exclusive_scan(m->d_scan_tmp.p, tmp_bytes, m->d_sam_len.p, m->d_sam_off.p, 0u, (size_t) units + 1, rocprim::plus<uint32_t>(), m->st));
+	(void) rocprim::exclusive_scan(nullptr, tmp_bytes, sc.len.p, sc.off.p, 0u, (size_t) units + 1, rocprim::plus<uint32_t>(), st);
+	MAP_OOM_TRY(sc.scan_tmp.reserve(tmp_bytes + 16), "out of device memory (scan)");
+	MAP_HIP_TRY(hipMemsetAsync(sc.len.p + units, 0, 4, st));
+	MAP_HIP_TRY(rocprim::exclusive_scan(sc.scan_tmp.p, tmp_bytes, sc.len.p, sc.off.p, 0u, (size_t) units + 1, rocprim::plus<uint32_t>(), st));
 	uint32_t total32 = 0;
 	unsigned long long total64 = 0;
-	MAP_HIP_TRY(hipMemcpyAsync(&total32, m->d_sam_off.p + units, 4, hipMemcpyDeviceToHost, m->st));
-	MAP_HIP_TRY(hipMemcpyAsync(&total64, m->d_total.p + 19, 8, hipMemcpyDeviceToHost, m->st));
-	MAP_HIP_TRY(hipStreamSynchronize(m->st));
+	MAP_HIP_TRY(hipMemcpyAsync(&total32, sc.off.p + units, 4, hipMemcpyDeviceToHost, st));
+	MAP_HIP_TRY(hipMemcpyAsync(&total64, S.counters + 3, 8, hipMemcpyDeviceToHost, st));
+	MAP_HIP_TRY(hipStreamSynchronize(st));
 	if (total64 != (unsigned long long) total32) {   // the 32-bit prefix sums have wrapped (detected directly, not through a per-record bound)
-		ngm::pipeline_set_error("ngm_mapper_map_sam: the text of this batch of %d reads is %llu bytes, beyond the 32-bit offsets of a batch: use smaller batches", n, total64);
+		ngm::pipeline_set_error("%s: the text of this batch of %d reads is %llu bytes, beyond the 32-bit offsets of a batch: use smaller batches", who, S.n, total64);
 		return -75;
 	}
 	*total = total32;
-	MAP_OOM_TRY(m->d_sam_text.reserve((size_t) *total + 16), "out of device memory (SAM text)");
-	S.out = m->d_sam_text.p;
-	stage_sam.acquire();
-	if (bam_slam) hipLaunchKernelGGL(ngm::sam_write_kernel<true>, dim3((units + 255) / 256), dim3(256), 0, m->st, S, units);
-	else hipLaunchKernelGGL(ngm::sam_write_kernel<false>, dim3((units + 255) / 256), dim3(256), 0, m->st, S, units);
+	MAP_OOM_TRY(sc.text.reserve((size_t) *total + 16), "out of device memory (SAM text)");
+	S.out = sc.text.p;
+	if (stage) stage->acquire();
+	if (bam_slam) hipLaunchKernelGGL(ngm::sam_write_kernel<true>, dim3((units + 255) / 256), dim3(256), 0, st, S, units);
+	else hipLaunchKernelGGL(ngm::sam_write_kernel<false>, dim3((units + 255) / 256), dim3(256), 0, st, S, units);
 	MAP_HIP_TRY(hipGetLastError());
 	return 0;
 }
@@ -252,7 +253,7 @@ int write_sam(MapBatch &b) {
 	hipEvent_t e0 = m->cev[0], e1 = m->cev[1];
 	MAP_HIP_TRY(hipEventRecord(e0, m->st));
 	unsigned long long total = 0;
-	if (units > 0) if (int rc = sam_text_kernels(b, S, units, stage_sam, &total)) return rc;
+	if (units > 0) if (int rc = sam_text_kernels(S, units, SamScratch{m->d_sam_len, m->d_sam_off, m->d_scan_tmp, m->d_sam_text}, m->st, &stage_sam, "ngm_mapper_map_sam", &total)) return rc;
 	MAP_HIP_TRY(hipEventRecord(e1, m->st));
 	SideAdds side{m, S, units};
 	if (int rc = side.enqueue()) return rc;
@@ -319,6 +320,120 @@ int ngm_mapper_sam_fetch(ngm_mapper *m, char *out, size_t out_cap) {
 	}
 	if (m->sam_text_bytes) MAP_HIP_TRY(hipMemcpy(out, m->d_sam_text.p, (size_t) m->sam_text_bytes, hipMemcpyDeviceToHost));
 	return 0;
+}
+
+// test hook: the record writers over constructed hits.  Everything the kernels index with is checked here first; then the uploads and
+// sam_text_kernels, the launch sequence of write_sam.
+long long ngm_debug_sam_records(int device, const ngm_sam_options *opt, int hard_clip, int silent_clip, int variant, int alt_scoring, int n, int q,
+		const char *reads, const char *quals, const char *names, size_t names_bytes, const ngm_sam_read *meta, const ngm_hit *hits, const char *const *cigars,
+		const char *const *mds, const uint16_t *polya, int n_contigs, const char *const *contig_names, const uint64_t *contig_lens, const ngm_ref *ref,
+		char *out, size_t out_cap, unsigned long long counters[7]) {
+	const char *fn = "ngm_debug_sam_records";
+	if (!opt || n < 0 || q < 1 || q > 0x7FFF || n_contigs < 0 || !counters || (out_cap && !out) || (n && (!reads || !quals || !meta || !hits || !cigars || !mds)) || (names_bytes && !names) ||
+			(n_contigs && (!contig_names || !contig_lens)) || (opt->paired && (n & 1))) { ngm::pipeline_set_error("%s: bad arguments", fn); return -22; }
+	const std::string rg = opt->rg_id ? opt->rg_id : "";
+	std::string cnames, str;
+	std::vector<uint32_t> cname_off((size_t) n_contigs + 1, 0);
+	std::vector<uint64_t> cstart((size_t) n_contigs + 1, 0);
+	for (int c = 0; c < n_contigs; ++c) {
+		if (!contig_names[c]) { ngm::pipeline_set_error("%s: contig %d has no name", fn, c); return -22; }
+		cname_off[c] = (uint32_t) cnames.size(); cnames += contig_names[c];
+	}
+	cname_off[n_contigs] = (uint32_t) cnames.size();
+	if (opt->slam_seq) {   // the tags read the packed genome: the reference's contigs are the table's
+		if (!ref || ref->device != device || !ref->d_genome || (int) ref->contigs.size() != n_contigs) { ngm::pipeline_set_error("%s: slam_seq needs a reference on device %d whose contigs are the table's", fn, device); return -22; }
+		for (int c = 0; c < n_contigs; ++c) {
+			const NgmContig &rc = ref->contigs[c];
+			if (rc.name != contig_names[c] || rc.len != contig_lens[c] || rc.start + rc.len > ref->genome_words * 8ull) { ngm::pipeline_set_error("%s: contig %d differs from the reference's", fn, c); return -22; }
+			cstart[c] = rc.start;
+		}
+	}
+	std::vector<ngm::SamRef> refs((size_t) n);
+	for (int i = 0; i < n; ++i) {
+		const ngm_sam_read &mt = meta[i];
+		const ngm_hit &h = hits[i];
+		if ((uint64_t) mt.name_off + mt.name_len > names_bytes) { ngm::pipeline_set_error("%s: read %d: its name ends beyond names_bytes", fn, i); return -22; }
+		if (mt.name_len > 254) { ngm::pipeline_set_error("%s: read %d: a name of %d bytes (BAM's l_read_name is one byte)", fn, i, (int) mt.name_len); return -22; }
+		const char *cg = cigars[i] ? cigars[i] : "", *md = mds[i] ? mds[i] : "";
+		const size_t cl = strlen(cg), ml = strlen(md);
+		if (cl > 0xFFFF || ml > 0xFFFF || str.size() + cl + ml > 0xFFFFFFFFull) { ngm::pipeline_set_error("%s: read %d: CIGAR or MD too long", fn, i); return -22; }
+		refs[i] = ngm::SamRef{(uint32_t) str.size(), (uint32_t) (str.size() + cl), (uint16_t) cl, (uint16_t) ml};
+		str.append(cg, cl); str.append(md, ml);
+		if (!h.mapped) continue;   // (no writer looks at the rest of a hit without `mapped`)
+		const int L = (int) strnlen(reads + (size_t) i * q, (size_t) q);
+		if (h.contig < 0 || h.contig >= n_contigs) { ngm::pipeline_set_error("%s: read %d: contig %d is not in the table", fn, i, h.contig); return -22; }
+		if (h.qstart < 0 || h.qend < 0 || (long long) h.qstart + h.qend > L) { ngm::pipeline_set_error("%s: read %d: clipped %d + %d of %d bases", fn, i, h.qstart, h.qend, L); return -22; }
+		unsigned long long num = 0, read_used = 0, span = 0;
+		bool digits = false;
+		for (size_t c = 0; c < cl; ++c) {
+			const char ch = cg[c];
+			if (ch >= '0' && ch <= '9') { num = num * 10ull + (unsigned long long) (ch - '0'); digits = true; if (num >= (1ull << 28)) break; continue; }
+			if (!digits || !strchr("MIDNSHP=X", ch)) { num = 1ull << 28; break; }
+			if (ch == 'M' || ch == 'I') read_used += num;
+			if (ch == 'M' || ch == 'D' || ch == 'N' || ch == '=' || ch == 'X') span += num;
+			num = 0; digits = false;
+		}
+		if (num >= (1ull << 28) || digits) { ngm::pipeline_set_error("%s: read %d: malformed CIGAR", fn, i); return -22; }
+		if (read_used > (unsigned long long) (L - h.qstart)) { ngm::pipeline_set_error("%s: read %d: its CIGAR consumes %llu bases, %d follow the clipped start", fn, i, read_used, L - h.qstart); return -22; }
+		if (opt->slam_seq && (h.pos > contig_lens[h.contig] || span > contig_lens[h.contig] - h.pos)) { ngm::pipeline_set_error("%s: read %d: the alignment ends beyond its contig", fn, i); return -22; }
+	}
+	const int units = opt->paired ? n / 2 : n;
+	const size_t rows = std::max<size_t>((size_t) n * (size_t) q, 1), nn = std::max<size_t>((size_t) n, 1);
+	ngm::DevGuard g(device);
+	ngm::DevBuf<uint8_t> d_reads, d_quals, d_scan_tmp;
+	ngm::DevBuf<char> d_names, d_str, d_cnames, d_rg, d_text;
+	ngm::DevBuf<ngm::SamMeta> d_meta;
+	ngm::DevBuf<ngm_hit> d_hits;
+	ngm::DevBuf<ngm::SamRef> d_refs;
+	ngm::DevBuf<uint32_t> d_coff, d_len, d_off;
+	ngm::DevBuf<uint64_t> d_cstart;
+	ngm::DevBuf<uint16_t> d_polya;
+	ngm::DevBuf<unsigned long long> d_ctr;
+	unsigned long long total = 0;
+	auto run = [&]() -> int {
+		if (d_reads.reserve(rows) || d_quals.reserve(rows) || d_names.reserve(names_bytes + 16) || d_str.reserve(str.size() + 16) || d_cnames.reserve(cnames.size() + 16) || d_rg.reserve(rg.size() + 16) ||
+				d_meta.reserve(nn) || d_hits.reserve(nn) || d_refs.reserve(nn) || d_coff.reserve(cname_off.size()) || d_cstart.reserve(cstart.size()) || d_polya.reserve(nn) ||
+				d_len.reserve((size_t) units + 1) || d_off.reserve((size_t) units + 1) || d_ctr.reserve(8)) { ngm::pipeline_set_error("out of device memory (%s)", fn); return -12; }
+		if (n) {
+			MAP_HIP_TRY(hipMemcpy(d_reads.p, reads, (size_t) n * q, hipMemcpyHostToDevice));
+			MAP_HIP_TRY(hipMemcpy(d_quals.p, quals, (size_t) n * q, hipMemcpyHostToDevice));
+			MAP_HIP_TRY(hipMemcpy(d_meta.p, meta, (size_t) n * sizeof(ngm::SamMeta), hipMemcpyHostToDevice));
+			MAP_HIP_TRY(hipMemcpy(d_hits.p, hits, (size_t) n * sizeof(ngm_hit), hipMemcpyHostToDevice));
+			MAP_HIP_TRY(hipMemcpy(d_refs.p, refs.data(), (size_t) n * sizeof(ngm::SamRef), hipMemcpyHostToDevice));
+			if (polya) MAP_HIP_TRY(hipMemcpy(d_polya.p, polya, (size_t) n * 2, hipMemcpyHostToDevice));
+		}
+		if (names_bytes) MAP_HIP_TRY(hipMemcpy(d_names.p, names, names_bytes, hipMemcpyHostToDevice));
+		if (!str.empty()) MAP_HIP_TRY(hipMemcpy(d_str.p, str.data(), str.size(), hipMemcpyHostToDevice));
+		if (!cnames.empty()) MAP_HIP_TRY(hipMemcpy(d_cnames.p, cnames.data(), cnames.size(), hipMemcpyHostToDevice));
+		if (!rg.empty()) MAP_HIP_TRY(hipMemcpy(d_rg.p, rg.data(), rg.size(), hipMemcpyHostToDevice));
+		MAP_HIP_TRY(hipMemcpy(d_coff.p, cname_off.data(), cname_off.size() * 4, hipMemcpyHostToDevice));
+		MAP_HIP_TRY(hipMemcpy(d_cstart.p, cstart.data(), cstart.size() * 8, hipMemcpyHostToDevice));
+		MAP_HIP_TRY(hipMemset(d_ctr.p, 0, 64));
+		MAP_HIP_TRY(hipDeviceSynchronize());
+		ngm::SamArgs S{};   // as sam_args fills it from a mapper
+		S.n = n; S.q = q; S.paired = opt->paired ? 1 : 0;
+		S.unit_len_bound = (uint32_t) ((opt->paired ? 2 : 1) * (2 * q + 1024));
+		S.reads = d_reads.p; S.quals = d_quals.p; S.names = d_names.p; S.meta = d_meta.p; S.hits = d_hits.p; S.refs = d_refs.p;
+		S.str = d_str.p; S.contig_names = d_cnames.p; S.contig_name_off = d_coff.p;
+		S.min_insert = opt->min_insert_size; S.max_insert = opt->max_insert_size > 0 ? opt->max_insert_size : 2147483647;
+		S.min_mq = opt->min_mq; S.no_unal = opt->no_unal; S.hard_clip = hard_clip; S.silent_clip = silent_clip;
+		S.min_identity = opt->min_identity; S.min_residues = opt->min_residues;
+		S.rg = rg.empty() ? nullptr : d_rg.p; S.rg_len = (int) rg.size(); S.bs_mapping = opt->bs_mapping;
+		S.slam_seq = opt->slam_seq; S.variant_cpu = variant == NGM_VARIANT_OCL_CPU ? 1 : 0; S.alt_scoring = alt_scoring ? 1 : 0;
+		S.genome = opt->slam_seq ? ref->d_genome : nullptr; S.contig_start = d_cstart.p;
+		S.unit_len = d_len.p; S.unit_off = d_off.p; S.counters = d_ctr.p;
+		S.bam = opt->bam ? 1 : 0;
+		S.polya = polya ? d_polya.p : nullptr;
+		if (units > 0) if (int rc = ngm::sam_text_kernels(S, units, ngm::SamScratch{d_len, d_off, d_scan_tmp, d_text}, 0, nullptr, fn, &total)) return rc;
+		MAP_HIP_TRY(hipDeviceSynchronize());
+		MAP_HIP_TRY(hipMemcpy(counters, d_ctr.p, 56, hipMemcpyDeviceToHost));
+		if (total && total <= out_cap) MAP_HIP_TRY(hipMemcpy(out, d_text.p, (size_t) total, hipMemcpyDeviceToHost));
+		return 0;
+	};
+	const int rc = run();
+	d_reads.release(); d_quals.release(); d_scan_tmp.release(); d_names.release(); d_str.release(); d_cnames.release(); d_rg.release(); d_text.release(); d_meta.release();
+	d_hits.release(); d_refs.release(); d_coff.release(); d_len.release(); d_off.release(); d_cstart.release(); d_polya.release(); d_ctr.release();
+	return rc < 0 ? (long long) rc : (long long) total;
 }
 
 }  // extern "C"

@@ -116,6 +116,9 @@ def _lib():
         lib.ngm_mapper_argos_counters.argtypes = [C.c_void_p, C.c_void_p]
         lib.ngm_mapper_argos_path_counters.argtypes = [C.c_void_p, C.c_void_p]
         lib.ngm_debug_argos_order.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        lib.ngm_debug_sam_records.restype = C.c_longlong
+        lib.ngm_debug_sam_records.argtypes = ([C.c_int, C.POINTER(SamOptions)] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 5 +
+                                              [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p])
         lib.ngm_bgzf_create.restype = C.c_void_p
         lib.ngm_bgzf_create.argtypes = [C.c_int]
         lib.ngm_bgzf_destroy.argtypes = [C.c_void_p]
@@ -553,6 +556,44 @@ class SnpCaller(_LineStream):
         d = dict(zip(("alignments", "alt_bases", "calls", "text_bytes", "covered_bases"), (int(x) for x in counts)))
         d.update(zip(("add_ms", "scan_ms", "flag_ms", "text_ms"), (float(x) for x in ms)))
         return d
+
+
+SAM_READ_DTYPE = np.dtype([("name_off", np.uint32), ("name_len", np.uint16), ("qual_len", np.uint16)])   # ngm_sam_read
+
+
+def debug_sam_records(options, reads, quals, names, meta, hits, cigars, mds, contig_names, contig_lens, polya=None, reference=None, hard_clip=0, silent_clip=0,
+                      variant=0, alt_scoring=0, device=0):
+    """ngm_debug_sam_records: the GPU record writers over constructed results.  options: a SamOptions; reads, quals: n x q uint8; names: the
+    name bytes; meta: SAM_READ_DTYPE[n]; hits: HIT_DTYPE[n]; cigars, mds: n byte strings; the contig table; polya: uint16[n] or None; reference:
+    a Reference (needed with slam_seq).  Returns (the text or the uncompressed BAM records, the seven counters); raises NgmHipError, whose
+    `code` is the entry's return value (-22: an input the kernels would index out of bounds with; nothing was launched)."""
+    lib = _lib()
+    reads, quals = np.ascontiguousarray(reads, dtype=np.uint8), np.ascontiguousarray(quals, dtype=np.uint8)
+    n, q = reads.shape
+    meta, hits = np.ascontiguousarray(meta, dtype=SAM_READ_DTYPE), np.ascontiguousarray(hits, dtype=HIT_DTYPE)
+    if quals.shape != (n, q) or len(meta) != n or len(hits) != n or len(cigars) != n or len(mds) != n or (polya is not None and len(polya) != n):
+        raise ValueError("one quality row, name, hit, CIGAR, MD and poly-A count per read")
+    names = bytes(names)
+    cg, md = (C.c_char_p * max(n, 1))(*cigars), (C.c_char_p * max(n, 1))(*mds)
+    nc = len(contig_names)
+    cn = (C.c_char_p * max(nc, 1))(*[s.encode() if isinstance(s, str) else s for s in contig_names])
+    cl = (C.c_uint64 * max(nc, 1))(*contig_lens)
+    pa = None if polya is None else np.ascontiguousarray(polya, dtype=np.uint16)
+    counters = np.zeros(7, np.uint64)
+    cap = max(1 << 16, n * (2 * q + 512))
+    for _ in range(2):
+        out = np.zeros(cap, np.uint8)
+        total = lib.ngm_debug_sam_records(device, C.byref(options), int(hard_clip), int(silent_clip), int(variant), int(alt_scoring), n, q, reads.ctypes.data, quals.ctypes.data,
+                                          names, len(names), meta.ctypes.data, hits.ctypes.data, cg, md, None if pa is None else pa.ctypes.data, nc, cn, cl,
+                                          None if reference is None else reference.h, out.ctypes.data, cap, counters.ctypes.data)
+        if total < 0:
+            e = _err()
+            e.code = int(total)
+            raise e
+        if total <= cap:
+            return out[:total].tobytes(), [int(x) for x in counters]
+        cap = int(total)
+    raise NgmHipError("ngm_debug_sam_records: the text grew between two calls")
 
 
 class Reference:

@@ -2,9 +2,10 @@
 //   bam <out.bam>        a small BAM file written with csrc/bam_writer.h (header, dictionary, records in several BGZF chunks, EOF)
 //   pool                 ngm::ThreadPool::parallel_for: sums, concurrent callers, nested use
 //   format <spec> [out.bam]   the host formatter of `ngm-hip` (csrc/cli_format.h) over the records a text file describes:
-//                        opt <key> <value> | contig <name> <bases> | rec <name> <row or -> <qualities or *> <seq_len> <unit> <polya>, followed by
-//                        topn lines: hit <mapped> <contig> <pos> <reverse> <mapq> <score> <identity> <nm> <qstart> <qend> <n_candidates> <n_best>
-//                        <max_votes> <pair_flags> <cigar> <md>.  Prints the SAM text (with out.bam: writes the records as a BAM file instead), what the
+//                        opt <key> <value> (q: bytes per read row, before the records) | contig <name> <bases> |
+//                        rec <name> <row or -> <qualities or *> <seq_len> <unit> <polya> [<qual_len>: the length of the quality string as the parser
+//                        holds it, where the row holds less of it], followed by topn lines: hit <mapped> <contig> <pos> <reverse> <mapq> <score>
+//                        <identity> <nm> <qstart> <qend> <n_candidates> <n_best> <max_votes> <pair_flags> <cigar or -> <md or ->.  Prints the SAM text (with out.bam: writes the records as a BAM file instead), what the
 //                        --coverage / --snp callbacks got ("#cov", "#snp"), and "#counts total mapped written pairs broken insert_sum"
 #include <atomic>
 #include <cstdio>
@@ -92,7 +93,7 @@ static int format_records(const char *spec, const char *bam_out) {
 	HostFormatter f;
 	f.q = 16;
 	std::vector<std::string> contig_seq;
-	struct Text { std::string name, row, qual; };
+	struct Text { std::string name, row, qual; long qual_len; };
 	std::vector<Text> text;
 	std::vector<ngm::cli::Rec> recs;
 	std::vector<ngm_hit> hits;
@@ -111,6 +112,7 @@ static int format_records(const char *spec, const char *bam_out) {
 			else if (k == "clip") f.clip = std::stoi(v); else if (k == "no_unal") f.no_unal = std::stoi(v); else if (k == "bs_mapping") f.bs_mapping = std::stoi(v);
 			else if (k == "slam_seq") f.slam_seq = std::stoi(v); else if (k == "variant") f.variant = std::stoi(v); else if (k == "xa_tag") f.xa_tag = std::stoi(v) != 0;
 			else if (k == "rg") f.set_read_group(v); else if (k == "min_insert") f.min_insert = std::stoi(v); else if (k == "max_insert") f.max_insert = std::stoi(v);
+			else if (k == "q") { f.q = std::stoi(v); if (f.q < 1 || !text.empty()) { fprintf(stderr, "bad q\n"); return 65; } }
 			else if (k == "coverage") cov = std::stoi(v) != 0; else if (k == "snp") snp = std::stoi(v) != 0;
 			else { fprintf(stderr, "unknown option %s\n", k.c_str()); return 65; }
 		} else if (kind == "contig") {
@@ -121,8 +123,11 @@ static int format_records(const char *spec, const char *bam_out) {
 			Text t;
 			unsigned seq_len = 0, unit = 0, polya = 0;
 			ls >> t.name >> t.row >> t.qual >> seq_len >> unit >> polya;
+			if (!ls) { fprintf(stderr, "bad rec line: %s\n", line.c_str()); return 65; }
 			if (t.row == "-") t.row.clear();
 			if (t.qual == "*") t.qual.clear();
+			if (!(ls >> t.qual_len)) t.qual_len = (long) t.qual.size();
+			if (t.qual_len < 0 || t.qual_len > 0x7FFF || (size_t) std::min<long>(t.qual_len, f.q - 1) > t.qual.size()) { fprintf(stderr, "bad quality length: %s\n", line.c_str()); return 65; }
 			t.row.resize((size_t) f.q, '\0');
 			text.push_back(t);
 			recs.push_back(ngm::cli::Rec{nullptr, nullptr, nullptr, 0, seq_len, 0, (uint8_t) unit, (uint16_t) polya});
@@ -131,6 +136,8 @@ static int format_records(const char *spec, const char *bam_out) {
 			std::string c, m;
 			ls >> h.mapped >> h.contig >> h.pos >> h.reverse >> h.mapq >> h.score >> h.identity >> h.nm >> h.qstart >> h.qend >> h.n_candidates >> h.n_best >> h.max_votes >> h.pair_flags >> c >> m;
 			if (!ls) { fprintf(stderr, "bad hit line: %s\n", line.c_str()); return 65; }
+			if (c == "-") c.clear();
+			if (m == "-") m.clear();
 			hits.push_back(h); cig.push_back(c); md.push_back(m);
 		} else { fprintf(stderr, "unknown line: %s\n", line.c_str()); return 65; }
 	}
@@ -142,7 +149,7 @@ static int format_records(const char *spec, const char *bam_out) {
 	for (size_t i = 0; i < n; ++i) {
 		memcpy(&rows[i * (size_t) f.q], text[i].row.data(), (size_t) f.q);
 		recs[i].name = text[i].name.data(); recs[i].name_len = (uint32_t) text[i].name.size();
-		recs[i].qual = text[i].qual.data(); recs[i].qual_len = (uint32_t) text[i].qual.size();
+		recs[i].qual = text[i].qual.data(); recs[i].qual_len = (uint32_t) text[i].qual_len;
 	}
 	for (size_t e = 0; e < hits.size(); ++e) {
 		if (cig[e].size() >= f.stride || md[e].size() >= f.stride) return 65;
