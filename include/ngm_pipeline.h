@@ -466,6 +466,54 @@ int ngm_count_stats(const ngm_count *c, uint64_t counts[5], float ms[2]);
  * ngm_count_add. */
 int ngm_mapper_set_count(ngm_mapper *m, ngm_count *c);
 
+/* ---- `ngm-hip --bs-mapping --methyl` (csrc/methyl.cpp): the per-cytosine methylation calls of a bisulfite run as Bismark's cytosine
+ * report ("--methyl", holds the definition).  One pair of uint32 (meth, unmeth) per base of the reference lives in the
+ * device's memory for the whole run: 8 bytes per base, about 25 GB for a genome of GRCh38's size.  The records that count are
+ * ngm_coverage's.  A record is top or bottom (bottom: the first character of its ZS:Z tag is '-').  An M, = or X column inside the contig
+ * counts when the record has no quality text or the column's Phred quality is at least min_qual: over a reference C (case folded) a top
+ * record's C adds to meth and its T to unmeth; over a reference G a bottom record's G adds to meth and its A to unmeth.  The file has no
+ * header and one line per site (a reference C, strand '+', or G, strand '-') with meth + unmeth >= max(1, min_depth) whose context is
+ * selected, contigs in the order given, positions ascending: name \t pos (1-based) \t strand \t meth \t unmeth \t context \t C n1 n2.
+ * The sums are integers: the text depends on the set of alignments and the parameters only.  Errors: < 0 with ngm_pipeline_last_error();
+ * the object stays destroyable after every error. */
+typedef struct ngm_methyl ngm_methyl;
+typedef struct ngm_methyl_params {
+	int device;
+	int n_ref;
+	const uint32_t *ref_len;
+	const char *const *ref_name;
+	const char *const *ref_seq;  /* one ASCII string of ref_len[c] letters per contig (ngm_methyl_create only) */
+	int min_qual;                /* Q, 0..93 (MethylDackel's -p: 5) */
+	int min_depth;               /* N, 0 or more */
+	const char *context;         /* "all", "CpG", "CHG" or "CHH"; NULL: "all" */
+	size_t scan_chunk;           /* bases flagged at a time by the finish (its temporaries are 5 bytes per base of a chunk plus the chunk's
+	                                lines); 0: 2^25; at most 2^30 */
+} ngm_methyl_params;
+/* allocates and zeroes 8 bytes per base on the device and uploads the reference packed to 4 bits per base; NULL with the error set when
+ * that fails */
+ngm_methyl *ngm_methyl_create(const ngm_methyl_params *p);
+/* the same over the contigs of r, on r's device, reading r's resident packed genome instead of a copy (n_ref, ref_len, ref_name, ref_seq
+ * and device of p are not read); r must outlive the object */
+ngm_methyl *ngm_methyl_create_for_ref(const ngm_ref *r, const ngm_methyl_params *p);
+void ngm_methyl_destroy(ngm_methyl *c);
+/* n alignments as ngm_snp_add takes them, and bottom[i] != 0 for a bottom record.  Thread-safe.  Validated on the host as ngm_snp_add
+ * validates: -22 with "ngm_methyl_add: alignment <i>: ..." names the first one refused, and nothing of the call is added.  -22 after
+ * ngm_methyl_finish. */
+int ngm_methyl_add(ngm_methyl *c, const int32_t *ref_id, const int32_t *pos0, const uint32_t *cigar_off /* [n + 1] */, const char *cigar_text,
+                   const uint32_t *seq_off /* [n + 1] */, const char *seq_text, const char *qual_text, const uint8_t *bottom /* [n] */, size_t n);
+/* no add after this; waits for the adds in flight and sets the finish up */
+int ngm_methyl_finish(ngm_methyl *c);
+/* the next lines of the file, made chunk by chunk as they are asked for: whole lines only; 0 at the end; > out_cap: nothing copied, call
+ * again with that much */
+long long ngm_methyl_next(ngm_methyl *c, void *out, size_t out_cap);
+/* counts: alignments added, and of the chunks made so far the lines written and meth, unmeth summed over all sites of context CG, then
+ * CHG, then CHH, whatever the selection (complete once ngm_methyl_next has returned 0); ms: kernel ms of add / flags / select / text */
+int ngm_methyl_stats(const ngm_methyl *c, uint64_t counts[8], float ms[4]);
+/* every batch ngm_mapper_map_sam* finishes adds the records ngm_mapper_set_coverage would add to c, in place from the batch's arrays in
+ * device memory, on the mapper's stream -- a record is bottom when its hit is reverse, the other way round for the second mate of a pair;
+ * NULL detaches.  When c lives on another device, the batch's arrays are downloaded and go through ngm_methyl_add. */
+int ngm_mapper_set_methyl(ngm_mapper *m, ngm_methyl *c);
+
 /* page-locked host memory for read batches (the H2D copy then runs at PCIe rate without a staging copy) */
 void *ngm_host_alloc(size_t bytes);
 void ngm_host_free(void *p);

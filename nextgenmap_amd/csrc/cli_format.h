@@ -47,10 +47,11 @@ inline void put_identity(std::string &s, float identity) {
 	s.append(b, k);
 }
 
-// what one format_range call hands to --coverage, --snp and --count: its records without 0x100, as the arrays ngm_coverage_add / ngm_snp_add /
-// ngm_count_add take (rev: flag bit 0x10 of each record)
+// what one format_range call hands to --coverage, --snp, --count and --methyl: its records without 0x100, as the arrays ngm_coverage_add /
+// ngm_snp_add / ngm_count_add / ngm_methyl_add take (rev: flag bit 0x10 of each record; MethylAcc's bottom: its ZS:Z tag begins with '-')
 struct CovAcc { std::vector<int32_t> ref, pos; std::vector<uint32_t> off; std::string text; };
 struct SnpAcc { std::vector<int32_t> ref, pos; std::vector<uint32_t> off, seq_off; std::vector<uint8_t> rev; std::string text, seq, qual; };
+struct MethylAcc : SnpAcc { std::vector<uint8_t> bottom; };
 
 struct HostFormatter {
 	// ---- set once per run ----
@@ -63,10 +64,11 @@ struct HostFormatter {
 	size_t stride = 0;     // bytes per CIGAR / MD row
 	int min_insert = 0, max_insert = 2147483647;
 	std::function<void(int contig, uint64_t pos, int span, uint8_t *out)> ref_classes;   // --slam-seq: the classes of `span` reference bases (ngm_ref_host_classes)
-	// --coverage / --snp / --count: set = wanted.  Called once per range that has such records (snp, count: once for those without a quality
-	// string, once for those with)
+	// --coverage / --snp / --count / --methyl: set = wanted.  Called once per range that has such records (snp, count, methyl: once for those
+	// without a quality string, once for those with)
 	std::function<void(const CovAcc &)> add_coverage;
 	std::function<void(const SnpAcc &, bool has_qual)> add_snp, add_count;
+	std::function<void(const MethylAcc &, bool has_qual)> add_methyl;
 
 	void set_read_group(const std::string &id) {
 		rg_id = id;
@@ -80,7 +82,7 @@ struct HostFormatter {
 	struct Counts { size_t total = 0, mapped = 0, written = 0; uint64_t pair[3] = {0, 0, 0}; };
 	struct View { const Rec *r; const ngm_hit *h; const char *row; int L; const char *cigar, *md; };
 	struct BamMate { int ref; long long pos0; long long tlen; };  // what BAMWriter::DoWritePair passes on (0-based, -1 = none; its own TLEN rule)
-	struct Side { CovAcc cov; SnpAcc snp[2]; };   // snp[0]: records without a quality string, [1]: with one
+	struct Side { CovAcc cov; MethylAcc snp[2]; };   // snp[0]: records without a quality string, [1]: with one
 	struct SlamTags { int tc = 0; int rates[25] = {0}; std::string mp; };
 
 	View view(const Input &in, int i, int t = 0) const {
@@ -173,10 +175,11 @@ struct HostFormatter {
 			a.ref.push_back(h.contig); a.pos.push_back((int32_t) h.pos); a.off.push_back((uint32_t) a.text.size());
 			a.text += v.cigar;
 		}
-		if (side && (add_snp || add_count) && !(flags & 0x100)) {   // the sequence and the qualities as the record prints them
-			SnpAcc &a = side->snp[noq ? 0 : 1];
+		if (side && (add_snp || add_count || add_methyl) && !(flags & 0x100)) {   // the sequence and the qualities as the record prints them
+			MethylAcc &a = side->snp[noq ? 0 : 1];
 			a.ref.push_back(h.contig); a.pos.push_back((int32_t) h.pos); a.off.push_back((uint32_t) a.text.size()); a.seq_off.push_back((uint32_t) a.seq.size());
 			a.rev.push_back(h.reverse ? 1 : 0);
+			if (add_methyl) a.bottom.push_back(zs_tag(h, flags)[0] == '-' ? 1 : 0);
 			a.text += v.cigar;
 			a.seq.resize(a.seq.size() + sl);
 			oriented_seq(v, s0, sl, &a.seq[a.seq.size() - sl]);
@@ -355,18 +358,19 @@ struct HostFormatter {
 		}
 	}
 	// records [lo, hi) of a batch (paired: lo and hi even) -> SAM text or BAM records appended to s, the counters added to c; the range's
-	// records without 0x100 go to --coverage, --snp and --count in one call each when the range is done
+	// records without 0x100 go to --coverage, --snp, --count and --methyl in one call each when the range is done
 	void format_range(const Input &in, int lo, int hi, std::string &s, Counts &c) const {
 		Side side;
-		Side *sp = (add_coverage || add_snp || add_count) ? &side : nullptr;
+		Side *sp = (add_coverage || add_snp || add_count || add_methyl) ? &side : nullptr;
 		s.reserve((size_t) (hi - lo) * (size_t) (2 * q + 160));
 		if (paired) format_pairs(in, lo, hi, s, c, sp); else format_single_end(in, lo, hi, s, c, sp);
-		for (int k = 0; (add_snp || add_count) && k < 2; ++k) {
-			SnpAcc &a = side.snp[k];
+		for (int k = 0; (add_snp || add_count || add_methyl) && k < 2; ++k) {
+			MethylAcc &a = side.snp[k];
 			if (a.ref.empty()) continue;
 			a.off.push_back((uint32_t) a.text.size()); a.seq_off.push_back((uint32_t) a.seq.size());
 			if (add_snp) add_snp(a, k == 1);
 			if (add_count) add_count(a, k == 1);
+			if (add_methyl) add_methyl(a, k == 1);
 		}
 		if (add_coverage && !side.cov.ref.empty()) {
 			side.cov.off.push_back((uint32_t) side.cov.text.size());

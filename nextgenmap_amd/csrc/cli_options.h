@@ -33,6 +33,9 @@ struct Opts {
 	double snp_min_frac = 0.8;
 	std::string count, count_out;   // --count FILE, --count-out FILE (ours): T>C conversion counts per region of the BED file, made on the GPU (csrc/count.cpp)
 	long count_min_qual = 27;       // --count-min-qual (slamdunk count's -q)
+	std::string methyl, methyl_context = "all";   // --methyl FILE, --methyl-context (ours, with --bs-mapping): per-cytosine methylation calls as Bismark's cytosine report, made on the GPU (csrc/methyl.cpp)
+	long methyl_min_qual = 5, methyl_min_depth = 1;   // --methyl-min-qual (MethylDackel's -p), --methyl-min-depth
+	bool methyl_opts = false;       // one of the three --methyl-* options was given
 	ngm::trim::Options trim;   // -5/--trim5, --max-polya (Options.h:103-104)
 	float argos_min = 0.f;   // --argos-min-score (Default(ARGOS_MINSCORE, 0), Config.cpp:505)
 	int bs_mapping = 0, bs_cutoff = 6, match_tt = -1, match_tc = -1, match_set = 0, mismatch_set = 0, slam_seq = 0;
@@ -55,7 +58,7 @@ inline Opts parse(int argc, char **argv) {
 	Opts o;
 	for (int i = 1; i < argc; ++i) { if (i > 1) o.cmdline += " "; o.cmdline += argv[i]; }  // Config.cpp:565-574
 	enum { KSKIP = 1000, HARD, SILENT, KMIN, MB, MMP, GRP, GFP, MAXCMRS, NOUNAL, NOPROG, MAXRL, BINSZ, MAXKF, VFAST, FAST, SENS, VSENS, DEVICE,
-		SKIPSAVE, BATCH, VARIANT, SHARD, SHARDOUT, KEEPSHARDS, BAMOUT, WORKERS, SERIAL, AFFINE, GEP, PEDELIM, STRATA, BSMAP, BSCUT, MBTT, MBTC, SLAM, FASTPAIR, BROKENPAIRS, REFSCOREBUF, STATSFD, MAXPOLYA, RG0, RG_LAST = RG0 + 11, ARGOS, ARGOSMIN, VCF, KEEPTAGS, PARSEALL, SORTOUT, MARKDUP, COVERAGE, SNP, SNPCOV, SNPFRAC, SNPQUAL, COUNT, COUNTOUT, COUNTQUAL, UNSUPPORTED };
+		SKIPSAVE, BATCH, VARIANT, SHARD, SHARDOUT, KEEPSHARDS, BAMOUT, WORKERS, SERIAL, AFFINE, GEP, PEDELIM, STRATA, BSMAP, BSCUT, MBTT, MBTC, SLAM, FASTPAIR, BROKENPAIRS, REFSCOREBUF, STATSFD, MAXPOLYA, RG0, RG_LAST = RG0 + 11, ARGOS, ARGOSMIN, VCF, KEEPTAGS, PARSEALL, SORTOUT, MARKDUP, COVERAGE, SNP, SNPCOV, SNPFRAC, SNPQUAL, COUNT, COUNTOUT, COUNTQUAL, METHYL, METHYLCTX, METHYLQUAL, METHYLDEPTH, UNSUPPORTED };
 	static const option lo[] = {
 		{"ref", required_argument, 0, 'r'}, {"qry", required_argument, 0, 'q'}, {"output", required_argument, 0, 'o'},
 		{"cpu-threads", required_argument, 0, 't'}, {"gpu", no_argument, 0, 'g'}, {"sensitivity", required_argument, 0, 's'},
@@ -84,6 +87,7 @@ inline Opts parse(int argc, char **argv) {
 		{"keep-tags", no_argument, 0, KEEPTAGS}, {"parse-all", no_argument, 0, PARSEALL}, {"sort", no_argument, 0, SORTOUT}, {"markdup", no_argument, 0, MARKDUP}, {"coverage", required_argument, 0, COVERAGE},
 		{"snp", required_argument, 0, SNP}, {"snp-min-cov", required_argument, 0, SNPCOV}, {"snp-min-frac", required_argument, 0, SNPFRAC}, {"snp-min-qual", required_argument, 0, SNPQUAL},
 		{"count", required_argument, 0, COUNT}, {"count-out", required_argument, 0, COUNTOUT}, {"count-min-qual", required_argument, 0, COUNTQUAL},
+		{"methyl", required_argument, 0, METHYL}, {"methyl-context", required_argument, 0, METHYLCTX}, {"methyl-min-qual", required_argument, 0, METHYLQUAL}, {"methyl-min-depth", required_argument, 0, METHYLDEPTH},
 		{"trim5", required_argument, 0, '5'}, {"max-polya", required_argument, 0, MAXPOLYA}, {"config", required_argument, 0, UNSUPPORTED},
 		{0, 0, 0, 0}};
 	int c, idx = 0;
@@ -178,6 +182,13 @@ inline Opts parse(int argc, char **argv) {
 		case SNPQUAL: { char *e = nullptr; o.snp_min_qual = strtol(optarg, &e, 10); if (e == optarg || *e || o.snp_min_qual < 0 || o.snp_min_qual > 93) die("--snp-min-qual expects a Phred quality in 0..93"); break; }
 		case COUNT: o.count = optarg; if (o.count.empty()) die("--count expects a BED file name"); break;
 		case COUNTOUT: o.count_out = optarg; if (o.count_out.empty()) die("--count-out expects a file name"); break;
+		case METHYL: o.methyl = optarg; if (o.methyl.empty()) die("--methyl expects a file name"); break;
+		case METHYLCTX:
+			o.methyl_context = optarg; o.methyl_opts = true;
+			if (o.methyl_context != "all" && o.methyl_context != "CpG" && o.methyl_context != "CHG" && o.methyl_context != "CHH") die("--methyl-context expects all, CpG, CHG or CHH, not " + o.methyl_context);
+			break;
+		case METHYLQUAL: { char *e = nullptr; o.methyl_opts = true; o.methyl_min_qual = strtol(optarg, &e, 10); if (e == optarg || *e || o.methyl_min_qual < 0 || o.methyl_min_qual > 93) die("--methyl-min-qual expects a Phred quality in 0..93"); break; }
+		case METHYLDEPTH: { char *e = nullptr; o.methyl_opts = true; o.methyl_min_depth = strtol(optarg, &e, 10); if (e == optarg || *e || o.methyl_min_depth < 0 || o.methyl_min_depth > 2147483647L) die("--methyl-min-depth expects a count of 0 or more"); break; }
 		case COUNTQUAL: { char *e = nullptr; o.count_min_qual = strtol(optarg, &e, 10); if (e == optarg || *e || o.count_min_qual < 0 || o.count_min_qual > 93) die("--count-min-qual expects a Phred quality in 0..93"); break; }
 		case UNSUPPORTED: die(std::string("option --") + lo[idx].name + " is not supported by the HIP backend yet");
 		default: die("unknown option (see src/config/Options.h of NextGenMap for the option set)");
@@ -209,6 +220,16 @@ inline Opts parse(int argc, char **argv) {
 		if (!o.vcf.empty()) die("--snp cannot be combined with --vcf: calling over an index built with known variants is not checked");
 		if (o.snp == o.out) die("--snp cannot be combined with -o " + o.out + ": the calls and the records need a file each");
 		if (o.snp == o.coverage) die("--snp cannot be combined with --coverage " + o.coverage + ": the calls and the depth need a file each");
+	}
+	if (!o.methyl.empty() || o.methyl_opts) {
+		// the calls are over the records of the whole run, counted in the first GPU's memory; refused before any GPU work
+		if (o.methyl.empty()) die("--methyl-context, --methyl-min-qual and --methyl-min-depth need --methyl FILE: where the report is written");
+		if (!o.bs_mapping) die("--methyl needs --bs-mapping: only a bisulfite run's records say which strand a read was converted on");
+		if (o.argos) die("--methyl cannot be combined with --argos: argos scores candidates, no alignments are made");
+		if (o.shard_n > 1) die("--methyl cannot be combined with --shard: the calls are over the whole run, not over one shard of it");
+		if (o.shard_output) die("--methyl cannot be combined with --shard-output: the calls are over the whole run, in one process");
+		if (o.methyl == o.out) die("--methyl cannot be combined with -o " + o.out + ": the report and the records need a file each");
+		if (o.methyl == o.coverage) die("--methyl cannot be combined with --coverage " + o.coverage + ": the report and the depth need a file each");
 	}
 	if (!o.count.empty() || !o.count_out.empty()) {
 		// the counts are over the records of the whole run, kept in the first GPU's memory; refused before any GPU work

@@ -796,6 +796,7 @@ int ngm_mapper_set_bam_sorter(ngm_mapper *m, ngm_bam_sort *s) { if (!m) return -
 int ngm_mapper_set_coverage(ngm_mapper *m, ngm_coverage *c) { if (!m) return -22; m->coverage = c; return 0; }
 int ngm_mapper_set_snp(ngm_mapper *m, ngm_snp *s) { if (!m) return -22; m->snp = s; return 0; }
 int ngm_mapper_set_count(ngm_mapper *m, ngm_count *c) { if (!m) return -22; m->count = c; return 0; }
+int ngm_mapper_set_methyl(ngm_mapper *m, ngm_methyl *c) { if (!m) return -22; m->methyl = c; return 0; }
 
 void *ngm_host_alloc(size_t bytes) {
 	void *p = nullptr;

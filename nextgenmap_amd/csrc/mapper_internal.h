@@ -119,7 +119,7 @@ struct ngm_mapper {
 	ngm::DevBuf<uint8_t> d_scan_tmp;
 	unsigned long long cs_kmers = 0, cs_hits = 0;
 	float cs_kernel_ms = 0.f;
-	hipEvent_t cev[8] = {};
+	hipEvent_t cev[10] = {};
 	hipEvent_t oev[4] = {};            // around the order replay's launches (its own stream)
 	float order_ms = 0.f;              // GPU time of the order replays of the last batch (ngm_mapper_last_order_replay_ms)
 	ngm::DevBuf<uint32_t> d_pair_read, d_winner, d_a_read, d_a_loc, d_a_sv;
@@ -149,6 +149,7 @@ struct ngm_mapper {
 	std::vector<uint32_t> cov_off;
 	ngm_snp *snp = nullptr;           // ngm_mapper_set_snp: the same records are added to its counters (snp_device.h)
 	ngm_count *count = nullptr;       // ngm_mapper_set_count: ... and to its conversion counters (count_device.h)
+	ngm_methyl *methyl = nullptr;     // ngm_mapper_set_methyl: ... and to its methylation counters (methyl_device.h)
 	std::vector<uint8_t> snp_rows;    // ... by way of the host when it lives on another device: the batch's read rows
 	bool sam_ready = false;
 	std::string sam_rg;

@@ -1,5 +1,5 @@
 // mapper_sam.cpp -- the write_sam stage of a map call (map_impl, mapper.cpp): the batch's records as SAM / BAM text on the GPU
-// (sam_device.h), the side outputs --coverage / --snp / --count from the same arrays, and where the text goes: the caller's buffer,
+// (sam_device.h), the side outputs --coverage / --snp / --count / --methyl from the same arrays, and where the text goes: the caller's buffer,
 // the BGZF compressor or the sorter.  With it the SAM entry points that need no map call: ngm_mapper_set_sam_options, ngm_mapper_sam_fetch.
 #define NGM_SAM_KERNELS
 #include "mapper_internal.h"
@@ -7,15 +7,16 @@
 #include "coverage_device.h"
 #include "snp_device.h"
 #include "count_device.h"
+#include "methyl_device.h"
 #include "side_output.h"
 #include <rocprim/rocprim.hpp>
 
 namespace ngm {
 namespace {
 
-// The side outputs (--coverage, --snp, --count) of a SAM batch whose object lives on another device than the mapper: cov_mask_kernel has said
-// which records count; they, the CIGAR texts and, for --snp and --count, the read rows come down and go through ngm_*_add.
-int side_outputs_away(ngm_mapper *m, bool cov_away, bool snp_away, bool count_away, int n, int q, int units, bool paired, const ngm_hit *hits, const ngm::SamRef *sam_refs,
+// The side outputs (--coverage, --snp, --count, --methyl) of a SAM batch whose object lives on another device than the mapper: cov_mask_kernel has
+// said which records count; they, the CIGAR texts and, for --snp, --count and --methyl, the read rows come down and go through ngm_*_add.
+int side_outputs_away(ngm_mapper *m, bool cov_away, bool snp_away, bool count_away, bool methyl_away, int n, int q, int units, bool paired, const ngm_hit *hits, const ngm::SamRef *sam_refs,
 		size_t str_bytes, const SamCall *sam) {
 	// the object lives on another device: which reads count and the CIGAR texts come down
 	m->cov_mask.resize((size_t) units); m->cov_text.resize(str_bytes + 1);
@@ -35,9 +36,10 @@ int side_outputs_away(ngm_mapper *m, bool cov_away, bool snp_away, bool count_aw
 		m->cov_off.push_back((uint32_t) packed.size());
 		if (int rc = ngm_coverage_add(m->coverage, m->cov_ref.data(), m->cov_pos.data(), m->cov_off.data(), packed.data(), m->cov_ref.size())) return rc;
 	}
-	if (snp_away || count_away) {
+	if (snp_away || count_away || methyl_away) {
 		// ... with the read rows; the sequences and qualities are put as the records print them (bam_mapped, sam_device.h) and the arrays
-		// go through ngm_snp_add and ngm_count_add (with the records' strands) -- the records with a quality string and those without one in
+		// go through ngm_snp_add, ngm_count_add (with the records' strands) and ngm_methyl_add (top or bottom: the strand, the other way
+		// round for a pair's second mate) -- the records with a quality string and those without one in
 		// a call each
 		m->snp_rows.resize((size_t) n * q);
 		MAP_HIP_TRY(hipMemcpy(m->snp_rows.data(), m->d_reads.p, (size_t) n * q, hipMemcpyDeviceToHost));
@@ -48,7 +50,7 @@ int side_outputs_away(ngm_mapper *m, bool cov_away, bool snp_away, bool count_aw
 		for (int with_q = 0; with_q < 2; ++with_q) {
 			std::vector<int32_t> s_ref, s_pos;
 			std::vector<uint32_t> c_off, s_off;
-			std::vector<uint8_t> s_rev;
+			std::vector<uint8_t> s_rev, s_bot;
 			std::string c_text, s_text, q_text;
 			for (int u = 0; u < units; ++u) for (int k = 0; k < per; ++k) {
 				if (!((m->cov_mask[u] >> k) & 1)) continue;
@@ -62,6 +64,7 @@ int side_outputs_away(ngm_mapper *m, bool cov_away, bool snp_away, bool count_aw
 				const int QL = std::min(qlen, L);
 				s_ref.push_back(hits[i].contig); s_pos.push_back((int32_t) hits[i].pos); c_off.push_back((uint32_t) c_text.size()); s_off.push_back((uint32_t) s_text.size());
 				s_rev.push_back(hits[i].reverse ? 1 : 0);
+				s_bot.push_back(((hits[i].reverse != 0) != (paired && k == 1)) ? 1 : 0);
 				c_text.append(m->cov_text.data() + sam_refs[i].cig_off, sam_refs[i].cig_len);
 				for (int t = 0; t < sl; ++t) {
 					if (!hits[i].reverse) { s_text.push_back((char) row[s0 + t]); if (with_q) q_text.push_back(s0 + t < QL ? (char) qrow[s0 + t] : ':'); }
@@ -76,6 +79,7 @@ int side_outputs_away(ngm_mapper *m, bool cov_away, bool snp_away, bool count_aw
 			if (s_ref.empty()) continue;
 			if (snp_away) if (int rc = ngm_snp_add(m->snp, s_ref.data(), s_pos.data(), c_off.data(), c_text.data(), s_off.data(), s_text.data(), with_q ? q_text.c_str() : nullptr, s_ref.size())) return rc;
 			if (count_away) if (int rc = ngm_count_add(m->count, s_ref.data(), s_pos.data(), c_off.data(), c_text.data(), s_off.data(), s_text.data(), with_q ? q_text.c_str() : nullptr, s_rev.data(), s_ref.size())) return rc;
+			if (methyl_away) if (int rc = ngm_methyl_add(m->methyl, s_ref.data(), s_pos.data(), c_off.data(), c_text.data(), s_off.data(), s_text.data(), with_q ? q_text.c_str() : nullptr, s_bot.data(), s_ref.size())) return rc;
 		}
 	}
 	return 0;
@@ -157,14 +161,16 @@ int sam_text_kernels(ngm::SamArgs &S, int units, const SamScratch &sc, hipStream
 	return 0;
 }
 
-// --coverage, --snp, --count: the records just written as mapped ones add to the run's counters on this device (coverage_device.h:
-// their blocks; snp_device.h: their depth blocks and their mismatching, qualifying columns; count_device.h: their eligible columns and
-// their regions' read counts), from the same arrays, before the batch's buffers are reused (behind e1: not part of the SAM stage's time)
+// --coverage, --snp, --count, --methyl: the records just written as mapped ones add to the run's counters on this device
+// (coverage_device.h: their blocks; snp_device.h: their depth blocks and their mismatching, qualifying columns; count_device.h: their
+// eligible columns and their regions' read counts; methyl_device.h: their calls over the reference's C or G), from the same arrays, before the batch's buffers are reused (behind e1: not part of the SAM stage's time)
 struct SideAdds {
 	ngm_mapper *m; const ngm::SamArgs &S; const int units;
-	ngm::side::Base *const cov_b = ngm::side::base(m->coverage), *const snp_b = ngm::side::base(m->snp), *const count_b = ngm::side::base(m->count);
+	ngm::side::Base *const cov_b = ngm::side::base(m->coverage), *const snp_b = ngm::side::base(m->snp), *const count_b = ngm::side::base(m->count),
+			*const methyl_b = ngm::side::base(m->methyl);
 	bool here(const ngm::side::Base *b) const { return b && units > 0 && ngm::side::device(b) == m->ref->device; }
-	const bool cov_away = cov_b && units > 0 && !here(cov_b), snp_away = snp_b && units > 0 && !here(snp_b), count_away = count_b && units > 0 && !here(count_b);
+	const bool cov_away = cov_b && units > 0 && !here(cov_b), snp_away = snp_b && units > 0 && !here(snp_b), count_away = count_b && units > 0 && !here(count_b),
+			methyl_away = methyl_b && units > 0 && !here(methyl_b);
 	template <typename L> int add_here(ngm::side::Base *b, hipEvent_t *ev, L launch) {   // (nothing for an object that is elsewhere)
 		if (!here(b)) return 0;
 		MAP_HIP_TRY(hipEventRecord(ev[0], m->st));
@@ -191,14 +197,20 @@ struct SideAdds {
 		if (int rc = add_here(count_b, m->cev + 6, [&] {
 			hipLaunchKernelGGL(ngm::cnt::count_add_kernel<ngm::cnt::CountBatch>, dim3((units + 255) / 256), dim3(256), 0, m->st, ngm::cnt::CountBatch{ngm::snp::SnpBatch{S, units}}, count_tab, count_to);
 		})) return rc;
-		if (cov_away || snp_away || count_away) {
+		ngm::met::Layout methyl_tab{};
+		ngm::met::Counters methyl_to{};
+		if (here(methyl_b)) if (int rc = ngm::methyl_target(m->methyl, &methyl_tab, &methyl_to)) return rc;
+		if (int rc = add_here(methyl_b, m->cev + 8, [&] {
+			hipLaunchKernelGGL(ngm::met::methyl_add_kernel<ngm::met::MethylBatch>, dim3((units + 255) / 256), dim3(256), 0, m->st, ngm::met::MethylBatch{ngm::snp::SnpBatch{S, units}}, methyl_tab, methyl_to);
+		})) return rc;
+		if (cov_away || snp_away || count_away || methyl_away) {
 			MAP_OOM_TRY(m->d_cov_mask.reserve((size_t) units), "out of device memory (coverage)");
 			hipLaunchKernelGGL(ngm::cov::cov_mask_kernel, dim3((units + 255) / 256), dim3(256), 0, m->st, S, units, m->d_cov_mask.p);
 			MAP_HIP_TRY(hipGetLastError());
 		}
 		return 0;
 	}
-	void note() { note_here(cov_b, m->cev + 2); note_here(snp_b, m->cev + 4); note_here(count_b, m->cev + 6); }
+	void note() { note_here(cov_b, m->cev + 2); note_here(snp_b, m->cev + 4); note_here(count_b, m->cev + 6); note_here(methyl_b, m->cev + 8); }
 };
 
 // the records stay in HBM: their BGZF blocks are written there too (bgzf_device.h, the compressor's own stream -- beside the next
@@ -266,8 +278,8 @@ int write_sam(MapBatch &b) {
 	MAP_HIP_TRY(hipStreamSynchronize(m->st));
 	sam->text_bytes = (long long) total;
 	side.note();
-	if (side.cov_away || side.snp_away || side.count_away)
-		if (int rc = side_outputs_away(m, side.cov_away, side.snp_away, side.count_away, n, q, units, paired, hits, sam_refs, (size_t) b.str_base + b.extra.size(), sam)) return rc;
+	if (side.cov_away || side.snp_away || side.count_away || side.methyl_away)
+		if (int rc = side_outputs_away(m, side.cov_away, side.snp_away, side.count_away, side.methyl_away, n, q, units, paired, hits, sam_refs, (size_t) b.str_base + b.extra.size(), sam)) return rc;
 	float bgzf_ms = 0.f;
 	if (bam && total > 0) if (int rc = route_bam(b, total, units, &bgzf_ms)) return rc;
 	if (sam->stats) { sam->stats[0] = ctr[0]; sam->stats[1] = ctr[1]; sam->stats[2] = ctr[2]; }

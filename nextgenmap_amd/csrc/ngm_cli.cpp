@@ -19,7 +19,9 @@
 // --snp-min-qual (ours: the mismatch pileup of the same records and its single-base substitution calls as VCF, counted and turned into text on the GPU,
 // csrc/snp.cpp; not with --argos, --shard, --shard-output, --bs-mapping, --vcf, nor FILE = the output or the --coverage file), and --count BED --count-out FILE
 // with --count-min-qual (ours: T>C conversion counts of the same records per region of the BED file, counted and summed on the GPU, the positions --snp calls
-// left out, csrc/count.cpp; not with --argos, --shard, --shard-output, --bs-mapping, nor FILE = another output).  Not supported (rejected loudly): --vcf with --bs-mapping, --max-polya with --argos or --vcf, --config.
+// left out, csrc/count.cpp; not with --argos, --shard, --shard-output, --bs-mapping, nor FILE = another output), and --methyl FILE with --methyl-context,
+// --methyl-min-qual, --methyl-min-depth (ours, with --bs-mapping: the per-cytosine methylation calls of the same records as Bismark's cytosine report, counted and
+// turned into text on the GPU, csrc/methyl.cpp; not with --argos, --shard, --shard-output, nor FILE = the output or the --coverage file).  Not supported (rejected loudly): --vcf with --bs-mapping, --max-polya with --argos or --vcf, --config.
 //
 // Pass 2 is a pipeline, not a loop:
 //   splitter (1 thread)   cuts the input into batches: for plain 4-line FASTQ it only counts line ends in the mapped file
@@ -356,13 +358,14 @@ struct Run {
 	ngm_coverage *coverage = nullptr;
 	ngm_snp *snp = nullptr;
 	ngm_count *counter = nullptr;
+	ngm_methyl *methyl = nullptr;   // --methyl: the methylation counters, beside the first GPU's resident reference
 	std::vector<ngm::cnt::Region> count_regions;   // --count: the BED file's regions, read before any GPU work
 	std::vector<std::string> count_names;          // ... and the contigs they were checked against (the FASTA's, as the reference will hold them)
 	std::vector<uint32_t> count_lens;
-	FILE *coverage_file = nullptr, *snp_file = nullptr, *count_file = nullptr;
+	FILE *coverage_file = nullptr, *snp_file = nullptr, *count_file = nullptr, *methyl_file = nullptr;
 	HostFormatter fmt;
 	std::atomic<uint64_t> pair_stat[3];   // AlignmentBuffer::WriteRead's pair counters, summed over the run (the GPU formatter counts the same: ngm_mapper_last_pair_stats)
-	std::atomic<bool> cov_failed{false}, snp_failed{false}, count_failed{false};   // an ngm_coverage_add / ngm_snp_add / ngm_count_add of a formatted range failed: the run fails behind its batch
+	std::atomic<bool> cov_failed{false}, snp_failed{false}, count_failed{false}, methyl_failed{false};   // an ngm_coverage_add / ngm_snp_add / ngm_count_add of a formatted range failed: the run fails behind its batch
 	// the pipeline
 	std::unique_ptr<BoundedQueue<std::unique_ptr<Batch>>> q_in;
 	std::mutex out_mu, fail_mu, text_mu, spare_mu;
@@ -853,6 +856,15 @@ void Run::create_mappers_and_side_outputs() {
 				(unsigned long long) tab.slots, (double) tab.slots * 8.0 / (double) (1 << 20), o.devices[0]);
 		if (route.gpu_sam) for (Worker &w : workers) if (ngm_mapper_set_count(w.m, counter) < 0) die(ngm_pipeline_last_error());
 	}
+	if (!o.methyl.empty()) {   // a pair of counters (meth, unmeth) per base, beside that GPU's resident reference
+		methyl_file = open_before_run(o.methyl);
+		ngm_methyl_params mp{};
+		mp.min_qual = (int) o.methyl_min_qual; mp.min_depth = (int) o.methyl_min_depth; mp.context = o.methyl_context.c_str();
+		methyl = ngm_methyl_create_for_ref(refs[0], &mp);
+		if (!methyl) die(std::string("--methyl: ") + ngm_pipeline_last_error());
+		infof("MAIN", "Methylation counters: %.1f MiB on GPU %d (8 bytes per base of the reference, held for the whole run)", (double) bases * 8.0 / (double) (1 << 20), o.devices[0]);
+		if (route.gpu_sam) for (Worker &w : workers) if (ngm_mapper_set_methyl(w.m, methyl) < 0) die(ngm_pipeline_last_error());
+	}
 }
 
 // the host formatter (cli_format.h), built once from plain values
@@ -871,6 +883,9 @@ void Run::setup_formatter() {
 	};
 	if (counter) fmt.add_count = [this](const SnpAcc &a, bool has_qual) {
 		if (ngm_count_add(counter, a.ref.data(), a.pos.data(), a.off.data(), a.text.data(), a.seq_off.data(), a.seq.data(), has_qual ? a.qual.c_str() : nullptr, a.rev.data(), a.ref.size()) < 0) count_failed = true;
+	};
+	if (methyl) fmt.add_methyl = [this](const MethylAcc &a, bool has_qual) {
+		if (ngm_methyl_add(methyl, a.ref.data(), a.pos.data(), a.off.data(), a.text.data(), a.seq_off.data(), a.seq.data(), has_qual ? a.qual.c_str() : nullptr, a.bottom.data(), a.ref.size()) < 0) methyl_failed = true;
 	};
 }
 
@@ -1241,7 +1256,7 @@ void Run::host_format_route(Worker &w, std::unique_ptr<Batch> &b, PairTurn &turn
 		for (int k = 0; k < 3; ++k) if (c.pair[k]) pair_stat[k] += c.pair[k];
 	}
 	auto add_failed = [&](const std::atomic<bool> &flag, const char *option) { if (flag) fail(std::string(option) + ngm_pipeline_last_error()); return (bool) flag; };
-	if (add_failed(cov_failed, "--coverage: ") || add_failed(snp_failed, "--snp: ") || add_failed(count_failed, "--count: ")) return;
+	if (add_failed(cov_failed, "--coverage: ") || add_failed(snp_failed, "--snp: ") || add_failed(count_failed, "--count: ") || add_failed(methyl_failed, "--methyl: ")) return;
 	if (route.gpu_bgzf && !gpu_bgzf_chunks(w, *b)) return;
 	recycle_input(*b);
 	t_format_us += us_since(tf);
@@ -1488,6 +1503,20 @@ void Run::drain_side_outputs() {
 					(unsigned long long) kc[4], count_regions.size(), kms[0], kms[1], span_s(t_count));
 		}
 	}
+	if (methyl && !failed) {
+		const auto t_methyl = Clock::now();
+		drain([&] { return ngm_methyl_finish(methyl); }, [&](char *p, size_t n) { return ngm_methyl_next(methyl, p, n); }, methyl_file, o.methyl, "--methyl: ");
+		if (!failed) {
+			uint64_t mc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+			float mms[4] = {0, 0, 0, 0};
+			(void) ngm_methyl_stats(methyl, mc, mms);
+			auto pct = [](uint64_t m, uint64_t u) { return m + u ? 100.0 * (double) m / (double) (m + u) : 0.0; };
+			infof("MAIN", "Methylation on the GPU: %llu alignments, %llu lines; kernels: add %.2f ms, flag %.2f ms, select %.2f ms, text %.2f ms; %.3f s after the last batch",
+					(unsigned long long) mc[0], (unsigned long long) mc[1], mms[0], mms[1], mms[2], mms[3], span_s(t_methyl));
+			infof("METHYL", "CpG %llu methylated, %llu unmethylated (%.2f%%); CHG %llu, %llu (%.2f%%); CHH %llu, %llu (%.2f%%)", (unsigned long long) mc[2], (unsigned long long) mc[3],
+					pct(mc[2], mc[3]), (unsigned long long) mc[4], (unsigned long long) mc[5], pct(mc[4], mc[5]), (unsigned long long) mc[6], (unsigned long long) mc[7], pct(mc[6], mc[7]));
+		}
+	}
 }
 
 // ---- the final report -----------------------------------------------------------------------------------------------------------
@@ -1595,8 +1624,8 @@ void Run::teardown() {
 	for (Worker &w : workers) { ngm_mapper_destroy(w.m); ngm_host_free(w.rows); ngm_host_free(w.qrows); ngm_host_free(w.names); ngm_host_free(w.meta); ngm_host_free(w.polya);
 		ngm_bgzf_destroy(w.bz); ngm_host_free(w.bam_raw); ngm_host_free(w.bam_out); }
 	ngm_bam_sort_destroy(sorter);
-	ngm_coverage_destroy(coverage); ngm_snp_destroy(snp); ngm_count_destroy(counter);
-	for (FILE *f : {coverage_file, snp_file, count_file}) if (f) fclose(f);
+	ngm_coverage_destroy(coverage); ngm_snp_destroy(snp); ngm_count_destroy(counter); ngm_methyl_destroy(methyl);
+	for (FILE *f : {coverage_file, snp_file, count_file, methyl_file}) if (f) fclose(f);
 	for (TextBuf &t : text_free) ngm_host_free(t.p);
 	ngm_pair_state_destroy(pair_state);
 	for (ngm_ref *r2 : refs) ngm_ref_destroy(r2);

@@ -123,20 +123,23 @@ void pipeline_set_error(const char *fmt, ...);
 // units + 1 offsets into d_records, the last one n_bytes; both complete), and the device a sorter lives on
 int bam_sort_add_device(struct ::ngm_bam_sort *s, uint64_t seq, const void *d_records, size_t n_bytes, const uint32_t *d_unit_off, size_t units);
 int bam_sort_device(const struct ::ngm_bam_sort *s);
-// for the mapper's SAM stage: a side output (--coverage, --snp, --count) as what the three share (side_output.h: its device, the time an
+// for the mapper's SAM stage: a side output (--coverage, --snp, --count, --methyl) as what the four share (side_output.h: its device, the time an
 // add kernel of the mapper's took), and per object where such a kernel on its device adds (-22 and the message after the object's finish)
 namespace side {
 struct Base;
 Base *base(struct ::ngm_coverage *c);
 Base *base(struct ::ngm_snp *c);
 Base *base(struct ::ngm_count *c);
+Base *base(struct ::ngm_methyl *c);
 }
 namespace cov { struct Target { int32_t *counters; const uint64_t *off; int n_ref; unsigned long long *n_aln; }; }   // (off: the contigs' offsets)
 namespace snp { struct Target; }                     // snp_device.h
 namespace cnt { struct Layout; struct Counters; }    // count.h, count_device.h
+namespace met { struct Layout; struct Counters; }    // methyl.h, methyl_device.h
 int coverage_target(struct ::ngm_coverage *c, cov::Target *t);
 int snp_target(struct ::ngm_snp *c, snp::Target *t);
 int count_target(struct ::ngm_count *c, cnt::Layout *l, cnt::Counters *t);
+int methyl_target(struct ::ngm_methyl *c, met::Layout *l, met::Counters *t);
 // k-mer integer as the reference builds it: 2 bits per base, A0 C1 T2 G3 ((c >> 1) & 3, CSstatic.cpp:20-22)
 inline uint32_t kmer_code_of_class(uint32_t cls) { return cls == 2 ? 3u : (cls == 3 ? 2u : cls); }
 // reverse complement of a k-mer integer (PrefixTable.cpp:94-108), valid for 2k <= 32

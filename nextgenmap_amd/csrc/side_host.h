@@ -1,4 +1,4 @@
-// side_host.h -- the host-only parts the run-long side outputs (csrc/coverage.cpp, csrc/snp.cpp, csrc/count.cpp) share: the checks in
+// side_host.h -- the host-only parts the run-long side outputs (csrc/coverage.cpp, csrc/snp.cpp, csrc/count.cpp, csrc/methyl.cpp) share: the checks in
 // front of an add, the whole-lines rule of a text output's next, and the contigs' table of an object.  No HIP here: compiles with plain
 // g++ (tests/cpp/side_host_driver.cpp, which supplies its own ngm::pipeline_set_error).  The HIP part: csrc/side_output.h.
 #pragma once

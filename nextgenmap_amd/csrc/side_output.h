@@ -1,4 +1,4 @@
-// side_output.h -- the HIP part the run-long side outputs (csrc/coverage.cpp, csrc/snp.cpp, csrc/count.cpp) share: an object's lifetime
+// side_output.h -- the HIP part the run-long side outputs (csrc/coverage.cpp, csrc/snp.cpp, csrc/count.cpp, csrc/methyl.cpp) share: an object's lifetime
 // and statistics (Base), the staging of a batch that comes as arrays (Staged), the contigs' names on the device (Names), and the chunked
 // finish of a per-base text output -- scan, flags, select, lengths, offsets, text, whole lines (LineStream).  A side output supplies its
 // kernels, their argument struct and what it carries from chunk to chunk; DESIGN.md, "A new side output".  Host-only parts: side_host.h.
@@ -211,6 +211,32 @@ struct LineStream {
 		NGM_HIP_TRY(hipEventRecord(b.ev[2], b.st));
 		NGM_HIP_TRY(hipMemcpyAsync(m, d_m.p, 4, hipMemcpyDeviceToHost, b.st));
 		NGM_HIP_TRY(hipMemcpyAsync(last_depth, depth + n - 1, 4, hipMemcpyDeviceToHost, b.st));
+		NGM_HIP_TRY(hipStreamSynchronize(b.st));
+		b.took(1, 0, 1);
+		b.took(2, 1, 2);
+		text.clear();
+		text_at = 0;
+		next_slot += n;
+		return 0;
+	}
+	// The two steps above for an output without a depth array: the temporaries of the select alone, and a chunk of n slots that
+	// flag_launch flags from the object's own counters -- no scan.  Times into ms[1] (flags) and ms[2] (select).
+	int reserve_select(Base &b, size_t n, const char *refusal) {
+		size_t tb = 0;
+		NGM_HIP_TRY(rocprim::select(nullptr, tb, rocprim::counting_iterator<uint32_t>(0), (uint8_t *) nullptr, (uint32_t *) nullptr, (uint32_t *) nullptr, n, b.st));
+		if (flag.alloc(n) || idx.alloc(n) || tmp.alloc(tb + 16)) { pipeline_set_error(refusal, n); return -12; }
+		return 0;
+	}
+	template <typename Launch>
+	int select_only(Base &b, size_t n, Launch flag_launch, uint32_t *m) {
+		NGM_HIP_TRY(hipEventRecord(b.ev[0], b.st));
+		flag_launch();
+		NGM_HIP_TRY(hipGetLastError());
+		NGM_HIP_TRY(hipEventRecord(b.ev[1], b.st));
+		size_t tb = tmp.n;
+		NGM_HIP_TRY(rocprim::select(tmp.p, tb, rocprim::counting_iterator<uint32_t>(0), flag.p, idx.p, d_m.p, n, b.st));
+		NGM_HIP_TRY(hipEventRecord(b.ev[2], b.st));
+		NGM_HIP_TRY(hipMemcpyAsync(m, d_m.p, 4, hipMemcpyDeviceToHost, b.st));
 		NGM_HIP_TRY(hipStreamSynchronize(b.st));
 		b.took(1, 0, 1);
 		b.took(2, 1, 2);

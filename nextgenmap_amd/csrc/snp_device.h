@@ -49,6 +49,7 @@ struct SnpBatch {
 		const uint8_t *row, *q;
 		int L, s0, QL;      // QL < 0: the read has no quality string
 		bool reverse;
+		int mate;           // 1: the second read of a pair (flag 0x80)
 		// the printed sequence and qualities of bam_mapped / sam_mapped (sam_device.h)
 		__device__ __forceinline__ char base(uint32_t i) const {
 			if (!reverse) return (char) row[s0 + (int) i];
@@ -75,7 +76,7 @@ struct SnpBatch {
 			const int s0 = max(0, min(clip ? (int) h.qstart : 0, v.L));
 			const int sl = max(0, min(clip ? v.L - (int) h.qstart - (int) h.qend : v.L, v.L - s0));   // (never past the row)
 			const int qlen = v.m.qual_len & 0x7FFF;
-			f(Rec{h.contig, (int64_t) h.pos, A.str + rf.cig_off, (uint32_t) rf.cig_len, (uint32_t) sl, v.row, v.qual, v.L, s0, qlen ? min(qlen, v.L) : -1, h.reverse != 0});
+			f(Rec{h.contig, (int64_t) h.pos, A.str + rf.cig_off, (uint32_t) rf.cig_len, (uint32_t) sl, v.row, v.qual, v.L, s0, qlen ? min(qlen, v.L) : -1, h.reverse != 0, k});
 		}
 	}
 };

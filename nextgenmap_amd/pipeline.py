@@ -52,6 +52,11 @@ class CountParams(C.Structure):   # ngm_count_params
                 ("min_qual", C.c_int), ("n_regions", C.c_size_t), ("region_ref", C.c_void_p), ("region_start", C.c_void_p), ("region_end", C.c_void_p), ("region_strand", C.c_char_p)]
 
 
+class MethylParams(C.Structure):   # ngm_methyl_params
+    _fields_ = [("device", C.c_int), ("n_ref", C.c_int), ("ref_len", C.POINTER(C.c_uint32)), ("ref_name", C.POINTER(C.c_char_p)), ("ref_seq", C.POINTER(C.c_char_p)),
+                ("min_qual", C.c_int), ("min_depth", C.c_int), ("context", C.c_char_p), ("scan_chunk", C.c_size_t)]
+
+
 def _lib():
     global _bound
     lib = load_library()
@@ -176,6 +181,17 @@ def _lib():
         lib.ngm_count_read.restype = C.c_longlong
         lib.ngm_count_read.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         lib.ngm_count_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.ngm_methyl_create.restype = C.c_void_p
+        lib.ngm_methyl_create.argtypes = [C.POINTER(MethylParams)]
+        lib.ngm_methyl_create_for_ref.restype = C.c_void_p
+        lib.ngm_methyl_create_for_ref.argtypes = [C.c_void_p, C.POINTER(MethylParams)]
+        lib.ngm_methyl_destroy.argtypes = [C.c_void_p]
+        lib.ngm_methyl_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t]
+        lib.ngm_methyl_finish.argtypes = [C.c_void_p]
+        lib.ngm_methyl_next.restype = C.c_longlong
+        lib.ngm_methyl_next.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.ngm_methyl_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.ngm_mapper_set_methyl.argtypes = [C.c_void_p, C.c_void_p]
         lib.ngm_mapper_set_count.argtypes = [C.c_void_p, C.c_void_p]
         _bound = True
     return lib
@@ -558,6 +574,63 @@ class SnpCaller(_LineStream):
         return d
 
 
+class MethylationCounter(_LineStream):
+    """The per-cytosine methylation calls of a bisulfite run, counted in GPU memory, handed back as Bismark's cytosine report
+    (include/ngm_pipeline.h, ngm_methyl_*): what `ngm-hip --bs-mapping --methyl` writes.  contigs: [(name, sequence)]; context: "all", "CpG",
+    "CHG" or "CHH"; reference: a Reference whose resident genome is read instead (contigs is then not used)."""
+
+    _prefix = "methyl"
+    STATS = ("alignments", "lines", "cpg_meth", "cpg_unmeth", "chg_meth", "chg_unmeth", "chh_meth", "chh_unmeth")
+
+    def __init__(self, contigs, device=0, min_qual=5, min_depth=1, context="all", scan_chunk=0, reference=None):
+        b = lambda x: x.encode() if isinstance(x, str) else bytes(x)
+        p = MethylParams()
+        p.device, p.min_qual, p.min_depth, p.context, p.scan_chunk = device, min_qual, min_depth, b(context), scan_chunk
+        if reference is not None:
+            self._ref = reference   # (it must outlive this object)
+            self._h = _lib().ngm_methyl_create_for_ref(reference.h, C.byref(p))
+        else:
+            n = len(contigs)
+            self._seq_bytes = [b(sq) for _, sq in contigs]
+            self._len = (C.c_uint32 * max(1, n))(*[len(sq) for sq in self._seq_bytes])
+            self._name = (C.c_char_p * max(1, n))(*[b(nm) for nm, _ in contigs])
+            self._seq = (C.c_char_p * max(1, n))(*self._seq_bytes)
+            p.n_ref, p.ref_len, p.ref_name, p.ref_seq = n, self._len, self._name, self._seq
+            self._h = _lib().ngm_methyl_create(C.byref(p))
+        if not self._h:
+            raise _err()
+
+    def add(self, records):
+        """[(contig index, 0-based position, CIGAR text, sequence, qualities or None, bottom)]: all with qualities or all without; raises
+        on the first record the validator refuses, adding nothing"""
+        self.add_arrays(*_pack_records(records, True))
+
+    def add_arrays(self, ref_id, pos0, cigar_off, cigar_text, seq_off, seq_text, qual_text, bottom):
+        ref_id = np.ascontiguousarray(ref_id, dtype=np.int32)
+        pos0 = np.ascontiguousarray(pos0, dtype=np.int32)
+        cigar_off = np.ascontiguousarray(cigar_off, dtype=np.uint32)
+        seq_off = np.ascontiguousarray(seq_off, dtype=np.uint32)
+        bottom = np.ascontiguousarray(bottom, dtype=np.uint8)
+        if len(pos0) != len(ref_id) or len(bottom) != len(ref_id) or len(cigar_off) != len(ref_id) + 1 or len(seq_off) != len(ref_id) + 1:
+            raise ValueError("ref_id, pos0, bottom of n entries and cigar_off, seq_off of n + 1")
+        if _lib().ngm_methyl_add(self._h, ref_id.ctypes.data, pos0.ctypes.data, cigar_off.ctypes.data, bytes(cigar_text), seq_off.ctypes.data, bytes(seq_text),
+                                 None if qual_text is None else bytes(qual_text), bottom.ctypes.data, len(ref_id)) < 0:
+            raise _err()
+
+    def text(self, cap=1 << 20):
+        """after finish(): the whole report"""
+        return b"".join(self.pieces(cap))
+
+    def stats(self):
+        counts = (C.c_uint64 * 8)()
+        ms = (C.c_float * 4)()
+        if _lib().ngm_methyl_stats(self._h, counts, ms) < 0:
+            raise _err()
+        d = dict(zip(self.STATS, (int(x) for x in counts)))
+        d.update(zip(("add_ms", "flag_ms", "select_ms", "text_ms"), (float(x) for x in ms)))
+        return d
+
+
 SAM_READ_DTYPE = np.dtype([("name_off", np.uint32), ("name_len", np.uint16), ("qual_len", np.uint16)])   # ngm_sam_read
 
 
@@ -813,6 +886,12 @@ class Mapper:
         if self.lib.ngm_mapper_set_count(self.h, count._h if count is not None else None) < 0:
             raise _err()
         self._count = count
+
+    def set_methyl(self, methyl):
+        """every batch map_sam finishes adds its mapped primary records to `methyl` (a MethylationCounter, or None to detach)"""
+        if self.lib.ngm_mapper_set_methyl(self.h, methyl._h if methyl is not None else None) < 0:
+            raise _err()
+        self._methyl = methyl
 
     def set_snp(self, snp):
         """every batch map_sam finishes adds its mapped primary records to `snp` (a SnpCaller, or None to detach)"""
