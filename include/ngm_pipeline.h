@@ -517,6 +517,9 @@ int ngm_mapper_set_methyl(ngm_mapper *m, ngm_methyl *c);
 /* page-locked host memory for read batches (the H2D copy then runs at PCIe rate without a staging copy) */
 void *ngm_host_alloc(size_t bytes);
 void ngm_host_free(void *p);
+/* test hook: what the library itself holds in this process (ngm_host_alloc is the caller's and is not counted) -- out[0] device bytes
+ * live, out[1] pinned host bytes live, out[2] device allocations so far, out[3] pinned allocations so far */
+int ngm_debug_live_memory(uint64_t out[4]);
 
 /* Host threads next to the GPU.  A two-socket host runs the host stages (read parsing, pair selection, SAM text) at half the
  * rate when their threads and buffers are spread over both sockets (measured with ngm-hip).  This pins the

@@ -31,9 +31,9 @@ using ngm::blocks_of;
 namespace {
 struct Segment {
 	uint64_t seq = 0;
-	uint8_t *d = nullptr;          // the run's bytes, 16 bytes of padding behind them
+	Buf<uint8_t> d;                // the run's bytes, 16 bytes of padding behind them
 	size_t bytes = 0;
-	uint32_t *d_rec_off = nullptr; // where its records start
+	Buf<uint32_t> d_rec_off;       // where its records start
 	uint32_t n_rec = 0;
 };
 
@@ -100,10 +100,7 @@ extern "C" void ngm_bam_sort_destroy(ngm_bam_sort *s) {
 	DeviceGuard g(s->device);
 	if (s->st) (void) hipStreamSynchronize(s->st);
 	if (s->st_gather) (void) hipStreamSynchronize(s->st_gather);
-	for (Segment &sg : s->segs) { (void) hipFree(sg.d); (void) hipFree(sg.d_rec_off); }
 	ngm_bgzf_destroy(s->bz);
-	s->key.release(); s->u.release(); s->s_ptr.release(); s->s_end.release(); s->s_bin_flag.release(); s->chunk[0].release(); s->chunk[1].release();
-	s->w_count.release(); s->w_base.release(); s->w_bad.release(); s->w_off.release(); s->w_tmp.release();
 	if (s->ev0) (void) hipEventDestroy(s->ev0);
 	if (s->ev1) (void) hipEventDestroy(s->ev1);
 	for (int b = 0; b < 2; ++b) for (int e = 0; e < 2; ++e) if (s->evg[b][e]) (void) hipEventDestroy(s->evg[b][e]);
@@ -127,15 +124,15 @@ int index_segment(ngm_bam_sort *s, Segment &sg, const uint32_t *d_off, uint32_t 
 	if (s->w_count.grow((size_t) n_ranges + 1) || s->w_base.grow((size_t) n_ranges + 1) || s->w_bad.grow(1) || s->w_tmp.grow(tb + 16)) return out_of_memory(s, "record offsets", ((size_t) n_ranges + 1) * 8 + tb);
 	auto write = [&](uint32_t cap) -> int {
 		if (cap == 0) return 0;
-		if (hipMalloc(&sg.d_rec_off, (size_t) cap * 4) != hipSuccess) { (void) hipGetLastError(); sg.d_rec_off = nullptr; return out_of_memory(s, "record offsets", (size_t) cap * 4); }
-		hipLaunchKernelGGL(bs::walk_ranges_kernel<true>, dim3(blocks_of(n_ranges)), dim3(256), 0, s->st, (const uint8_t *) sg.d, d_off, n_ranges, (uint32_t *) nullptr, (const uint32_t *) s->w_base.p,
-				sg.d_rec_off, cap, s->w_bad.p);
+		if (sg.d_rec_off.alloc(cap)) return out_of_memory(s, "record offsets", (size_t) cap * 4);
+		hipLaunchKernelGGL(bs::walk_ranges_kernel<true>, dim3(blocks_of(n_ranges)), dim3(256), 0, s->st, (const uint8_t *) sg.d.p, d_off, n_ranges, (uint32_t *) nullptr, (const uint32_t *) s->w_base.p,
+				sg.d_rec_off.p, cap, s->w_bad.p);
 		NGM_HIP_TRY(hipGetLastError());
 		return 0;
 	};
 	NGM_HIP_TRY(hipMemsetAsync(s->w_bad.p, 0xFF, 4, s->st));
 	NGM_HIP_TRY(hipMemsetAsync(s->w_count.p + n_ranges, 0, 4, s->st));
-	hipLaunchKernelGGL(bs::walk_ranges_kernel<false>, dim3(blocks_of(n_ranges)), dim3(256), 0, s->st, (const uint8_t *) sg.d, d_off, n_ranges, s->w_count.p, (const uint32_t *) nullptr,
+	hipLaunchKernelGGL(bs::walk_ranges_kernel<false>, dim3(blocks_of(n_ranges)), dim3(256), 0, s->st, (const uint8_t *) sg.d.p, d_off, n_ranges, s->w_count.p, (const uint32_t *) nullptr,
 			(uint32_t *) nullptr, 0u, s->w_bad.p);
 	NGM_HIP_TRY(hipGetLastError());
 	NGM_HIP_TRY(rocprim::exclusive_scan(s->w_tmp.p, tb, s->w_count.p, s->w_base.p, 0u, (size_t) n_ranges + 1, rocprim::plus<uint32_t>(), s->st));
@@ -169,11 +166,11 @@ int add_segment(ngm_bam_sort *s, uint64_t seq, const void *src, bool src_on_devi
 	DeviceGuard g(s->device);
 	Segment sg;
 	sg.seq = seq; sg.bytes = n_bytes;
-	if (hipMalloc(&sg.d, n_bytes + 16) != hipSuccess) { (void) hipGetLastError(); s->seqs.erase(seq); return out_of_memory(s, "a segment of records", n_bytes + 16); }
+	if (sg.d.alloc(n_bytes + 16)) { s->seqs.erase(seq); return out_of_memory(s, "a segment of records", n_bytes + 16); }
 	int rc = 0;
 	auto body = [&]() -> int {
-		NGM_HIP_TRY(hipMemsetAsync(sg.d + n_bytes, 0, 16, s->st));
-		NGM_HIP_TRY(hipMemcpyAsync(sg.d, src, n_bytes, src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->st));
+		NGM_HIP_TRY(hipMemsetAsync(sg.d.p + n_bytes, 0, 16, s->st));
+		NGM_HIP_TRY(hipMemcpyAsync(sg.d.p, src, n_bytes, src_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s->st));
 		if (h_off) {
 			if (s->w_off.grow((size_t) n_ranges + 1)) return out_of_memory(s, "range offsets", ((size_t) n_ranges + 1) * 4);
 			NGM_HIP_TRY(hipMemcpyAsync(s->w_off.p, h_off, ((size_t) n_ranges + 1) * 4, hipMemcpyHostToDevice, s->st));   // (pageable memory: staged before the call returns)
@@ -181,10 +178,10 @@ int add_segment(ngm_bam_sort *s, uint64_t seq, const void *src, bool src_on_devi
 		return index_segment(s, sg, h_off ? s->w_off.p : d_off, n_ranges, expect_records);
 	};
 	rc = body();
-	if (rc < 0) { (void) hipStreamSynchronize(s->st); (void) hipFree(sg.d); (void) hipFree(sg.d_rec_off); s->seqs.erase(seq); return rc; }
+	if (rc < 0) { (void) hipStreamSynchronize(s->st); s->seqs.erase(seq); return rc; }   // (the segment goes behind the synchronisation)
 	s->total_bytes += n_bytes;
 	s->n_rec += sg.n_rec;
-	s->segs.push_back(sg);
+	s->segs.push_back(std::move(sg));
 	return 0;
 }
 }  // namespace
@@ -238,13 +235,13 @@ int mark_duplicates(ngm_bam_sort *s) {
 	auto sort64 = [&](auto keys_in, uint64_t *keys_out, auto vals_in, uint32_t *vals_out, uint64_t count) -> int {
 		size_t tb = 0;
 		NGM_HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, keys_in, keys_out, vals_in, vals_out, (size_t) count, 0, 64, st));
-		if (tb + 16 > tmp.n && tmp.alloc(tb + 16)) return out_of_memory(s, "the sort of duplicate marking", tb);
+		if (tb + 16 > tmp.cap && tmp.alloc(tb + 16)) return out_of_memory(s, "the sort of duplicate marking", tb);
 		return timed(1, [&]() -> int { NGM_HIP_TRY(rocprim::radix_sort_pairs(tmp.p, tb, keys_in, keys_out, vals_in, vals_out, (size_t) count, 0, 64, st)); return 0; });
 	};
 	auto head_places = [&](uint32_t *hp, uint64_t count) -> int {   // in place: hp[r] = the place of r's group head
 		size_t tb = 0;
 		NGM_HIP_TRY(rocprim::inclusive_scan(nullptr, tb, hp, hp, (size_t) count, rocprim::maximum<uint32_t>(), st));
-		if (tb + 16 > tmp.n && tmp.alloc(tb + 16)) return out_of_memory(s, "a scan of duplicate marking", tb);
+		if (tb + 16 > tmp.cap && tmp.alloc(tb + 16)) return out_of_memory(s, "a scan of duplicate marking", tb);
 		NGM_HIP_TRY(rocprim::inclusive_scan(tmp.p, tb, hp, hp, (size_t) count, rocprim::maximum<uint32_t>(), st));
 		return 0;
 	};
@@ -260,7 +257,7 @@ int mark_duplicates(ngm_bam_sort *s) {
 		uint64_t g0 = 0;
 		for (const Segment &sg : s->segs) {
 			if (!sg.n_rec) continue;
-			hipLaunchKernelGGL(md::ptrs_kernel, dim3(blocks_of(sg.n_rec)), dim3(256), 0, st, (const uint8_t *) sg.d, (const uint32_t *) sg.d_rec_off, sg.n_rec, g0, ptr.p);
+			hipLaunchKernelGGL(md::ptrs_kernel, dim3(blocks_of(sg.n_rec)), dim3(256), 0, st, (const uint8_t *) sg.d.p, (const uint32_t *) sg.d_rec_off.p, sg.n_rec, g0, ptr.p);
 			NGM_HIP_TRY(hipGetLastError());
 			g0 += sg.n_rec;
 		}
@@ -376,7 +373,7 @@ extern "C" int ngm_bam_sort_finish(ngm_bam_sort *s, int n_ref) {
 	uint64_t g0 = 0;
 	for (const Segment &sg : s->segs) {
 		if (!sg.n_rec) continue;
-		hipLaunchKernelGGL(bs::keys_kernel, dim3(blocks_of(sg.n_rec)), dim3(256), 0, s->st, (const uint8_t *) sg.d, (const uint32_t *) sg.d_rec_off, sg.n_rec, g0, n_ref, key_in.p, idx_in.p, ptr.p,
+		hipLaunchKernelGGL(bs::keys_kernel, dim3(blocks_of(sg.n_rec)), dim3(256), 0, s->st, (const uint8_t *) sg.d.p, (const uint32_t *) sg.d_rec_off.p, sg.n_rec, g0, n_ref, key_in.p, idx_in.p, ptr.p,
 				len.p, end_in.p, bin_flag.p, ctr.p, ctr.p + 1);
 		NGM_HIP_TRY(hipGetLastError());
 		g0 += sg.n_rec;
@@ -514,7 +511,7 @@ int build_index(ngm_bam_sort *s, uint64_t first) {
 				(const unsigned long long *) I.ref_last, (const unsigned long long *) I.ref_unmapped, n_intv.p, ref_mapped.p);
 		NGM_HIP_TRY(hipGetLastError());
 		NGM_HIP_TRY(rocprim::exclusive_scan(nullptr, tb, n_intv.p, win_base.p, (uint64_t) 0, (size_t) n_ref + 1, rocprim::plus<uint64_t>(), s->st));
-		if (tb + 16 > tmp.n && tmp.alloc(tb + 16)) return out_of_memory(s, "a scan", tb);
+		if (tb + 16 > tmp.cap && tmp.alloc(tb + 16)) return out_of_memory(s, "a scan", tb);
 		NGM_HIP_TRY(rocprim::exclusive_scan(tmp.p, tb, n_intv.p, win_base.p, (uint64_t) 0, (size_t) n_ref + 1, rocprim::plus<uint64_t>(), s->st));
 		NGM_HIP_TRY(hipMemcpyAsync(h_win_base.data(), win_base.p, ((size_t) n_ref + 1) * 8, hipMemcpyDeviceToHost, s->st));
 		NGM_HIP_TRY(hipStreamSynchronize(s->st));
@@ -526,7 +523,7 @@ int build_index(ngm_bam_sort *s, uint64_t first) {
 		hipLaunchKernelGGL(bs::chunks_kernel, dim3(blocks_of(n_coor)), dim3(256), 0, s->st, I, (const uint32_t *) before.p, ckey.p, cval.p, cbeg.p, cend.p);
 		NGM_HIP_TRY(hipGetLastError());
 		NGM_HIP_TRY(rocprim::radix_sort_pairs(nullptr, tb, ckey.p, ckey_s.p, cval.p, cval_s.p, (size_t) n_chunks, 0, 64, s->st));
-		if (tb + 16 > tmp.n && tmp.alloc(tb + 16)) return out_of_memory(s, "the sort of the chunks", tb);
+		if (tb + 16 > tmp.cap && tmp.alloc(tb + 16)) return out_of_memory(s, "the sort of the chunks", tb);
 		NGM_HIP_TRY(rocprim::radix_sort_pairs(tmp.p, tb, ckey.p, ckey_s.p, cval.p, cval_s.p, (size_t) n_chunks, 0, 64, s->st));
 		hipLaunchKernelGGL(bs::chunks_permute_kernel, dim3(blocks_of(n_chunks)), dim3(256), 0, s->st, (const uint32_t *) cval_s.p, (uint64_t) n_chunks, (const uint64_t *) cbeg.p,
 				(const uint64_t *) cend.p, cbeg_s.p, cend_s.p);
@@ -536,7 +533,7 @@ int build_index(ngm_bam_sort *s, uint64_t first) {
 		hipLaunchKernelGGL(bs::windows_kernel, dim3(blocks_of(n_coor)), dim3(256), 0, s->st, I, (const uint64_t *) win_base.p, n_win, rev.p);
 		NGM_HIP_TRY(hipGetLastError());
 		NGM_HIP_TRY(rocprim::inclusive_scan(nullptr, tb, rev.p, rev_s.p, (size_t) n_win, rocprim::minimum<unsigned long long>(), s->st));
-		if (tb + 16 > tmp.n && tmp.alloc(tb + 16)) return out_of_memory(s, "a scan", tb);
+		if (tb + 16 > tmp.cap && tmp.alloc(tb + 16)) return out_of_memory(s, "a scan", tb);
 		NGM_HIP_TRY(rocprim::inclusive_scan(tmp.p, tb, rev.p, rev_s.p, (size_t) n_win, rocprim::minimum<unsigned long long>(), s->st));
 		hipLaunchKernelGGL(bs::reverse_kernel, dim3(blocks_of(n_win)), dim3(256), 0, s->st, (const uint64_t *) rev_s.p, n_win, (uint64_t *) rev.p);
 		NGM_HIP_TRY(hipGetLastError());

@@ -23,34 +23,39 @@
 		}                                                                                       \
 	} while (0)
 
+using ngm::Buf;
+using ngm::PinnedBuf;
+
 struct ngm_bgzf {
 	int device = 0;
 	hipStream_t st = nullptr;
-	uint8_t *d_raw = nullptr, *d_out = nullptr, *d_dense = nullptr, *d_tables = nullptr;
-	uint32_t *d_sizes = nullptr;
-	unsigned long long *d_offsets = nullptr;
-	uint2 *d_scratch = nullptr;
-	unsigned long long *d_phases = nullptr;
-	size_t raw_cap = 0, blocks_cap = 0, dense_cap = 0;
+	// (buffers that grow together are released together before they are allocated anew, and the one allocated last is asked whether they
+	// fit: its capacity is 0 after any refusal)
+	Buf<uint8_t> d_raw, d_out, d_dense, d_tables;
+	Buf<uint32_t> d_sizes;
+	Buf<unsigned long long> d_offsets;
+	Buf<uint2> d_scratch;
+	Buf<unsigned long long> d_phases;
 	int grid = 0;
-	uint32_t *h_sizes = nullptr;              // page-locked
-	unsigned long long *h_offsets = nullptr;  // page-locked
-	size_t h_cap = 0;
+	PinnedBuf<uint32_t> h_sizes;
+	PinnedBuf<unsigned long long> h_offsets;
 	float last_ms = 0.f;
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
 	// the inflater (set up by the first ngm_bgzf_inflate): two slots, so that one chunk's copies run under its neighbour's kernel
 	struct InflateSlot {
 		hipStream_t st = nullptr;
 		hipEvent_t ev0 = nullptr, ev1 = nullptr;
-		uint8_t *d_in = nullptr, *d_out = nullptr, *h_in = nullptr, *h_out = nullptr;   // h_*: page-locked
-		ngm::inflate::Member *d_mem = nullptr, *h_mem = nullptr;
-		uint32_t *d_status = nullptr, *h_status = nullptr;
-		size_t in_cap = 0, out_cap = 0, mem_cap = 0;
+		Buf<uint8_t> d_in, d_out;
+		PinnedBuf<uint8_t> h_in, h_out;
+		Buf<ngm::inflate::Member> d_mem;
+		PinnedBuf<ngm::inflate::Member> h_mem;
+		Buf<uint32_t> d_status;
+		PinnedBuf<uint32_t> h_status;
 		// the chunk in flight
 		size_t first_member = 0, n_members = 0, text_at = 0, text_bytes = 0;
 		bool busy = false;
 	} inf[2];
-	uint8_t *d_inf_tables = nullptr;   // CRC byte table [256], x^(8 m) [65537]
+	Buf<uint32_t> d_inf_tables;        // CRC byte table [256], x^(8 m) [65537]
 	hipEvent_t inf_base = nullptr;     // recorded in front of a call's first kernel: the chunks' kernel intervals are measured from it
 	float inf_busy_until = 0.f;        // ms after inf_base up to which the intervals seen so far reach
 	bool inf_ready = false;
@@ -99,9 +104,9 @@ extern "C" ngm_bgzf *ngm_bgzf_create(int device) {
 	bool ok = hipGetDeviceProperties(&prop, device) == hipSuccess;
 	z->grid = ok ? prop.multiProcessorCount : 256;
 	ok = ok && hipStreamCreateWithFlags(&z->st, hipStreamNonBlocking) == hipSuccess;
-	ok = ok && hipMalloc(&z->d_tables, kTabBytes) == hipSuccess && hipMemcpy(z->d_tables, t.data(), kTabBytes, hipMemcpyHostToDevice) == hipSuccess;
-	ok = ok && hipMalloc(&z->d_scratch, (size_t) z->grid * ngm::bgzf::kSegs * ngm::bgzf::kMatCap * sizeof(uint2)) == hipSuccess;
-	if (getenv("NGM_HIP_CS_PHASES")) ok = ok && hipMalloc(&z->d_phases, 64) == hipSuccess;   // (the diagnostics switch of the search kernels: phases of the deflate kernel too)
+	ok = ok && !z->d_tables.alloc(kTabBytes) && hipMemcpy(z->d_tables.p, t.data(), kTabBytes, hipMemcpyHostToDevice) == hipSuccess;
+	ok = ok && !z->d_scratch.alloc((size_t) z->grid * ngm::bgzf::kSegs * ngm::bgzf::kMatCap);
+	if (getenv("NGM_HIP_CS_PHASES")) ok = ok && !z->d_phases.alloc(8);   // (the diagnostics switch of the search kernels: phases of the deflate kernel too)
 	ok = ok && hipEventCreate(&z->ev0) == hipSuccess && hipEventCreate(&z->ev1) == hipSuccess;
 	ok = ok && hipFuncSetAttribute((const void *) ngm::bgzf::deflate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ngm::bgzf::deflate_lds_bytes()) == hipSuccess;
 	if (!ok) { ngm::pipeline_set_error("GPU BGZF compressor: set-up failed on device %d (%s)", device, hipGetErrorString(hipGetLastError())); ngm_bgzf_destroy(z); return nullptr; }
@@ -112,25 +117,15 @@ extern "C" void ngm_bgzf_destroy(ngm_bgzf *z) {
 	if (!z) return;
 	(void) hipSetDevice(z->device);
 	if (z->st) (void) hipStreamSynchronize(z->st);
-	(void) hipFree(z->d_raw); (void) hipFree(z->d_out); (void) hipFree(z->d_dense); (void) hipFree(z->d_tables); (void) hipFree(z->d_sizes);
-	(void) hipFree(z->d_offsets); (void) hipFree(z->d_scratch); (void) hipFree(z->d_phases);
-	if (z->h_sizes) (void) hipHostFree(z->h_sizes);
-	if (z->h_offsets) (void) hipHostFree(z->h_offsets);
 	if (z->ev0) (void) hipEventDestroy(z->ev0);
 	if (z->ev1) (void) hipEventDestroy(z->ev1);
 	if (z->st) (void) hipStreamDestroy(z->st);
 	for (ngm_bgzf::InflateSlot &s : z->inf) {
 		if (s.st) (void) hipStreamSynchronize(s.st);
-		(void) hipFree(s.d_in); (void) hipFree(s.d_out); (void) hipFree(s.d_mem); (void) hipFree(s.d_status);
-		if (s.h_in) (void) hipHostFree(s.h_in);
-		if (s.h_out) (void) hipHostFree(s.h_out);
-		if (s.h_mem) (void) hipHostFree(s.h_mem);
-		if (s.h_status) (void) hipHostFree(s.h_status);
 		if (s.ev0) (void) hipEventDestroy(s.ev0);
 		if (s.ev1) (void) hipEventDestroy(s.ev1);
 		if (s.st) (void) hipStreamDestroy(s.st);
 	}
-	(void) hipFree(z->d_inf_tables);
 	if (z->inf_base) (void) hipEventDestroy(z->inf_base);
 	delete z;
 }
@@ -145,14 +140,9 @@ extern "C" long long ngm_bgzf_compress(ngm_bgzf *z, const void *raw, size_t n, v
 	if (!z || (!raw && n) || !out) { ngm::pipeline_set_error("ngm_bgzf_compress: bad arguments"); return -22; }
 	if (n == 0) return 0;
 	BGZF_HIP_TRY(hipSetDevice(z->device));
-	if (n + 16 > z->raw_cap) {
-		(void) hipFree(z->d_raw); z->d_raw = nullptr; z->raw_cap = 0;
-		const size_t cap = n + n / 4 + 4096;
-		BGZF_HIP_TRY(hipMalloc(&z->d_raw, cap));
-		z->raw_cap = cap;
-	}
-	BGZF_HIP_TRY(hipMemcpyAsync(z->d_raw, raw, n, hipMemcpyHostToDevice, z->st));
-	return compress_on_device(z, z->d_raw, n, out, out_cap);
+	if (n + 16 > z->d_raw.cap) NGM_MEM_TRY(z->d_raw.alloc(n + n / 4 + 4096));
+	BGZF_HIP_TRY(hipMemcpyAsync(z->d_raw.p, raw, n, hipMemcpyHostToDevice, z->st));
+	return compress_on_device(z, z->d_raw.p, n, out, out_cap);
 }
 
 // the same for bytes that already are in this device's memory (complete: the caller has synchronised the stream that wrote them)
@@ -167,58 +157,47 @@ static long long compress_on_device(ngm_bgzf *z, const uint8_t *d_raw, size_t n,
 	if (out_cap < ngm_bgzf_bound(n)) { ngm::pipeline_set_error("ngm_bgzf_compress: the output buffer holds %zu bytes, %zu may be needed", out_cap, ngm_bgzf_bound(n)); return -22; }
 	const size_t nb = (n + ngm::bgzf::kIn - 1) / ngm::bgzf::kIn;
 	if (nb > 0x7fffffffull) { ngm::pipeline_set_error("ngm_bgzf_compress: too much input for one call"); return -22; }
-	if (nb > z->blocks_cap) {
-		(void) hipFree(z->d_out); (void) hipFree(z->d_sizes); (void) hipFree(z->d_offsets);
-		z->d_out = nullptr; z->d_sizes = nullptr; z->d_offsets = nullptr; z->blocks_cap = 0;
-		const size_t cap = nb + nb / 4 + 16;
-		BGZF_HIP_TRY(hipMalloc(&z->d_out, cap * ngm::bgzf::kStride));
-		BGZF_HIP_TRY(hipMalloc(&z->d_sizes, cap * 4));
-		BGZF_HIP_TRY(hipMalloc(&z->d_offsets, cap * 8));
-		z->blocks_cap = cap;
+	const size_t blocks = nb + nb / 4 + 16;
+	if (nb > z->d_offsets.cap) {
+		z->d_out.release(); z->d_sizes.release(); z->d_offsets.release();   // (the whole group first: after a refusal nothing of it is left, and the next call asks again)
+		NGM_MEM_TRY(z->d_out.alloc(blocks * ngm::bgzf::kStride));
+		NGM_MEM_TRY(z->d_sizes.alloc(blocks));
+		NGM_MEM_TRY(z->d_offsets.alloc(blocks));
 	}
-	if (nb > z->h_cap) {
-		if (z->h_sizes) (void) hipHostFree(z->h_sizes);
-		if (z->h_offsets) (void) hipHostFree(z->h_offsets);
-		z->h_sizes = nullptr; z->h_offsets = nullptr; z->h_cap = 0;
-		const size_t cap = nb + nb / 4 + 16;
-		BGZF_HIP_TRY(hipHostMalloc(&z->h_sizes, cap * 4, hipHostMallocDefault));
-		BGZF_HIP_TRY(hipHostMalloc(&z->h_offsets, cap * 8, hipHostMallocDefault));
-		z->h_cap = cap;
+	if (nb > z->h_offsets.cap) {
+		z->h_sizes.release(); z->h_offsets.release();
+		NGM_MEM_TRY(z->h_sizes.alloc(blocks));
+		NGM_MEM_TRY(z->h_offsets.alloc(blocks));
 	}
 	ngm::bgzf::Args A{};
-	A.raw = d_raw; A.n = n; A.n_blocks = (int) nb; A.out = z->d_out; A.sizes = z->d_sizes; A.scratch = z->d_scratch;
-	A.crc_table = (const uint32_t *) (z->d_tables + kTabCrc); A.xpow = (const uint32_t *) (z->d_tables + kTabXpow);
-	A.len_code = z->d_tables + kTabLen; A.dist_code = z->d_tables + kTabDist;
-	A.phase_cycles = z->d_phases;
-	if (z->d_phases) BGZF_HIP_TRY(hipMemsetAsync(z->d_phases, 0, 64, z->st));
+	A.raw = d_raw; A.n = n; A.n_blocks = (int) nb; A.out = z->d_out.p; A.sizes = z->d_sizes.p; A.scratch = z->d_scratch.p;
+	A.crc_table = (const uint32_t *) (z->d_tables.p + kTabCrc); A.xpow = (const uint32_t *) (z->d_tables.p + kTabXpow);
+	A.len_code = z->d_tables.p + kTabLen; A.dist_code = z->d_tables.p + kTabDist;
+	A.phase_cycles = z->d_phases.p;
+	if (z->d_phases.p) BGZF_HIP_TRY(hipMemsetAsync(z->d_phases.p, 0, 64, z->st));
 	BGZF_HIP_TRY(hipEventRecord(z->ev0, z->st));
 	hipLaunchKernelGGL(ngm::bgzf::deflate_kernel, dim3((unsigned) std::min<size_t>(nb, (size_t) z->grid)), dim3(ngm::bgzf::kNT), ngm::bgzf::deflate_lds_bytes(), z->st, A);
 	BGZF_HIP_TRY(hipGetLastError());
 	BGZF_HIP_TRY(hipEventRecord(z->ev1, z->st));
-	BGZF_HIP_TRY(hipMemcpyAsync(z->h_sizes, z->d_sizes, nb * 4, hipMemcpyDeviceToHost, z->st));
+	BGZF_HIP_TRY(hipMemcpyAsync(z->h_sizes.p, z->d_sizes.p, nb * 4, hipMemcpyDeviceToHost, z->st));
 	BGZF_HIP_TRY(hipStreamSynchronize(z->st));
 	unsigned long long total = 0;
 	for (size_t b = 0; b < nb; ++b) {
-		if (z->h_sizes[b] < 26u + 2u || z->h_sizes[b] > (uint32_t) ngm::bgzf::kStride) { ngm::pipeline_set_error("GPU BGZF compressor: block %zu has %u bytes", b, z->h_sizes[b]); return -5; }
-		z->h_offsets[b] = total;
-		total += z->h_sizes[b];
+		if (z->h_sizes.p[b] < 26u + 2u || z->h_sizes.p[b] > (uint32_t) ngm::bgzf::kStride) { ngm::pipeline_set_error("GPU BGZF compressor: block %zu has %u bytes", b, z->h_sizes.p[b]); return -5; }
+		z->h_offsets.p[b] = total;
+		total += z->h_sizes.p[b];
 	}
 	if (total > out_cap) { ngm::pipeline_set_error("GPU BGZF compressor: %llu bytes for a buffer of %zu", total, out_cap); return -5; }
-	if (total + 16 > z->dense_cap) {
-		(void) hipFree(z->d_dense); z->d_dense = nullptr; z->dense_cap = 0;
-		const size_t cap = (size_t) total + (size_t) total / 4 + 4096;
-		BGZF_HIP_TRY(hipMalloc(&z->d_dense, cap));
-		z->dense_cap = cap;
-	}
-	BGZF_HIP_TRY(hipMemcpyAsync(z->d_offsets, z->h_offsets, nb * 8, hipMemcpyHostToDevice, z->st));
-	hipLaunchKernelGGL(ngm::bgzf::gather_kernel, dim3((unsigned) std::min<size_t>(nb, (size_t) z->grid * 8)), dim3(256), 0, z->st, (const uint8_t *) z->d_out, (const uint32_t *) z->d_sizes,
-			(const unsigned long long *) z->d_offsets, z->d_dense, (int) nb);
+	if (total + 16 > z->d_dense.cap) NGM_MEM_TRY(z->d_dense.alloc((size_t) total + (size_t) total / 4 + 4096));
+	BGZF_HIP_TRY(hipMemcpyAsync(z->d_offsets.p, z->h_offsets.p, nb * 8, hipMemcpyHostToDevice, z->st));
+	hipLaunchKernelGGL(ngm::bgzf::gather_kernel, dim3((unsigned) std::min<size_t>(nb, (size_t) z->grid * 8)), dim3(256), 0, z->st, (const uint8_t *) z->d_out.p, (const uint32_t *) z->d_sizes.p,
+			(const unsigned long long *) z->d_offsets.p, z->d_dense.p, (int) nb);
 	BGZF_HIP_TRY(hipGetLastError());
-	BGZF_HIP_TRY(hipMemcpyAsync(out, z->d_dense, (size_t) total, hipMemcpyDeviceToHost, z->st));
+	BGZF_HIP_TRY(hipMemcpyAsync(out, z->d_dense.p, (size_t) total, hipMemcpyDeviceToHost, z->st));
 	BGZF_HIP_TRY(hipStreamSynchronize(z->st));
-	if (z->d_phases) {
+	if (z->d_phases.p) {
 		unsigned long long ph[8];
-		BGZF_HIP_TRY(hipMemcpy(ph, z->d_phases, 64, hipMemcpyDeviceToHost));
+		BGZF_HIP_TRY(hipMemcpy(ph, z->d_phases.p, 64, hipMemcpyDeviceToHost));
 		fprintf(stderr, "[ngm-hip] BGZF kernel, us of thread 0 per block (100 MHz clock): load %.1f | matching %.1f | crc + histograms %.1f | code lengths + codes %.1f | header + match scan %.1f | token bits %.1f | emit + copy out %.1f\n",
 				ph[0] / 100.0 / nb, ph[1] / 100.0 / nb, ph[2] / 100.0 / nb, ph[3] / 100.0 / nb, ph[4] / 100.0 / nb, ph[5] / 100.0 / nb, ph[6] / 100.0 / nb);
 	}
@@ -240,8 +219,8 @@ constexpr size_t kInfChunkIn = (size_t) 16 << 20, kInfChunkOut = (size_t) 64 << 
 int inflate_setup(ngm_bgzf *z) {
 	if (z->inf_ready) return 0;
 	const std::vector<uint32_t> t = ngm::inflate::crc_tables();
-	BGZF_HIP_TRY(hipMalloc(&z->d_inf_tables, t.size() * 4));
-	BGZF_HIP_TRY(hipMemcpy(z->d_inf_tables, t.data(), t.size() * 4, hipMemcpyHostToDevice));
+	NGM_MEM_TRY(z->d_inf_tables.alloc(t.size()));
+	BGZF_HIP_TRY(hipMemcpy(z->d_inf_tables.p, t.data(), t.size() * 4, hipMemcpyHostToDevice));
 	// more than 64 KiB of LDS per workgroup: the attribute is set for this object's device, and its result counts
 	BGZF_HIP_TRY(hipFuncSetAttribute((const void *) ngm::inflate::inflate_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) ngm::inflate::inflate_lds_bytes()));
 	for (ngm_bgzf::InflateSlot &s : z->inf) {
@@ -255,28 +234,22 @@ int inflate_setup(ngm_bgzf *z) {
 }
 
 int inflate_reserve(ngm_bgzf::InflateSlot &s, size_t in_bytes, size_t out_bytes, size_t members) {
-	if (in_bytes > s.in_cap) {
-		(void) hipFree(s.d_in); if (s.h_in) (void) hipHostFree(s.h_in);
-		s.d_in = s.h_in = nullptr; s.in_cap = 0;
-		BGZF_HIP_TRY(hipMalloc(&s.d_in, in_bytes));
-		BGZF_HIP_TRY(hipHostMalloc(&s.h_in, in_bytes, hipHostMallocDefault));
-		s.in_cap = in_bytes;
+	if (in_bytes > s.h_in.cap) {
+		s.d_in.release(); s.h_in.release();
+		NGM_MEM_TRY(s.d_in.alloc(in_bytes));
+		NGM_MEM_TRY(s.h_in.alloc(in_bytes));
 	}
-	if (out_bytes > s.out_cap) {
-		(void) hipFree(s.d_out); if (s.h_out) (void) hipHostFree(s.h_out);
-		s.d_out = s.h_out = nullptr; s.out_cap = 0;
-		BGZF_HIP_TRY(hipMalloc(&s.d_out, out_bytes));
-		BGZF_HIP_TRY(hipHostMalloc(&s.h_out, out_bytes, hipHostMallocDefault));
-		s.out_cap = out_bytes;
+	if (out_bytes > s.h_out.cap) {
+		s.d_out.release(); s.h_out.release();
+		NGM_MEM_TRY(s.d_out.alloc(out_bytes));
+		NGM_MEM_TRY(s.h_out.alloc(out_bytes));
 	}
-	if (members > s.mem_cap) {
-		(void) hipFree(s.d_mem); (void) hipFree(s.d_status); if (s.h_mem) (void) hipHostFree(s.h_mem); if (s.h_status) (void) hipHostFree(s.h_status);
-		s.d_mem = s.h_mem = nullptr; s.d_status = s.h_status = nullptr; s.mem_cap = 0;
-		BGZF_HIP_TRY(hipMalloc(&s.d_mem, members * sizeof(ngm::inflate::Member)));
-		BGZF_HIP_TRY(hipHostMalloc(&s.h_mem, members * sizeof(ngm::inflate::Member), hipHostMallocDefault));
-		BGZF_HIP_TRY(hipMalloc(&s.d_status, members * 4));
-		BGZF_HIP_TRY(hipHostMalloc(&s.h_status, members * 4, hipHostMallocDefault));
-		s.mem_cap = members;
+	if (members > s.h_status.cap) {
+		s.d_mem.release(); s.d_status.release(); s.h_mem.release(); s.h_status.release();
+		NGM_MEM_TRY(s.d_mem.alloc(members));
+		NGM_MEM_TRY(s.h_mem.alloc(members));
+		NGM_MEM_TRY(s.d_status.alloc(members));
+		NGM_MEM_TRY(s.h_status.alloc(members));
 	}
 	return 0;
 }
@@ -293,11 +266,11 @@ int inflate_harvest(ngm_bgzf *z, ngm_bgzf::InflateSlot &s, uint8_t *out, long lo
 		if (t1 > std::max(t0, z->inf_busy_until)) z->last_ms += t1 - std::max(t0, z->inf_busy_until);
 		z->inf_busy_until = std::max(z->inf_busy_until, t1);
 	}
-	for (size_t m = 0; m < s.n_members; ++m) if (s.h_status[m] != ngm::inflate::kOk) {
-		if (*bad < 0) { *bad = (long long) (s.first_member + m); *bad_status = s.h_status[m]; }
+	for (size_t m = 0; m < s.n_members; ++m) if (s.h_status.p[m] != ngm::inflate::kOk) {
+		if (*bad < 0) { *bad = (long long) (s.first_member + m); *bad_status = s.h_status.p[m]; }
 		return 0;
 	}
-	if (*bad < 0) memcpy(out + s.text_at, s.h_out, s.text_bytes);
+	if (*bad < 0) memcpy(out + s.text_at, s.h_out.p, s.text_bytes);
 	return 0;
 }
 }  // namespace
@@ -328,26 +301,26 @@ extern "C" long long ngm_bgzf_inflate(ngm_bgzf *z, const void *members, size_t n
 		const bool whole = m0 == 0 && m1 == chain.size();   // (a small input takes what it needs, a large one whole chunks)
 		if (int rc = inflate_reserve(s, whole ? in_bytes + 64 : kInfChunkIn + 65536 + 64, whole ? out_bytes + 64 : kInfChunkOut + 65536 + 64, whole ? m1 - m0 : std::max<size_t>(m1 - m0, kInfChunkIn / 28 / 64))) return rc;
 		const size_t base = chain[m0].at;
-		memcpy(s.h_in, in + base, in_bytes);
+		memcpy(s.h_in.p, in + base, in_bytes);
 		size_t o = 0;
 		for (size_t m = m0; m < m1; ++m) {
 			const ngm::inflate::HostMember &h = chain[m];
-			s.h_mem[m - m0] = ngm::inflate::Member{(uint32_t) (h.at - base + h.payload), (uint32_t) (h.at - base + h.size - 8), (uint32_t) o, h.isize};
+			s.h_mem.p[m - m0] = ngm::inflate::Member{(uint32_t) (h.at - base + h.payload), (uint32_t) (h.at - base + h.size - 8), (uint32_t) o, h.isize};
 			o += h.isize;
 		}
 		s.first_member = m0; s.n_members = m1 - m0; s.text_at = text_at; s.text_bytes = out_bytes;
-		BGZF_HIP_TRY(hipMemcpyAsync(s.d_in, s.h_in, in_bytes, hipMemcpyHostToDevice, s.st));
-		BGZF_HIP_TRY(hipMemcpyAsync(s.d_mem, s.h_mem, s.n_members * sizeof(ngm::inflate::Member), hipMemcpyHostToDevice, s.st));
+		BGZF_HIP_TRY(hipMemcpyAsync(s.d_in.p, s.h_in.p, in_bytes, hipMemcpyHostToDevice, s.st));
+		BGZF_HIP_TRY(hipMemcpyAsync(s.d_mem.p, s.h_mem.p, s.n_members * sizeof(ngm::inflate::Member), hipMemcpyHostToDevice, s.st));
 		ngm::inflate::Args A{};
-		A.in = s.d_in; A.members = s.d_mem; A.n_members = (int) s.n_members; A.out = s.d_out; A.status = s.d_status;
-		A.crc_table = (const uint32_t *) z->d_inf_tables; A.xpow = (const uint32_t *) z->d_inf_tables + 256;
+		A.in = s.d_in.p; A.members = s.d_mem.p; A.n_members = (int) s.n_members; A.out = s.d_out.p; A.status = s.d_status.p;
+		A.crc_table = z->d_inf_tables.p; A.xpow = z->d_inf_tables.p + 256;
 		if (c == 0) { BGZF_HIP_TRY(hipEventRecord(z->inf_base, s.st)); z->inf_busy_until = 0.f; }
 		BGZF_HIP_TRY(hipEventRecord(s.ev0, s.st));
 		hipLaunchKernelGGL(ngm::inflate::inflate_kernel, dim3((unsigned) std::min<size_t>(s.n_members, (size_t) z->grid * 2)), dim3(ngm::inflate::kNT), ngm::inflate::inflate_lds_bytes(), s.st, A);
 		BGZF_HIP_TRY(hipGetLastError());
 		BGZF_HIP_TRY(hipEventRecord(s.ev1, s.st));
-		BGZF_HIP_TRY(hipMemcpyAsync(s.h_status, s.d_status, s.n_members * 4, hipMemcpyDeviceToHost, s.st));
-		if (out_bytes) BGZF_HIP_TRY(hipMemcpyAsync(s.h_out, s.d_out, out_bytes, hipMemcpyDeviceToHost, s.st));
+		BGZF_HIP_TRY(hipMemcpyAsync(s.h_status.p, s.d_status.p, s.n_members * 4, hipMemcpyDeviceToHost, s.st));
+		if (out_bytes) BGZF_HIP_TRY(hipMemcpyAsync(s.h_out.p, s.d_out.p, out_bytes, hipMemcpyDeviceToHost, s.st));
 		s.busy = true;
 		text_at += out_bytes;
 		m0 = m1;

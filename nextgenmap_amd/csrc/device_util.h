@@ -9,6 +9,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "device_mem.h"   // ngm::Buf
 #include "refindex.h"   // ngm::pipeline_set_error
 
 // a failed HIP call: its text becomes ngm_pipeline_last_error() and the calling function returns -5
@@ -22,24 +23,6 @@
 	} while (0)
 
 namespace ngm {
-
-template <typename T>
-struct Buf {   // device memory: alloc() of exactly the size asked for, grow() with a quarter to spare when it has to
-	T *p = nullptr;
-	size_t n = 0;
-	int alloc(size_t count) {
-		release();
-		if (hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) { (void) hipGetLastError(); p = nullptr; return -1; }
-		n = count;
-		return 0;
-	}
-	int grow(size_t count) { return count <= n ? 0 : alloc(count + count / 4 + 64); }
-	void release() { if (p) (void) hipFree(p); p = nullptr; n = 0; }
-	~Buf() { release(); }
-	Buf() = default;
-	Buf(const Buf &) = delete;
-	Buf &operator=(const Buf &) = delete;
-};
 
 // a host vector into a buffer of exactly its size (true: placed; the copy is through once st is synchronised)
 template <typename T> bool put(Buf<T> &b, const std::vector<T> &v, hipStream_t st) {

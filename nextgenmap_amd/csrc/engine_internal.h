@@ -14,47 +14,7 @@
 #include "affine_device.h"
 #include "cigar_device.h"
 #include "jit.h"
-
-namespace ngm {
-template <typename T>
-struct DevBuf {
-	T *p = nullptr;
-	size_t cap = 0;  // elements
-	int reserve(size_t n) {
-		if (n <= cap) return 0;
-		if (p) (void) hipFree(p);
-		p = nullptr;
-		cap = 0;
-		// (an eighth more than asked for: batches of a real run differ by a few per cent, and every new maximum would otherwise be a
-		// hipFree + hipMalloc -- two device-wide synchronisations -- in the middle of the mapping pass)
-		const size_t want = n + std::min<size_t>(n / 8, ((size_t) 64 << 20) / sizeof(T));   // (at most 64 MB more: the index arrays come through here too)
-		if (hipMalloc(&p, want * sizeof(T)) == hipSuccess) { cap = want; return 0; }
-		if (hipMalloc(&p, n * sizeof(T)) != hipSuccess) return -1;
-		cap = n;
-		return 0;
-	}
-	void release() { if (p) (void) hipFree(p); p = nullptr; cap = 0; }
-};
-
-template <typename T>
-struct PinnedBuf {
-	T *p = nullptr;
-	size_t cap = 0;
-	int reserve(size_t n) {
-		if (n <= cap) return 0;
-		if (p) (void) hipHostFree(p);
-		p = nullptr;
-		cap = 0;
-		const size_t want = n + std::min<size_t>(n / 8, ((size_t) 64 << 20) / sizeof(T));
-		if (hipHostMalloc(&p, want * sizeof(T), hipHostMallocDefault) == hipSuccess) { cap = want; return 0; }
-		if (hipHostMalloc(&p, n * sizeof(T), hipHostMallocDefault) != hipSuccess) return -1;
-		cap = n;
-		return 0;
-	}
-	void release() { if (p) (void) hipHostFree(p); p = nullptr; cap = 0; }
-};
-
-}  // namespace ngm
+#include "device_mem.h"
 
 struct ngm_hip_ctx {
 	int device = 0;

@@ -30,6 +30,7 @@ namespace {
 int upload_reads(ngm_mapper *m, int n, const char *reads) {
 	const size_t bytes = (size_t) n * m->prm.qry_max_len;
 	if (m->d_reads.reserve(bytes)) { ngm::pipeline_set_error("out of device memory (reads)"); return -12; }
+	m->batch_reads = m->d_reads.p;
 	MAP_HIP_TRY(hipMemcpyAsync(m->d_reads.p, reads, bytes, hipMemcpyHostToDevice, m->st));
 	return 0;
 }
@@ -79,7 +80,7 @@ int score_candidates(ngm_mapper *m, int n, uint64_t np, int alt_dir) {
 	hipLaunchKernelGGL(ngm::expand_pairs_kernel, dim3((n + 255) / 256), dim3(256), 0, m->st, n, m->d_cand_base.p, m->d_cand_count.p, m->d_pair_read.p);
 	const int nb = (int) ((np + ngm::kSlots - 1) / ngm::kSlots);
 	ngm::WindowGeom Gs{r->n_bases - 1, ((q + c) | 1) + 1, c >> 1};  // refMaxLen of ScoreBuffer.h:112
-	hipLaunchKernelGGL(ngm::gather_pairs_kernel, dim3(nb), dim3(256), 0, m->st, m->d_reads.p, m->d_read_len.p, q, r->d_genome, Gs,
+	hipLaunchKernelGGL(ngm::gather_pairs_kernel, dim3(nb), dim3(256), 0, m->st, m->batch_reads, m->d_read_len.p, q, r->d_genome.p, Gs,
 			m->d_pair_read.p, m->d_out_loc.p, m->d_out_sv.p, (int) np, eng->RW, eng->FW, eng->packed.p, eng->lens.p, eng->blk_rows.p, alt_dir);
 	MAP_HIP_TRY(hipGetLastError());
 	MAP_HIP_TRY(hipEventRecord(m->ev[2], m->st));
@@ -167,8 +168,8 @@ int begin(MapBatch &b) {
 	for (auto &x : m->ms) x = 0.f;
 	m->order_ms = 0.f;
 
-	// reads already in HBM: alias them as the batch (no copy); otherwise upload
-	if (d_reads_ext) { m->d_reads.p = (uint8_t *) d_reads_ext; m->d_reads.cap = (size_t) n * q; }
+	// reads already in HBM: the stages read them where they are (no copy); otherwise upload
+	if (d_reads_ext) m->batch_reads = (const uint8_t *) d_reads_ext;
 	b.host_timing = getenv("NGM_HIP_HOST_TIMING") != nullptr;
 	b.alt_cigar = m->prm.bs_mapping ? NGM_ALT_BISULFITE : (m->prm.slam_seq ? NGM_ALT_SLAMSEQ : NGM_ALT_NONE);
 	b.alt_dir = b.alt_cigar ? (paired ? 2 : 1) : 0;   // the pairs' direction bits (gather_pairs_kernel): score tables, conversion rule
@@ -381,8 +382,8 @@ int align(MapBatch &b) {
 		stage_align.acquire();
 		MAP_HIP_TRY(hipEventRecord(m->ev[5], m->st));
 		ngm::WindowGeom Ga{r->n_bases - 1, align_buf_len, c >> 1};
-		hipLaunchKernelGGL(ngm::gather_pairs_kernel, dim3((na + ngm::kSlots - 1) / ngm::kSlots), dim3(256), 0, m->st, m->d_reads.p, m->d_read_len.p, q,
-				r->d_genome, Ga, m->d_a_read.p, m->d_a_loc.p, m->d_a_sv.p, na, eng->RW, eng->FW, eng->packed.p, eng->lens.p, eng->blk_rows.p, alt_dir);
+		hipLaunchKernelGGL(ngm::gather_pairs_kernel, dim3((na + ngm::kSlots - 1) / ngm::kSlots), dim3(256), 0, m->st, m->batch_reads, m->d_read_len.p, q,
+				r->d_genome.p, Ga, m->d_a_read.p, m->d_a_loc.p, m->d_a_sv.p, na, eng->RW, eng->FW, eng->packed.p, eng->lens.p, eng->blk_rows.p, alt_dir);
 		MAP_HIP_TRY(hipGetLastError());
 		MAP_HIP_TRY(hipEventRecord(m->ev[6], m->st));
 		const bool was_prof = eng->profiling;
@@ -609,24 +610,24 @@ int ngm_ref_decode(const ngm_ref *r, uint64_t offset, int buffer_len, char *out)
 	// reuse the gather kernel: one pair, read of length 0, corridor 0, q = buffer_len rounded up
 	const int q = 8, c = buffer_len;  // window = q + c >= buffer_len bytes
 	const int RW = ngm::read_words(q), FW = (q + c + 7) / 8 + 1;
-	uint32_t *d_out; uint16_t *d_lens, *d_rows, *d_rl; uint8_t *d_reads; uint32_t *d_pr, *d_pl, *d_ps;
-	MAP_HIP_TRY(hipMalloc(&d_out, (size_t) (RW + FW) * 64 * 4)); MAP_HIP_TRY(hipMalloc(&d_lens, 128)); MAP_HIP_TRY(hipMalloc(&d_rows, 8));
-	MAP_HIP_TRY(hipMalloc(&d_rl, 8)); MAP_HIP_TRY(hipMalloc(&d_reads, q)); MAP_HIP_TRY(hipMalloc(&d_pr, 4)); MAP_HIP_TRY(hipMalloc(&d_pl, 4)); MAP_HIP_TRY(hipMalloc(&d_ps, 4));
-	MAP_HIP_TRY(hipMemset(d_rl, 0, 8)); MAP_HIP_TRY(hipMemset(d_reads, 0, q)); MAP_HIP_TRY(hipMemset(d_pr, 0, 4)); MAP_HIP_TRY(hipMemset(d_ps, 0, 4));
+	ngm::Buf<uint32_t> d_out, d_pr, d_pl, d_ps;
+	ngm::Buf<uint16_t> d_lens, d_rows, d_rl;
+	ngm::Buf<uint8_t> d_reads;
+	NGM_MEM_TRY(d_out.alloc((size_t) (RW + FW) * 64) || d_lens.alloc(64) || d_rows.alloc(4) || d_rl.alloc(4) || d_reads.alloc(q) || d_pr.alloc(1) || d_pl.alloc(1) || d_ps.alloc(1));
+	MAP_HIP_TRY(hipMemset(d_rl.p, 0, 8)); MAP_HIP_TRY(hipMemset(d_reads.p, 0, q)); MAP_HIP_TRY(hipMemset(d_pr.p, 0, 4)); MAP_HIP_TRY(hipMemset(d_ps.p, 0, 4));
 	const uint32_t loc = (uint32_t) offset;
-	MAP_HIP_TRY(hipMemcpy(d_pl, &loc, 4, hipMemcpyHostToDevice));
+	MAP_HIP_TRY(hipMemcpy(d_pl.p, &loc, 4, hipMemcpyHostToDevice));
 	ngm::WindowGeom G{concat_len, buffer_len, 0};
-	hipLaunchKernelGGL(ngm::gather_pairs_kernel, dim3(1), dim3(256), 0, 0, d_reads, d_rl, q, r->d_genome, G, d_pr, d_pl, d_ps, 1, RW, FW, d_out, d_lens, d_rows);
+	hipLaunchKernelGGL(ngm::gather_pairs_kernel, dim3(1), dim3(256), 0, 0, d_reads.p, d_rl.p, q, r->d_genome.p, G, d_pr.p, d_pl.p, d_ps.p, 1, RW, FW, d_out.p, d_lens.p, d_rows.p);
 	MAP_HIP_TRY(hipGetLastError());
 	std::vector<uint32_t> h((size_t) (RW + FW) * 64);
-	MAP_HIP_TRY(hipMemcpy(h.data(), d_out, h.size() * 4, hipMemcpyDeviceToHost));
+	MAP_HIP_TRY(hipMemcpy(h.data(), d_out.p, h.size() * 4, hipMemcpyDeviceToHost));
 	for (int j = 0; j < buffer_len; ++j) {
 		const uint32_t w = h[(size_t) (RW + j / 8) * 64];
 		const int b = j & 7;
 		const uint32_t cls = (b < 4) ? (w >> (8 * b)) & 15u : (w >> (8 * (b - 4) + 4)) & 15u;
 		out[j] = class_char((uint8_t) cls);
 	}
-	(void) hipFree(d_out); (void) hipFree(d_lens); (void) hipFree(d_rows); (void) hipFree(d_rl); (void) hipFree(d_reads); (void) hipFree(d_pr); (void) hipFree(d_pl); (void) hipFree(d_ps);
 	return 1;
 }
 
@@ -700,21 +701,10 @@ void ngm_mapper_destroy(ngm_mapper *m) {
 	(void) hipStreamSynchronize(m->st);
 	ngm_bgzf_destroy(m->bz);
 	if (m->st_hi) { (void) hipStreamSynchronize(m->st_hi); (void) hipStreamDestroy(m->st_hi); }
-	ngm::cs_release(m);
-	ngm::argos_release(m);
-	m->d_reads.release(); m->d_scores.release(); m->d_best.release(); m->d_pair_read.release();
-	m->d_winner.release(); m->d_a_read.release(); m->d_a_loc.release(); m->d_a_sv.release(); m->d_mapq.release(); m->d_nbest.release();
-	m->d_records.release(); m->d_runs.release(); m->d_runs_c.release();
-	m->d_pair_info.release(); m->p_pair_info.release(); m->d_sam_contig_start.release();
-	m->d_pair_out.release(); m->d_pair_top.release(); m->d_pair_tied_n.release(); m->d_pair_list.release(); m->p_pair_out.release(); m->p_pair_top.release(); m->p_pair_tied_n.release();
-	m->d_sam_contig_names.release(); m->d_sam_rg.release(); m->d_sam_names.release(); m->d_sam_text.release(); m->d_sam_contig_off.release(); m->d_sam_len.release(); m->d_sam_off.release();
-	m->d_sam_quals.release(); m->d_sam_polya.release(); m->d_sam_meta.release(); m->d_sam_refs.release(); m->d_sam_hits.release(); m->p_sam_hits.release(); m->p_sam_refs.release(); m->p_sam_extra.release();
 	for (auto &e : m->ev) if (e) (void) hipEventDestroy(e);
 	for (auto &e : m->cev) if (e) (void) hipEventDestroy(e);
 	for (auto &e : m->oev) if (e) (void) hipEventDestroy(e);
-	m->p_winner.release(); m->p_loc.release(); m->p_sv.release(); m->p_mapq.release(); m->p_nbest.release(); m->p_rec.release();
-	m->p_best.release(); m->p_scores.release(); m->p_runs.release();
-	m->d_str.release(); m->d_cigout.release(); m->p_cigout.release(); m->p_str.release();
+	for (auto &e : m->aev) if (e) (void) hipEventDestroy(e);
 	ngm_hip_destroy(m->eng);
 	delete m;
 }
@@ -805,6 +795,14 @@ void *ngm_host_alloc(size_t bytes) {
 }
 void ngm_host_free(void *p) { if (p) (void) hipHostFree(p); }
 
+int ngm_debug_live_memory(uint64_t out[4]) {
+	if (!out) return -22;
+	const ngm::MemCount &d = ngm::DeviceMem::count, &h = ngm::PinnedMem::count;
+	out[0] = d.live.load(std::memory_order_relaxed); out[1] = h.live.load(std::memory_order_relaxed);
+	out[2] = d.calls.load(std::memory_order_relaxed); out[3] = h.calls.load(std::memory_order_relaxed);
+	return 0;
+}
+
 int ngm_host_pin_to_device_node(int device) {
 	char bdf[64] = {0};
 	if (hipDeviceGetPCIBusId(bdf, (int) sizeof(bdf), device) != hipSuccess) { ngm::pipeline_set_error("no PCI bus id for device %d", device); return -19; }
@@ -894,7 +892,6 @@ int ngm_debug_select_top1(int device, int n_reads, const uint32_t *base, const u
 	MAP_HIP_TRY(hipMemcpy(mapq, d_mq.p, (size_t) n_reads * 4, hipMemcpyDeviceToHost));
 	MAP_HIP_TRY(hipMemcpy(n_best, d_nb.p, (size_t) n_reads * 4, hipMemcpyDeviceToHost));
 	MAP_HIP_TRY(hipMemcpy(best_score, d_best.p, (size_t) n_reads * 4, hipMemcpyDeviceToHost));
-	d_base.release(); d_count.release(); d_loc.release(); d_sv.release(); d_win.release(); d_mq.release(); d_nb.release(); d_sc.release(); d_best.release();
 	return 0;
 }
 
@@ -902,20 +899,15 @@ int ngm_debug_expand_pairs(int device, int n_reads, const uint32_t *base, const 
 	if (n_reads <= 0 || !base || !count || (n_cand && !out)) return -22;
 	DevGuard g(device);
 	ngm::DevBuf<uint32_t> d_base, d_count, d_out;
-	auto run = [&]() -> int {
-		if (d_base.reserve(n_reads) || d_count.reserve(n_reads) || d_out.reserve((size_t) std::max<uint64_t>(n_cand, 1))) { ngm::pipeline_set_error("out of device memory (ngm_debug_expand_pairs)"); return -12; }
-		MAP_HIP_TRY(hipMemcpy(d_base.p, base, (size_t) n_reads * 4, hipMemcpyHostToDevice));
-		MAP_HIP_TRY(hipMemcpy(d_count.p, count, (size_t) n_reads * 4, hipMemcpyHostToDevice));
-		MAP_HIP_TRY(hipMemset(d_out.p, 0xFF, (size_t) std::max<uint64_t>(n_cand, 1) * 4));
-		hipLaunchKernelGGL(ngm::expand_pairs_kernel, dim3((n_reads + 255) / 256), dim3(256), 0, 0, n_reads, d_base.p, d_count.p, d_out.p);
-		MAP_HIP_TRY(hipGetLastError());
-		MAP_HIP_TRY(hipDeviceSynchronize());
-		if (n_cand) MAP_HIP_TRY(hipMemcpy(out, d_out.p, (size_t) n_cand * 4, hipMemcpyDeviceToHost));
-		return 0;
-	};
-	const int rc = run();
-	d_base.release(); d_count.release(); d_out.release();
-	return rc;
+	if (d_base.reserve(n_reads) || d_count.reserve(n_reads) || d_out.reserve((size_t) std::max<uint64_t>(n_cand, 1))) { ngm::pipeline_set_error("out of device memory (ngm_debug_expand_pairs)"); return -12; }
+	MAP_HIP_TRY(hipMemcpy(d_base.p, base, (size_t) n_reads * 4, hipMemcpyHostToDevice));
+	MAP_HIP_TRY(hipMemcpy(d_count.p, count, (size_t) n_reads * 4, hipMemcpyHostToDevice));
+	MAP_HIP_TRY(hipMemset(d_out.p, 0xFF, (size_t) std::max<uint64_t>(n_cand, 1) * 4));
+	hipLaunchKernelGGL(ngm::expand_pairs_kernel, dim3((n_reads + 255) / 256), dim3(256), 0, 0, n_reads, d_base.p, d_count.p, d_out.p);
+	MAP_HIP_TRY(hipGetLastError());
+	MAP_HIP_TRY(hipDeviceSynchronize());
+	if (n_cand) MAP_HIP_TRY(hipMemcpy(out, d_out.p, (size_t) n_cand * 4, hipMemcpyDeviceToHost));
+	return 0;
 }
 
 int ngm_debug_pair_select(int device, int n_pairs, const uint32_t *base, const uint32_t *count, uint64_t n_cand, const float *scores, const uint32_t *loc,
@@ -930,39 +922,33 @@ int ngm_debug_pair_select(int device, int n_pairs, const uint32_t *base, const u
 	ngm::DevBuf<int32_t> d_mq, d_nb, d_info;
 	ngm::DevBuf<ngm::PairOut> d_out;
 	ngm::DevBuf<ngm::PairTop> d_top;
-	auto run = [&]() -> int {
-		if (d_base.reserve(n) || d_count.reserve(n) || d_len.reserve(n) || d_loc.reserve(nc) || d_sc.reserve(nc) || d_mq.reserve(n) || d_nb.reserve(n) || d_info.reserve(npairs + 1) ||
-				d_tied_n.reserve(4) || d_list.reserve(3 * npairs + 2) || d_out.reserve(2 * npairs + 2) || d_top.reserve(npairs + 1)) {
-			ngm::pipeline_set_error("out of device memory (ngm_debug_pair_select)"); return -12; }
-		MAP_HIP_TRY(hipMemcpy(d_base.p, base, n * 4, hipMemcpyHostToDevice));
-		MAP_HIP_TRY(hipMemcpy(d_count.p, count, n * 4, hipMemcpyHostToDevice));
-		MAP_HIP_TRY(hipMemcpy(d_len.p, read_len, n * 2, hipMemcpyHostToDevice));
-		MAP_HIP_TRY(hipMemcpy(d_mq.p, mapq, n * 4, hipMemcpyHostToDevice));
-		MAP_HIP_TRY(hipMemcpy(d_nb.p, n_best, n * 4, hipMemcpyHostToDevice));
-		if (n_cand) {
-			MAP_HIP_TRY(hipMemcpy(d_sc.p, scores, (size_t) n_cand * 4, hipMemcpyHostToDevice));
-			MAP_HIP_TRY(hipMemcpy(d_loc.p, loc, (size_t) n_cand * 4, hipMemcpyHostToDevice));
-		}
-		// (what no kernel writes reads as -1 everywhere: an entry's `pair` field tells whether it was written)
-		MAP_HIP_TRY(hipMemset(d_info.p, 0xFF, (npairs + 1) * 4));
-		MAP_HIP_TRY(hipMemset(d_out.p, 0xFF, (2 * npairs + 2) * sizeof(ngm::PairOut)));
-		MAP_HIP_TRY(hipMemset(d_top.p, 0xFF, (npairs + 1) * sizeof(ngm::PairTop)));
-		MAP_HIP_TRY(hipDeviceSynchronize());
-		if (int rc = launch_pair_select(0, npairs, d_base.p, d_count.p, d_sc.p, d_loc.p, d_len.p, min_insert, max_insert, cutoff, d_mq.p, d_nb.p, d_info.p, true,
-				d_tied_n.p, d_list.p, d_out.p, d_top.p)) return rc;
-		MAP_HIP_TRY(hipDeviceSynchronize());
-		MAP_HIP_TRY(hipMemcpy(info, d_info.p, npairs * 4, hipMemcpyDeviceToHost));
-		MAP_HIP_TRY(hipMemcpy(mapq, d_mq.p, n * 4, hipMemcpyDeviceToHost));
-		MAP_HIP_TRY(hipMemcpy(n_best, d_nb.p, n * 4, hipMemcpyDeviceToHost));
-		MAP_HIP_TRY(hipMemcpy(counts, d_tied_n.p, 16, hipMemcpyDeviceToHost));
-		MAP_HIP_TRY(hipMemcpy(entries, d_out.p, (2 * npairs + 2) * sizeof(ngm::PairOut), hipMemcpyDeviceToHost));
-		MAP_HIP_TRY(hipMemcpy(tops, d_top.p, (npairs + 1) * sizeof(ngm::PairTop), hipMemcpyDeviceToHost));
-		return 0;
-	};
-	const int rc = run();
-	d_base.release(); d_count.release(); d_loc.release(); d_tied_n.release(); d_list.release(); d_len.release(); d_sc.release(); d_mq.release(); d_nb.release(); d_info.release();
-	d_out.release(); d_top.release();
-	return rc;
+	if (d_base.reserve(n) || d_count.reserve(n) || d_len.reserve(n) || d_loc.reserve(nc) || d_sc.reserve(nc) || d_mq.reserve(n) || d_nb.reserve(n) || d_info.reserve(npairs + 1) ||
+			d_tied_n.reserve(4) || d_list.reserve(3 * npairs + 2) || d_out.reserve(2 * npairs + 2) || d_top.reserve(npairs + 1)) {
+		ngm::pipeline_set_error("out of device memory (ngm_debug_pair_select)"); return -12; }
+	MAP_HIP_TRY(hipMemcpy(d_base.p, base, n * 4, hipMemcpyHostToDevice));
+	MAP_HIP_TRY(hipMemcpy(d_count.p, count, n * 4, hipMemcpyHostToDevice));
+	MAP_HIP_TRY(hipMemcpy(d_len.p, read_len, n * 2, hipMemcpyHostToDevice));
+	MAP_HIP_TRY(hipMemcpy(d_mq.p, mapq, n * 4, hipMemcpyHostToDevice));
+	MAP_HIP_TRY(hipMemcpy(d_nb.p, n_best, n * 4, hipMemcpyHostToDevice));
+	if (n_cand) {
+		MAP_HIP_TRY(hipMemcpy(d_sc.p, scores, (size_t) n_cand * 4, hipMemcpyHostToDevice));
+		MAP_HIP_TRY(hipMemcpy(d_loc.p, loc, (size_t) n_cand * 4, hipMemcpyHostToDevice));
+	}
+	// (what no kernel writes reads as -1 everywhere: an entry's `pair` field tells whether it was written)
+	MAP_HIP_TRY(hipMemset(d_info.p, 0xFF, (npairs + 1) * 4));
+	MAP_HIP_TRY(hipMemset(d_out.p, 0xFF, (2 * npairs + 2) * sizeof(ngm::PairOut)));
+	MAP_HIP_TRY(hipMemset(d_top.p, 0xFF, (npairs + 1) * sizeof(ngm::PairTop)));
+	MAP_HIP_TRY(hipDeviceSynchronize());
+	if (int rc = launch_pair_select(0, npairs, d_base.p, d_count.p, d_sc.p, d_loc.p, d_len.p, min_insert, max_insert, cutoff, d_mq.p, d_nb.p, d_info.p, true,
+			d_tied_n.p, d_list.p, d_out.p, d_top.p)) return rc;
+	MAP_HIP_TRY(hipDeviceSynchronize());
+	MAP_HIP_TRY(hipMemcpy(info, d_info.p, npairs * 4, hipMemcpyDeviceToHost));
+	MAP_HIP_TRY(hipMemcpy(mapq, d_mq.p, n * 4, hipMemcpyDeviceToHost));
+	MAP_HIP_TRY(hipMemcpy(n_best, d_nb.p, n * 4, hipMemcpyDeviceToHost));
+	MAP_HIP_TRY(hipMemcpy(counts, d_tied_n.p, 16, hipMemcpyDeviceToHost));
+	MAP_HIP_TRY(hipMemcpy(entries, d_out.p, (2 * npairs + 2) * sizeof(ngm::PairOut), hipMemcpyDeviceToHost));
+	MAP_HIP_TRY(hipMemcpy(tops, d_top.p, (npairs + 1) * sizeof(ngm::PairTop), hipMemcpyDeviceToHost));
+	return 0;
 }
 
 int ngm_mapper_heavy_counters(ngm_mapper *m, uint64_t out[4]) {

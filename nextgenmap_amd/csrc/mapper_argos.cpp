@@ -9,15 +9,6 @@
 using ngm::DevGuard;
 using ngm::GpuStage;
 
-namespace ngm {
-void argos_release(ngm_mapper *m) {
-	m->d_argos_starts.release(); m->d_argos_loff.release(); m->d_argos_gkeys.release(); m->d_argos_ord.release(); m->d_argos_nsurv.release();
-	m->d_argos_npos.release(); m->d_argos_list.release(); m->d_argos_llist.release(); m->d_argos_gvals.release(); m->d_argos_hord.release();
-	m->d_argos_hoff.release(); m->d_argos_cls.release(); m->d_argos_ctr.release(); m->p_argos_cls.release(); m->p_argos_nsurv.release();
-	for (auto &e : m->aev) if (e) { (void) hipEventDestroy(e); e = nullptr; }
-}
-}  // namespace ngm
-
 namespace {
 inline uint64_t pow2_at_least(uint32_t v) { uint64_t p = 1; while (p < v) p <<= 1; return p; }
 
@@ -91,6 +82,7 @@ long long ngm_mapper_map_argos(ngm_mapper *m, int n, const char *reads, const ch
 			m->d_argos_npos.reserve(n) || m->d_argos_cls.reserve(n) || m->p_argos_cls.reserve(n) || m->p_argos_nsurv.reserve(n) ||
 			m->d_sam_len.reserve((size_t) n + 1) || m->d_sam_off.reserve((size_t) n + 1) || m->d_argos_ctr.reserve(4)) {
 		ngm::pipeline_set_error("out of memory (argos)"); return -12; }
+	m->batch_reads = m->d_reads.p;
 	MAP_HIP_TRY(hipEventRecord(m->ev[0], m->st));
 	MAP_HIP_TRY(hipMemcpyAsync(m->d_reads.p, reads, (size_t) n * q, hipMemcpyHostToDevice, m->st));
 	if (names_bytes) MAP_HIP_TRY(hipMemcpyAsync(m->d_sam_names.p, names, names_bytes, hipMemcpyHostToDevice, m->st));

@@ -108,6 +108,7 @@ struct ngm_mapper {
 	ngm::PinnedBuf<uint16_t> p_runs;
 	// batch state in HBM
 	ngm::DevBuf<uint8_t> d_reads;
+	const uint8_t *batch_reads = nullptr;   // the reads of the batch in flight, where the stages read them: d_reads.p, or the caller's device rows (the *_resident entry points) -- not owned
 	ngm::DevBuf<uint16_t> d_read_len;
 	ngm::DevBuf<uint32_t> d_cand_base, d_cand_count, d_out_loc, d_out_sv, d_status, d_ovf_read, d_ovf_read2, d_ovf_hits, d_ovf_hits2, d_ovf_log2;
 	ngm::PinnedBuf<uint32_t> p_cs_status;   // what a search's one synchronisation waits for, as downloaded: status and control blocks (cs_queue_device.h), candidate count, counters
@@ -259,7 +260,7 @@ struct GpuStage {
 // ---- mapper_search.cpp ----------------------------------------------------------------------------------------------------------
 // fast-path geometry, kernel attributes (part of ngm_mapper_create)
 int cs_configure(ngm_mapper *m, const ngm_mapper_params *p);
-// candidate search for the reads already in m->d_reads; leaves per-read base/count/max votes and the candidate arrays in HBM (and
+// candidate search for the reads at m->batch_reads; leaves per-read base/count/max votes and the candidate arrays in HBM (and
 // base/count/max votes on the host)
 // defer_host_arrays: the per-read arrays are NOT enqueued (the search's synchronisation waits for the status / control blocks, the
 // counters and the candidate count only); the caller enqueues them later with cs_enqueue_host_arrays, or cs_host_arrays does
@@ -271,12 +272,10 @@ int cs_host_arrays(ngm_mapper *m);           // returns when h_base / h_count / 
 // wait = false: only enqueue (the list must stay alive until candidate_order_wait)
 int candidate_order(ngm_mapper *m, const std::vector<uint32_t> &list, uint64_t np, uint32_t **h_rank, bool wait = true);
 int candidate_order_wait(ngm_mapper *m, uint32_t **h_rank);
-void cs_release(ngm_mapper *m);   // the search side's buffers (ngm_mapper_destroy)
 long test_limit(const char *key, long dflt);   // NGM_HIP_TEST_LIMITS (mapper_search.cpp)
 
 // ---- mapper.cpp / mapper_argos.cpp ---------------------------------------------------------------------------------------------------
 int score_candidates(ngm_mapper *m, int n, uint64_t np, int alt_dir);   // window gather + BatchScore of the batch's candidates into d_scores
-void argos_release(ngm_mapper *m);   // the --argos buffers (ngm_mapper_destroy)
 
 // per-read host loops run on the process-wide persistent pool (thread_pool.h): shared by the mapper instances, sized
 // to this rank's share of the host cores; no threads are started per call
@@ -313,14 +312,12 @@ struct PairTurn {
 };
 
 // What the stages of one map call share.  A local of map_impl: the members with a destructor are its scope objects -- the paired-end
-// turn is passed on, the mapper's own read buffer put back and the search + score turn given up on every return.
+// turn is passed on and the search + score turn given up on every return.
 struct MapBatch {
 	ngm_mapper *m; int n; const char *reads; const void *d_reads_ext; ngm_hit *hits; char *cigars, *mds; bool paired; SamCall *sam;
-	// (these three are built before the argument checks and the device guard of map_impl and go after that guard: their constructors
-	// and destructors must stay free of HIP calls -- a mutex, a condition variable, a pointer put back -- and keep this order)
+	// (these two are built before the argument checks and the device guard of map_impl and go after that guard: their constructors
+	// and destructors must stay free of HIP calls -- a mutex, a condition variable -- and keep this order)
 	PairTurn pair_turn;
-	// reads already in HBM are aliased as the batch (begin); the mapper's own buffer comes back when the call ends
-	struct Restore { ngm_mapper *m; ngm::DevBuf<uint8_t> own; bool on; ~Restore() { if (on) m->d_reads = own; } } restore;
 	GpuStage stage_cs;   // the turn begins at the search's first enqueue (run_cs takes it) and ends in the select stage
 	int q = 0, c = 0, topn = 1, alt_cigar = 0, alt_dir = 0;
 	size_t str_stride = 0;
@@ -347,7 +344,7 @@ struct MapBatch {
 	void lap(int k) { auto t = std::chrono::steady_clock::now(); t_stage[k] += std::chrono::duration<double, std::milli>(t - tp0).count(); tp0 = t; }
 	MapBatch(ngm_mapper *m_, int n_, const char *reads_, const void *d_reads_ext_, ngm_hit *hits_, char *cigars_, char *mds_, bool paired_, SamCall *sam_)
 		: m(m_), n(n_), reads(reads_), d_reads_ext(d_reads_ext_), hits(hits_), cigars(cigars_), mds(mds_), paired(paired_), sam(sam_),
-		  pair_turn{m_, paired_ && m_->ps != nullptr}, restore{m_, m_->d_reads, d_reads_ext_ != nullptr}, stage_cs(m_, 0, false) {}
+		  pair_turn{m_, paired_ && m_->ps != nullptr}, stage_cs(m_, 0, false) {}
 };
 int select(MapBatch &b);      // mapper_select.cpp: from behind the score stage's synchronisation to the end of the search + score turn
 int write_sam(MapBatch &b);   // mapper_sam.cpp: the batch's records as SAM / BAM text, side outputs, sorter and BGZF routes

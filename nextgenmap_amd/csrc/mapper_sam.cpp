@@ -42,7 +42,7 @@ int side_outputs_away(ngm_mapper *m, bool cov_away, bool snp_away, bool count_aw
 		// round for a pair's second mate) -- the records with a quality string and those without one in
 		// a call each
 		m->snp_rows.resize((size_t) n * q);
-		MAP_HIP_TRY(hipMemcpy(m->snp_rows.data(), m->d_reads.p, (size_t) n * q, hipMemcpyDeviceToHost));
+		MAP_HIP_TRY(hipMemcpy(m->snp_rows.data(), m->batch_reads, (size_t) n * q, hipMemcpyDeviceToHost));
 		const ngm::SamMeta *meta = (const ngm::SamMeta *) sam->meta;
 		const uint8_t *quals = (const uint8_t *) sam->quals;
 		const int per = paired ? 2 : 1;
@@ -96,8 +96,7 @@ int append_host_strings(MapBatch &b) {
 		MAP_OOM_TRY(bigger.reserve(need + 4096), "out of device memory (SAM strings)");
 		if (str_base) MAP_HIP_TRY(hipMemcpyAsync(bigger.p, m->d_str.p, (size_t) str_base, hipMemcpyDeviceToDevice, m->st));
 		MAP_HIP_TRY(hipStreamSynchronize(m->st));
-		std::swap(bigger, m->d_str);
-		bigger.release();
+		std::swap(bigger, m->d_str);   // (the smaller one goes with `bigger`, here)
 	}
 	MAP_OOM_TRY(m->p_sam_extra.reserve(extra.size()), "out of pinned host memory");
 	memcpy(m->p_sam_extra.p, extra.data(), extra.size());
@@ -114,14 +113,14 @@ ngm::SamArgs sam_args(const MapBatch &b) {
 	ngm::SamArgs S{};
 	S.n = n; S.q = q; S.paired = paired ? 1 : 0;
 	S.unit_len_bound = (uint32_t) ((paired ? 2 : 1) * (2 * q + 1024));
-	S.reads = m->d_reads.p; S.quals = m->d_sam_quals.p; S.names = m->d_sam_names.p; S.meta = m->d_sam_meta.p; S.hits = m->d_sam_hits.p; S.refs = m->d_sam_refs.p;
+	S.reads = m->batch_reads; S.quals = m->d_sam_quals.p; S.names = m->d_sam_names.p; S.meta = m->d_sam_meta.p; S.hits = m->d_sam_hits.p; S.refs = m->d_sam_refs.p;
 	S.str = m->d_str.p; S.contig_names = m->d_sam_contig_names.p; S.contig_name_off = m->d_sam_contig_off.p;
 	S.min_insert = m->sam_opt.min_insert_size; S.max_insert = m->sam_opt.max_insert_size > 0 ? m->sam_opt.max_insert_size : 2147483647;
 	S.min_mq = m->sam_opt.min_mq; S.no_unal = m->sam_opt.no_unal; S.hard_clip = m->prm.hard_clip; S.silent_clip = m->prm.silent_clip;
 	S.min_identity = m->sam_opt.min_identity; S.min_residues = m->sam_opt.min_residues;
 	S.rg = m->sam_rg.empty() ? nullptr : m->d_sam_rg.p; S.rg_len = (int) m->sam_rg.size(); S.bs_mapping = m->sam_opt.bs_mapping;
 	S.slam_seq = m->sam_opt.slam_seq; S.variant_cpu = m->prm.variant == NGM_VARIANT_OCL_CPU ? 1 : 0; S.alt_scoring = (m->prm.bs_mapping || (m->prm.slam_seq & 2)) ? 1 : 0;
-	S.genome = r->d_genome; S.contig_start = m->d_sam_contig_start.p;
+	S.genome = r->d_genome.p; S.contig_start = m->d_sam_contig_start.p;
 	S.unit_len = m->d_sam_len.p; S.unit_off = m->d_sam_off.p; S.counters = m->d_total.p + 16;
 	S.bam = m->sam_opt.bam ? 1 : 0;
 	S.polya = sam->polya ? m->d_sam_polya.p : nullptr;
@@ -353,7 +352,7 @@ long long ngm_debug_sam_records(int device, const ngm_sam_options *opt, int hard
 	}
 	cname_off[n_contigs] = (uint32_t) cnames.size();
 	if (opt->slam_seq) {   // the tags read the packed genome: the reference's contigs are the table's
-		if (!ref || ref->device != device || !ref->d_genome || (int) ref->contigs.size() != n_contigs) { ngm::pipeline_set_error("%s: slam_seq needs a reference on device %d whose contigs are the table's", fn, device); return -22; }
+		if (!ref || ref->device != device || !ref->d_genome.p || (int) ref->contigs.size() != n_contigs) { ngm::pipeline_set_error("%s: slam_seq needs a reference on device %d whose contigs are the table's", fn, device); return -22; }
 		for (int c = 0; c < n_contigs; ++c) {
 			const NgmContig &rc = ref->contigs[c];
 			if (rc.name != contig_names[c] || rc.len != contig_lens[c] || rc.start + rc.len > ref->genome_words * 8ull) { ngm::pipeline_set_error("%s: contig %d differs from the reference's", fn, c); return -22; }
@@ -402,50 +401,44 @@ long long ngm_debug_sam_records(int device, const ngm_sam_options *opt, int hard
 	ngm::DevBuf<uint16_t> d_polya;
 	ngm::DevBuf<unsigned long long> d_ctr;
 	unsigned long long total = 0;
-	auto run = [&]() -> int {
-		if (d_reads.reserve(rows) || d_quals.reserve(rows) || d_names.reserve(names_bytes + 16) || d_str.reserve(str.size() + 16) || d_cnames.reserve(cnames.size() + 16) || d_rg.reserve(rg.size() + 16) ||
-				d_meta.reserve(nn) || d_hits.reserve(nn) || d_refs.reserve(nn) || d_coff.reserve(cname_off.size()) || d_cstart.reserve(cstart.size()) || d_polya.reserve(nn) ||
-				d_len.reserve((size_t) units + 1) || d_off.reserve((size_t) units + 1) || d_ctr.reserve(8)) { ngm::pipeline_set_error("out of device memory (%s)", fn); return -12; }
-		if (n) {
-			MAP_HIP_TRY(hipMemcpy(d_reads.p, reads, (size_t) n * q, hipMemcpyHostToDevice));
-			MAP_HIP_TRY(hipMemcpy(d_quals.p, quals, (size_t) n * q, hipMemcpyHostToDevice));
-			MAP_HIP_TRY(hipMemcpy(d_meta.p, meta, (size_t) n * sizeof(ngm::SamMeta), hipMemcpyHostToDevice));
-			MAP_HIP_TRY(hipMemcpy(d_hits.p, hits, (size_t) n * sizeof(ngm_hit), hipMemcpyHostToDevice));
-			MAP_HIP_TRY(hipMemcpy(d_refs.p, refs.data(), (size_t) n * sizeof(ngm::SamRef), hipMemcpyHostToDevice));
-			if (polya) MAP_HIP_TRY(hipMemcpy(d_polya.p, polya, (size_t) n * 2, hipMemcpyHostToDevice));
-		}
-		if (names_bytes) MAP_HIP_TRY(hipMemcpy(d_names.p, names, names_bytes, hipMemcpyHostToDevice));
-		if (!str.empty()) MAP_HIP_TRY(hipMemcpy(d_str.p, str.data(), str.size(), hipMemcpyHostToDevice));
-		if (!cnames.empty()) MAP_HIP_TRY(hipMemcpy(d_cnames.p, cnames.data(), cnames.size(), hipMemcpyHostToDevice));
-		if (!rg.empty()) MAP_HIP_TRY(hipMemcpy(d_rg.p, rg.data(), rg.size(), hipMemcpyHostToDevice));
-		MAP_HIP_TRY(hipMemcpy(d_coff.p, cname_off.data(), cname_off.size() * 4, hipMemcpyHostToDevice));
-		MAP_HIP_TRY(hipMemcpy(d_cstart.p, cstart.data(), cstart.size() * 8, hipMemcpyHostToDevice));
-		MAP_HIP_TRY(hipMemset(d_ctr.p, 0, 64));
-		MAP_HIP_TRY(hipDeviceSynchronize());
-		ngm::SamArgs S{};   // as sam_args fills it from a mapper
-		S.n = n; S.q = q; S.paired = opt->paired ? 1 : 0;
-		S.unit_len_bound = (uint32_t) ((opt->paired ? 2 : 1) * (2 * q + 1024));
-		S.reads = d_reads.p; S.quals = d_quals.p; S.names = d_names.p; S.meta = d_meta.p; S.hits = d_hits.p; S.refs = d_refs.p;
-		S.str = d_str.p; S.contig_names = d_cnames.p; S.contig_name_off = d_coff.p;
-		S.min_insert = opt->min_insert_size; S.max_insert = opt->max_insert_size > 0 ? opt->max_insert_size : 2147483647;
-		S.min_mq = opt->min_mq; S.no_unal = opt->no_unal; S.hard_clip = hard_clip; S.silent_clip = silent_clip;
-		S.min_identity = opt->min_identity; S.min_residues = opt->min_residues;
-		S.rg = rg.empty() ? nullptr : d_rg.p; S.rg_len = (int) rg.size(); S.bs_mapping = opt->bs_mapping;
-		S.slam_seq = opt->slam_seq; S.variant_cpu = variant == NGM_VARIANT_OCL_CPU ? 1 : 0; S.alt_scoring = alt_scoring ? 1 : 0;
-		S.genome = opt->slam_seq ? ref->d_genome : nullptr; S.contig_start = d_cstart.p;
-		S.unit_len = d_len.p; S.unit_off = d_off.p; S.counters = d_ctr.p;
-		S.bam = opt->bam ? 1 : 0;
-		S.polya = polya ? d_polya.p : nullptr;
-		if (units > 0) if (int rc = ngm::sam_text_kernels(S, units, ngm::SamScratch{d_len, d_off, d_scan_tmp, d_text}, 0, nullptr, fn, &total)) return rc;
-		MAP_HIP_TRY(hipDeviceSynchronize());
-		MAP_HIP_TRY(hipMemcpy(counters, d_ctr.p, 56, hipMemcpyDeviceToHost));
-		if (total && total <= out_cap) MAP_HIP_TRY(hipMemcpy(out, d_text.p, (size_t) total, hipMemcpyDeviceToHost));
-		return 0;
-	};
-	const int rc = run();
-	d_reads.release(); d_quals.release(); d_scan_tmp.release(); d_names.release(); d_str.release(); d_cnames.release(); d_rg.release(); d_text.release(); d_meta.release();
-	d_hits.release(); d_refs.release(); d_coff.release(); d_len.release(); d_off.release(); d_cstart.release(); d_polya.release(); d_ctr.release();
-	return rc < 0 ? (long long) rc : (long long) total;
+	if (d_reads.reserve(rows) || d_quals.reserve(rows) || d_names.reserve(names_bytes + 16) || d_str.reserve(str.size() + 16) || d_cnames.reserve(cnames.size() + 16) || d_rg.reserve(rg.size() + 16) ||
+			d_meta.reserve(nn) || d_hits.reserve(nn) || d_refs.reserve(nn) || d_coff.reserve(cname_off.size()) || d_cstart.reserve(cstart.size()) || d_polya.reserve(nn) ||
+			d_len.reserve((size_t) units + 1) || d_off.reserve((size_t) units + 1) || d_ctr.reserve(8)) { ngm::pipeline_set_error("out of device memory (%s)", fn); return -12; }
+	if (n) {
+		MAP_HIP_TRY(hipMemcpy(d_reads.p, reads, (size_t) n * q, hipMemcpyHostToDevice));
+		MAP_HIP_TRY(hipMemcpy(d_quals.p, quals, (size_t) n * q, hipMemcpyHostToDevice));
+		MAP_HIP_TRY(hipMemcpy(d_meta.p, meta, (size_t) n * sizeof(ngm::SamMeta), hipMemcpyHostToDevice));
+		MAP_HIP_TRY(hipMemcpy(d_hits.p, hits, (size_t) n * sizeof(ngm_hit), hipMemcpyHostToDevice));
+		MAP_HIP_TRY(hipMemcpy(d_refs.p, refs.data(), (size_t) n * sizeof(ngm::SamRef), hipMemcpyHostToDevice));
+		if (polya) MAP_HIP_TRY(hipMemcpy(d_polya.p, polya, (size_t) n * 2, hipMemcpyHostToDevice));
+	}
+	if (names_bytes) MAP_HIP_TRY(hipMemcpy(d_names.p, names, names_bytes, hipMemcpyHostToDevice));
+	if (!str.empty()) MAP_HIP_TRY(hipMemcpy(d_str.p, str.data(), str.size(), hipMemcpyHostToDevice));
+	if (!cnames.empty()) MAP_HIP_TRY(hipMemcpy(d_cnames.p, cnames.data(), cnames.size(), hipMemcpyHostToDevice));
+	if (!rg.empty()) MAP_HIP_TRY(hipMemcpy(d_rg.p, rg.data(), rg.size(), hipMemcpyHostToDevice));
+	MAP_HIP_TRY(hipMemcpy(d_coff.p, cname_off.data(), cname_off.size() * 4, hipMemcpyHostToDevice));
+	MAP_HIP_TRY(hipMemcpy(d_cstart.p, cstart.data(), cstart.size() * 8, hipMemcpyHostToDevice));
+	MAP_HIP_TRY(hipMemset(d_ctr.p, 0, 64));
+	MAP_HIP_TRY(hipDeviceSynchronize());
+	ngm::SamArgs S{};   // as sam_args fills it from a mapper
+	S.n = n; S.q = q; S.paired = opt->paired ? 1 : 0;
+	S.unit_len_bound = (uint32_t) ((opt->paired ? 2 : 1) * (2 * q + 1024));
+	S.reads = d_reads.p; S.quals = d_quals.p; S.names = d_names.p; S.meta = d_meta.p; S.hits = d_hits.p; S.refs = d_refs.p;
+	S.str = d_str.p; S.contig_names = d_cnames.p; S.contig_name_off = d_coff.p;
+	S.min_insert = opt->min_insert_size; S.max_insert = opt->max_insert_size > 0 ? opt->max_insert_size : 2147483647;
+	S.min_mq = opt->min_mq; S.no_unal = opt->no_unal; S.hard_clip = hard_clip; S.silent_clip = silent_clip;
+	S.min_identity = opt->min_identity; S.min_residues = opt->min_residues;
+	S.rg = rg.empty() ? nullptr : d_rg.p; S.rg_len = (int) rg.size(); S.bs_mapping = opt->bs_mapping;
+	S.slam_seq = opt->slam_seq; S.variant_cpu = variant == NGM_VARIANT_OCL_CPU ? 1 : 0; S.alt_scoring = alt_scoring ? 1 : 0;
+	S.genome = opt->slam_seq ? ref->d_genome.p : nullptr; S.contig_start = d_cstart.p;
+	S.unit_len = d_len.p; S.unit_off = d_off.p; S.counters = d_ctr.p;
+	S.bam = opt->bam ? 1 : 0;
+	S.polya = polya ? d_polya.p : nullptr;
+	if (units > 0) if (int rc = ngm::sam_text_kernels(S, units, ngm::SamScratch{d_len, d_off, d_scan_tmp, d_text}, 0, nullptr, fn, &total)) return rc;
+	MAP_HIP_TRY(hipDeviceSynchronize());
+	MAP_HIP_TRY(hipMemcpy(counters, d_ctr.p, 56, hipMemcpyDeviceToHost));
+	if (total && total <= out_cap) MAP_HIP_TRY(hipMemcpy(out, d_text.p, (size_t) total, hipMemcpyDeviceToHost));
+	return (long long) total;
 }
 
 }  // extern "C"

@@ -203,16 +203,7 @@ int cs_configure(ngm_mapper *m, const ngm_mapper_params *p) {
 	return 0;
 }
 
-void cs_release(ngm_mapper *m) {
-	m->d_read_len.release(); m->d_cand_base.release(); m->d_cand_count.release(); m->d_out_loc.release(); m->d_out_sv.release();
-	m->d_status.release(); m->d_ovf_read.release(); m->d_ovf_read2.release(); m->d_ovf_hits.release(); m->d_ovf_hits2.release(); m->d_ovf_log2.release(); m->d_ovf_off.release(); m->d_gt_keys.release();
-	m->d_gt_votes.release(); m->d_heavy_list.release(); m->d_heavy_ctr.release(); m->d_max_votes.release(); m->d_max_both.release(); m->d_total.release();
-	m->d_counters.release(); m->d_heavy_diag.release(); m->d_order_list.release(); m->d_cand_rank.release(); m->d_order_scratch.release(); m->d_order_info.release(); m->p_order_info.release();
-	m->d_order_big.release(); m->d_order_gt.release(); m->d_order_log2.release(); m->d_order_off.release(); m->p_rank.release(); m->h_base.b.release(); m->h_count.b.release(); m->h_maxv.b.release();
-	m->d_out_loc2.release(); m->d_out_sv2.release(); m->d_new_base.release(); m->d_scan_tmp.release(); m->p_cs_status.release();
-}
-
-// candidate search for the reads already in m->d_reads; leaves per-read base/count/max votes and the
+// candidate search for the reads at m->batch_reads; leaves per-read base/count/max votes and the
 // candidate arrays in HBM (and base/count/max votes on the host)
 int run_cs(ngm_mapper *m, int n, GpuStage *stage, bool defer_host_arrays) {
 	const ngm_ref *r = m->ref;
@@ -252,9 +243,9 @@ int run_cs(ngm_mapper *m, int n, GpuStage *stage, bool defer_host_arrays) {
 				m->d_counters.p, (int) (ctr_words + 32), m->d_heavy_ctr.p, (int) kCsqWords, m->d_cand_count.p, n);
 		MAP_HIP_TRY(hipGetLastError());
 		CsArgs A{};
-		A.reads = m->d_reads.p; A.n = n; A.q = q; A.k = r->prm.kmer; A.bin_shift = r->prm.bin_size;
+		A.reads = m->batch_reads; A.n = n; A.q = q; A.k = r->prm.kmer; A.bin_shift = r->prm.bin_size;
 		A.max_kfreq = m->max_kfreq; A.sensitivity = m->prm.sensitivity; A.kmer_min = m->prm.kmer_min; A.max_cmrs = m->prm.max_cmrs;
-		A.index = r->d_index; A.positions = r->d_positions;
+		A.index = r->d_index.p; A.positions = r->d_positions.p;
 		A.lists_cap = 2 * std::max(1, q - r->prm.kmer + 1);
 		A.read_len = m->d_read_len.p; A.cand_base = m->d_cand_base.p; A.cand_count = m->d_cand_count.p; A.max_votes = m->d_max_votes.p; A.max_both = m->d_max_both.p;
 		A.out_loc = m->d_out_loc.p; A.out_sv = m->d_out_sv.p; A.out_total = m->d_total.p; A.out_capacity = cap / kCsRegions;
@@ -320,7 +311,7 @@ int run_cs(ngm_mapper *m, int n, GpuStage *stage, bool defer_host_arrays) {
 		A.bs = bs ? 1 : 0; A.bs_cutoff = m->prm.bs_cutoff; A.bs_read_skip = std::max(0, m->prm.bs_read_skip); A.bs_paired = m->cs_paired ? 1 : 0;
 		if (bs) A.lists_cap = 2 * kCsBsChunk;  // the exact kernels hold the lists of kCsBsChunk k-mer variants at a time
 		A.log2_bits = m->cs_log2_bits; A.plane_bits = m->cs_plane_bits; A.log2_slots = m->cs_log2_small; A.fast_items = m->cs_fast_items;
-		A.buckets = r->d_buckets; A.bucket_log2_words = r->bucket_log2_words; A.pos_base = r->bucket_pos_base;
+		A.buckets = r->d_buckets.p; A.bucket_log2_words = r->bucket_log2_words; A.pos_base = r->bucket_pos_base;
 		A.hit_cap = m->cs_plane_bits / 6u;
 		if (A.bin_shift < 2) A.hit_cap = 0;  // the register encoding of the fast path keeps bins in 30 bits
 		MAP_HIP_TRY(hipEventRecord(m->cev[0], m->st));
@@ -419,7 +410,7 @@ int run_cs(ngm_mapper *m, int n, GpuStage *stage, bool defer_host_arrays) {
 			A.items16 = (A.lists_cap <= 512 && m->max_kfreq <= 128 * kCsSeg) ? 1 : 0;
 			if (!A.items16) A.fast_items = kCsFastItemsLong;  // the 32-bit item list only exists in the large size
 			if (m->cs_canon) {
-				A.buckets = r->d_cbuckets; A.bucket_log2_words = r->cbucket_log2_words; A.pos_base = r->cbucket_pos_base;
+				A.buckets = r->d_cbuckets.p; A.bucket_log2_words = r->cbucket_log2_words; A.pos_base = r->cbucket_pos_base;
 				const size_t lds = cs_canon_lds_bytes(A, m->cs_canon) - 96;  // (the kernel has no static LDS: its shared variables are the last 160 bytes of this)
 				// persistent workgroups: as many as the GPU holds at once, each walking the reads with that stride
 				const void *fn = cs_canon_fn(m->cs_canon, A.bin_shift);
@@ -650,7 +641,7 @@ int candidate_order_finish(ngm_mapper *m, hipStream_t ost, uint64_t np) {
 		// which run at the same time (measured at 3.1 Gbp, four instances: 2.63 M reads/s with one, 2.54 M with the two that fit)
 		// (round 6, four instances, same box: reads drawn uniformly 3.49 / 3.48 M with one / two, stress sub-leg 1.31 / 1.24 M)
 		// elements of a workgroup's slice: the most hits a read of this run can have (a list per k-mer and strand, none longer than max_kfreq) --
-		// not the most of THIS list: every new maximum would be a hipFree + hipMalloc, two device-wide synchronisations, in the middle of the run
+		// not the most of THIS list: every new maximum would be a free + allocation, two device-wide synchronisations, in the middle of the run
 		uint64_t cap = std::min<uint64_t>(kCsOrderBucketMaxHits, (((uint64_t) (B.lists_cap / 2) * (uint64_t) std::max(B.max_kfreq, 1)) + 63) & ~63ull);
 		uint32_t grid = (uint32_t) m->cus;
 		{

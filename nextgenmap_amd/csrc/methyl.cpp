@@ -74,10 +74,10 @@ extern "C" ngm_methyl *ngm_methyl_create(const ngm_methyl_params *p) {
 }
 
 extern "C" ngm_methyl *ngm_methyl_create_for_ref(const ngm_ref *r, const ngm_methyl_params *p) {
-	if (!r || !p || !r->d_genome) { ngm::pipeline_set_error("ngm_methyl_create_for_ref: bad arguments"); return nullptr; }
+	if (!r || !p || !r->d_genome.p) { ngm::pipeline_set_error("ngm_methyl_create_for_ref: bad arguments"); return nullptr; }
 	side::RefView ref;
 	if (!ref.from_ref("ngm_methyl_create_for_ref", *r)) return nullptr;
-	return create(p, r->device, ref, r->d_genome);   // (the reference outlives the run's caller)
+	return create(p, r->device, ref, r->d_genome.p);   // (the reference outlives the run's caller)
 }
 
 extern "C" void ngm_methyl_destroy(ngm_methyl *c) { side::destroy(c); }

@@ -378,9 +378,6 @@ void ngm_hip_destroy(ngm_hip_ctx *ctx) {
 	if (!ctx) return;
 	ScopedDevice sd(ctx->device);
 	if (ctx->stream) (void) hipStreamSynchronize(ctx->stream);
-	ctx->packed.release(); ctx->lens.release(); ctx->blk_rows.release(); ctx->d_ref.release(); ctx->d_qry.release();
-	ctx->d_scores.release(); ctx->dirs.release(); ctx->d_pair_dir.release(); ctx->d_records.release(); ctx->d_runs.release();
-	ctx->h_ref.release(); ctx->h_qry.release(); ctx->h_scores.release(); ctx->h_records.release(); ctx->h_runs.release();
 	for (auto &e : ctx->ev) if (e) (void) hipEventDestroy(e);
 	if (ctx->stream) (void) hipStreamDestroy(ctx->stream);
 	delete ctx;
@@ -554,31 +551,25 @@ int ngm_debug_align_finish(void *engine, int mode, int n, const char *const *ref
 	std::vector<ngm::CigarDevOut> h_out((size_t) n);
 	std::vector<char> h_str((size_t) scap);
 	unsigned long long ctr[2] = {0, 0};
-	auto run = [&]() -> int {
-		if (d_out.reserve(n) || d_str.reserve(scap) || d_ctr.reserve(2)) { set_error(ctx, "out of device memory (ngm_debug_align_finish)"); return -12; }
-		HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ref.p, ctx->h_ref.p, (size_t) n * rl, hipMemcpyHostToDevice, ctx->stream));
-		HIP_TRY(ctx, hipMemcpyAsync(ctx->d_qry.p, ctx->h_qry.p, (size_t) n * q, hipMemcpyHostToDevice, ctx->stream));
-		HIP_TRY(ctx, hipMemsetAsync(d_ctr.p, 0, 16, ctx->stream));
-		if (int r = engine_reserve(ctx, n)) return r;
-		if (int r = launch_pack(ctx, n, ctx->d_ref.p, ctx->d_qry.p, ctx->stream)) return r;
-		const ngm::AlignFinish fin{d_out.p, d_str.p, scap, d_ctr.p};
-		if (int r = ngm::engine_align_packed(ctx, mode, n, ctx->d_records.p, ctx->d_runs.p, rs, ctx->stream, &fin)) return r;
-		HIP_TRY(ctx, hipMemcpyAsync(h_out.data(), d_out.p, (size_t) n * sizeof(ngm::CigarDevOut), hipMemcpyDeviceToHost, ctx->stream));
-		HIP_TRY(ctx, hipMemcpyAsync(ctr, d_ctr.p, 16, hipMemcpyDeviceToHost, ctx->stream));
+	if (d_out.reserve(n) || d_str.reserve(scap) || d_ctr.reserve(2)) { set_error(ctx, "out of device memory (ngm_debug_align_finish)"); return -12; }
+	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ref.p, ctx->h_ref.p, (size_t) n * rl, hipMemcpyHostToDevice, ctx->stream));
+	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_qry.p, ctx->h_qry.p, (size_t) n * q, hipMemcpyHostToDevice, ctx->stream));
+	HIP_TRY(ctx, hipMemsetAsync(d_ctr.p, 0, 16, ctx->stream));
+	if (int r = engine_reserve(ctx, n)) return r;
+	if (int r = launch_pack(ctx, n, ctx->d_ref.p, ctx->d_qry.p, ctx->stream)) return r;
+	const ngm::AlignFinish fin{d_out.p, d_str.p, scap, d_ctr.p};
+	if (int r = ngm::engine_align_packed(ctx, mode, n, ctx->d_records.p, ctx->d_runs.p, rs, ctx->stream, &fin)) return r;
+	HIP_TRY(ctx, hipMemcpyAsync(h_out.data(), d_out.p, (size_t) n * sizeof(ngm::CigarDevOut), hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(ctx, hipMemcpyAsync(ctr, d_ctr.p, 16, hipMemcpyDeviceToHost, ctx->stream));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+	const unsigned long long used = std::min(ctr[0], scap);
+	if (used) HIP_TRY(ctx, hipMemcpy(h_str.data(), d_str.p, (size_t) used, hipMemcpyDeviceToHost));
+	if (ctr[1]) {
+		if (int r = ngm::engine_affine_traceback_packed(ctx, n, ctx->d_records.p, ctx->d_runs.p, rs, ctx->stream)) return r;
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->h_records.p, ctx->d_records.p, sizeof(int32_t) * 8 * (size_t) n, hipMemcpyDeviceToHost, ctx->stream));
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->h_runs.p, ctx->d_runs.p, sizeof(uint16_t) * (size_t) rs * n, hipMemcpyDeviceToHost, ctx->stream));
 		HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-		const unsigned long long used = std::min(ctr[0], scap);
-		if (used) HIP_TRY(ctx, hipMemcpy(h_str.data(), d_str.p, (size_t) used, hipMemcpyDeviceToHost));
-		if (ctr[1]) {
-			if (int r = ngm::engine_affine_traceback_packed(ctx, n, ctx->d_records.p, ctx->d_runs.p, rs, ctx->stream)) return r;
-			HIP_TRY(ctx, hipMemcpyAsync(ctx->h_records.p, ctx->d_records.p, sizeof(int32_t) * 8 * (size_t) n, hipMemcpyDeviceToHost, ctx->stream));
-			HIP_TRY(ctx, hipMemcpyAsync(ctx->h_runs.p, ctx->d_runs.p, sizeof(uint16_t) * (size_t) rs * n, hipMemcpyDeviceToHost, ctx->stream));
-			HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-		}
-		return 0;
-	};
-	const int rc = run();
-	d_out.release(); d_str.release(); d_ctr.release();
-	if (rc) return rc;
+	}
 	*n_fallback = ctr[1];
 	for (int i = 0; i < n; ++i) {
 		const ngm::CigarDevOut &dv = h_out[(size_t) i];

@@ -7,7 +7,6 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <functional>
 #include <mutex>
 #include <string.h>
 #include <fcntl.h>
@@ -35,6 +34,8 @@ thread_local std::string g_pipeline_error;
 			return -5;                                                                         \
 		}                                                                                      \
 	} while (0)
+
+using ngm::Buf;
 
 inline uint8_t class_of_base(uint8_t c) {  // enc4 semantics (SequenceProvider.cpp:72-85): non-ACGT -> N
 	switch (c & 0xDF) {
@@ -223,60 +224,54 @@ __global__ void walk_store_flags_kernel(const uint32_t *__restrict__ pos, const 
 // carried walk state (CompactPrefixTable::lastPrefix / lastBin) after the last contig, and the visited k-mer count: --vcf needs both
 struct WalkEnd { uint64_t visited = 0; uint32_t last_prefix = 111111u; int64_t last_bin = -1; };
 
-int gpu_kmer_walk(ngm_ref *r, uint32_t **d_keys_out, uint32_t **d_vals_out, uint64_t *n_out, WalkEnd *end) {
+int gpu_kmer_walk(ngm_ref *r, Buf<uint32_t> &keys_out, Buf<uint32_t> &vals_out, uint64_t *n_out, WalkEnd *end) {
 	const uint64_t n = r->n_bases;
 	const int k = r->prm.kmer, nc = (int) r->contigs.size();
 	std::vector<uint64_t> hs(nc), he(nc);
 	for (int c = 0; c < nc; ++c) { hs[c] = r->contigs[c].start; he[c] = r->contigs[c].start + r->contigs[c].len; }
-	uint64_t *d_cs = nullptr, *d_ce = nullptr;
-	uint32_t *d_run = nullptr, *d_pos = nullptr, *d_keys = nullptr, *d_keys2 = nullptr, *d_pos2 = nullptr;
-	uint8_t *d_flag = nullptr;
-	uint64_t *d_count = nullptr;
-	void *d_tmp = nullptr;
-	auto cleanup = [&]() { (void) hipFree(d_cs); (void) hipFree(d_ce); (void) hipFree(d_run); (void) hipFree(d_flag); (void) hipFree(d_count); (void) hipFree(d_tmp);
-		d_cs = d_ce = nullptr; d_run = nullptr; d_flag = nullptr; d_count = nullptr; d_tmp = nullptr; };
-	// every error return below frees what the walk holds (up to ~12 GB of scratch for a human-size genome)
-	bool done = false;
-	struct Guard { std::function<void()> f; bool *done; ~Guard() { if (!*done) f(); } } guard{[&]() { cleanup(); (void) hipFree(d_pos); (void) hipFree(d_keys); (void) hipFree(d_keys2); (void) hipFree(d_pos2); }, &done};
-	REF_HIP_TRY(hipMalloc(&d_cs, std::max(1, nc) * 8)); REF_HIP_TRY(hipMalloc(&d_ce, std::max(1, nc) * 8));
-	REF_HIP_TRY(hipMemcpy(d_cs, hs.data(), nc * 8, hipMemcpyHostToDevice)); REF_HIP_TRY(hipMemcpy(d_ce, he.data(), nc * 8, hipMemcpyHostToDevice));
-	REF_HIP_TRY(hipMalloc(&d_run, std::max<uint64_t>(n, 1) * 4)); REF_HIP_TRY(hipMalloc(&d_flag, std::max<uint64_t>(n, 1))); REF_HIP_TRY(hipMalloc(&d_count, 8));
+	// (every return frees what the walk still holds: up to ~12 GB of scratch for a human-size genome)
+	Buf<uint64_t> d_cs, d_ce, d_count;
+	Buf<uint32_t> d_run, d_pos, d_keys, d_keys2, d_pos2;
+	Buf<uint8_t> d_flag, d_tmp;
+	NGM_MEM_TRY(d_cs.alloc(std::max(1, nc))); NGM_MEM_TRY(d_ce.alloc(std::max(1, nc)));
+	REF_HIP_TRY(hipMemcpy(d_cs.p, hs.data(), nc * 8, hipMemcpyHostToDevice)); REF_HIP_TRY(hipMemcpy(d_ce.p, he.data(), nc * 8, hipMemcpyHostToDevice));
+	NGM_MEM_TRY(d_run.alloc(std::max<uint64_t>(n, 1))); NGM_MEM_TRY(d_flag.alloc(std::max<uint64_t>(n, 1))); NGM_MEM_TRY(d_count.alloc(1));
 	const unsigned nb = (unsigned) ((n + 255) / 256);
-	hipLaunchKernelGGL(walk_mark_n_kernel, dim3(nb), dim3(256), 0, 0, r->d_genome, n, d_run);
-	if (nc > 0) hipLaunchKernelGGL(walk_unmark_tails_kernel, dim3((nc + 255) / 256), dim3(256), 0, 0, d_ce, nc, d_run);
+	hipLaunchKernelGGL(walk_mark_n_kernel, dim3(nb), dim3(256), 0, 0, r->d_genome.p, n, d_run.p);
+	if (nc > 0) hipLaunchKernelGGL(walk_unmark_tails_kernel, dim3((nc + 255) / 256), dim3(256), 0, 0, d_ce.p, nc, d_run.p);
 	size_t tb = 0, tb2 = 0;
-	(void) rocprim::inclusive_scan(nullptr, tb, d_run, d_run, (size_t) n, rocprim::maximum<uint32_t>());
-	(void) rocprim::select(nullptr, tb2, rocprim::counting_iterator<uint32_t>(0), d_flag, (uint32_t *) nullptr, d_count, (size_t) n);
+	(void) rocprim::inclusive_scan(nullptr, tb, d_run.p, d_run.p, (size_t) n, rocprim::maximum<uint32_t>());
+	(void) rocprim::select(nullptr, tb2, rocprim::counting_iterator<uint32_t>(0), d_flag.p, (uint32_t *) nullptr, d_count.p, (size_t) n);
 	size_t tb3 = 0;
-	(void) rocprim::select(nullptr, tb3, (uint32_t *) nullptr, d_flag, (uint32_t *) nullptr, d_count, (size_t) n);
+	(void) rocprim::select(nullptr, tb3, (uint32_t *) nullptr, d_flag.p, (uint32_t *) nullptr, d_count.p, (size_t) n);
 	tb = std::max(tb, std::max(tb2, tb3)) + 256;
-	REF_HIP_TRY(hipMalloc(&d_tmp, tb));
-	REF_HIP_TRY(rocprim::inclusive_scan(d_tmp, tb, d_run, d_run, (size_t) n, rocprim::maximum<uint32_t>()));
-	hipLaunchKernelGGL(walk_visit_flags_kernel, dim3(nb), dim3(256), 0, 0, d_run, r->d_genome, n, k, r->prm.kmer_skip + 1, d_cs, d_ce, nc, d_flag);
+	NGM_MEM_TRY(d_tmp.alloc(tb));
+	REF_HIP_TRY(rocprim::inclusive_scan(d_tmp.p, tb, d_run.p, d_run.p, (size_t) n, rocprim::maximum<uint32_t>()));
+	hipLaunchKernelGGL(walk_visit_flags_kernel, dim3(nb), dim3(256), 0, 0, d_run.p, r->d_genome.p, n, k, r->prm.kmer_skip + 1, d_cs.p, d_ce.p, nc, d_flag.p);
 	REF_HIP_TRY(hipGetLastError());
 	// upper bound of visited k-mers: every (skip+1)-th position plus one per run
 	const uint64_t cap = n / (uint64_t) (r->prm.kmer_skip + 1) + n / 1000 + 4096;
-	REF_HIP_TRY(hipMalloc(&d_pos, cap * 4));
-	REF_HIP_TRY(rocprim::select(d_tmp, tb, rocprim::counting_iterator<uint32_t>(0), d_flag, d_pos, d_count, (size_t) n));
+	NGM_MEM_TRY(d_pos.alloc(cap));
+	REF_HIP_TRY(rocprim::select(d_tmp.p, tb, rocprim::counting_iterator<uint32_t>(0), d_flag.p, d_pos.p, d_count.p, (size_t) n));
 	uint64_t m = 0;
-	REF_HIP_TRY(hipMemcpy(&m, d_count, 8, hipMemcpyDeviceToHost));
+	REF_HIP_TRY(hipMemcpy(&m, d_count.p, 8, hipMemcpyDeviceToHost));
 	if (m > cap) { ngm::pipeline_set_error("k-mer walk: more visited k-mers than expected"); return -75; }
-	(void) hipFree(d_run); d_run = nullptr;
-	REF_HIP_TRY(hipMalloc(&d_keys, std::max<uint64_t>(m, 1) * 4)); REF_HIP_TRY(hipMalloc(&d_keys2, std::max<uint64_t>(m, 1) * 4)); REF_HIP_TRY(hipMalloc(&d_pos2, std::max<uint64_t>(m, 1) * 4));
+	d_run.release();   // (early: its four bytes per base make room for the three arrays below)
+	NGM_MEM_TRY(d_keys.alloc(std::max<uint64_t>(m, 1))); NGM_MEM_TRY(d_keys2.alloc(std::max<uint64_t>(m, 1))); NGM_MEM_TRY(d_pos2.alloc(std::max<uint64_t>(m, 1)));
 	uint64_t kept = 0;
 	if (m > 0) {
 		const unsigned mb = (unsigned) ((m + 255) / 256);
-		hipLaunchKernelGGL(walk_keys_kernel, dim3(mb), dim3(256), 0, 0, d_pos, m, r->d_genome, k, d_cs, d_ce, nc, d_keys);
-		hipLaunchKernelGGL(walk_store_flags_kernel, dim3(mb), dim3(256), 0, 0, d_pos, d_keys, m, r->prm.bin_size, d_cs, nc, d_flag);
+		hipLaunchKernelGGL(walk_keys_kernel, dim3(mb), dim3(256), 0, 0, d_pos.p, m, r->d_genome.p, k, d_cs.p, d_ce.p, nc, d_keys.p);
+		hipLaunchKernelGGL(walk_store_flags_kernel, dim3(mb), dim3(256), 0, 0, d_pos.p, d_keys.p, m, r->prm.bin_size, d_cs.p, nc, d_flag.p);
 		REF_HIP_TRY(hipGetLastError());
-		REF_HIP_TRY(rocprim::select(d_tmp, tb, d_keys, d_flag, d_keys2, d_count, (size_t) m));
-		REF_HIP_TRY(rocprim::select(d_tmp, tb, d_pos, d_flag, d_pos2, d_count, (size_t) m));
-		REF_HIP_TRY(hipMemcpy(&kept, d_count, 8, hipMemcpyDeviceToHost));
+		REF_HIP_TRY(rocprim::select(d_tmp.p, tb, d_keys.p, d_flag.p, d_keys2.p, d_count.p, (size_t) m));
+		REF_HIP_TRY(rocprim::select(d_tmp.p, tb, d_pos.p, d_flag.p, d_pos2.p, d_count.p, (size_t) m));
+		REF_HIP_TRY(hipMemcpy(&kept, d_count.p, 8, hipMemcpyDeviceToHost));
 		if (end && nc > 0) {  // the state the last contig's walk leaves behind: from its last two visited k-mers
 			uint32_t lk[2] = {0, 0}, lp[2] = {0, 0};
 			const uint64_t t = m >= 2 ? m - 2 : 0, cnt = m - t;
-			REF_HIP_TRY(hipMemcpy(lk, d_keys + t, cnt * 4, hipMemcpyDeviceToHost));
-			REF_HIP_TRY(hipMemcpy(lp, d_pos + t, cnt * 4, hipMemcpyDeviceToHost));
+			REF_HIP_TRY(hipMemcpy(lk, d_keys.p + t, cnt * 4, hipMemcpyDeviceToHost));
+			REF_HIP_TRY(hipMemcpy(lp, d_pos.p + t, cnt * 4, hipMemcpyDeviceToHost));
 			const uint64_t last_start = hs[nc - 1];
 			const int in_last = (cnt >= 1 && lp[cnt - 1] >= last_start) + (cnt >= 2 && lp[0] >= last_start);
 			if (in_last >= 1) {
@@ -287,10 +282,7 @@ int gpu_kmer_walk(ngm_ref *r, uint32_t **d_keys_out, uint32_t **d_vals_out, uint
 		}
 	}
 	if (end) end->visited = m;
-	cleanup();
-	(void) hipFree(d_pos); (void) hipFree(d_keys);
-	done = true;
-	*d_keys_out = d_keys2; *d_vals_out = d_pos2; *n_out = kept;
+	keys_out = std::move(d_keys2); vals_out = std::move(d_pos2); *n_out = kept;
 	return 0;
 }
 
@@ -479,9 +471,8 @@ __global__ void vcf_index_kernel(uint32_t n_kmers, const uint32_t *__restrict__ 
 
 // what the variants add to the table: fill-pass entries (keys + positions, VCF order) and count-pass keys
 struct VcfEntries {
-	uint32_t *d_fkeys = nullptr, *d_fvals = nullptr, *d_ckeys = nullptr;
+	Buf<uint32_t> d_fkeys, d_fvals, d_ckeys;
 	uint64_t nf = 0, nc = 0, visited = 0;
-	~VcfEntries() { (void) hipFree(d_fkeys); (void) hipFree(d_fvals); (void) hipFree(d_ckeys); }
 };
 
 // regions on the GPU; their walk on the GPU, or (host_walk) on the host like KmerWalker
@@ -496,46 +487,41 @@ int build_vcf_entries(ngm_ref *r, const WalkEnd &end, bool host_walk, VcfEntries
 		if (v.pos < half) { ngm::pipeline_set_error("VCF variant at %llu: its region would start before the genome", (unsigned long long) v.pos); return -22; }
 		if (v.pos - half >= concat) { ngm::pipeline_set_error("VCF variant at %llu lies beyond the end of the genome", (unsigned long long) v.pos); return -22; }
 	}
-	NgmVariant *d_var = nullptr;
-	char *d_seq = nullptr;
-	uint8_t *d_status = nullptr, *d_regions = nullptr, *d_cf = nullptr, *d_ff = nullptr;
-	uint64_t *d_len = nullptr, *d_roff = nullptr, *d_vcount = nullptr, *d_voff = nullptr, *d_sel = nullptr;
-	unsigned long long *d_bad = nullptr, *d_counts = nullptr;
-	uint32_t *d_vk = nullptr, *d_vp = nullptr, *d_vr = nullptr;
-	void *d_tmp = nullptr;
-	struct Free { std::function<void()> f; ~Free() { f(); } } free_all{[&] {
-		(void) hipFree(d_var); (void) hipFree(d_seq); (void) hipFree(d_status); (void) hipFree(d_regions); (void) hipFree(d_cf); (void) hipFree(d_ff);
-		(void) hipFree(d_len); (void) hipFree(d_roff); (void) hipFree(d_vcount); (void) hipFree(d_voff); (void) hipFree(d_sel); (void) hipFree(d_bad);
-		(void) hipFree(d_counts); (void) hipFree(d_vk); (void) hipFree(d_vp); (void) hipFree(d_vr); (void) hipFree(d_tmp); }};
-	REF_HIP_TRY(hipMalloc(&d_var, n * sizeof(NgmVariant)));
-	REF_HIP_TRY(hipMalloc(&d_seq, std::max<size_t>(vcf.seq.size(), 1)));
-	REF_HIP_TRY(hipMemcpy(d_var, vcf.v.data(), n * sizeof(NgmVariant), hipMemcpyHostToDevice));
-	REF_HIP_TRY(hipMemcpy(d_seq, vcf.seq.data(), vcf.seq.size(), hipMemcpyHostToDevice));
-	REF_HIP_TRY(hipMalloc(&d_status, n)); REF_HIP_TRY(hipMalloc(&d_len, n * 8)); REF_HIP_TRY(hipMalloc(&d_roff, n * 8));
-	REF_HIP_TRY(hipMalloc(&d_bad, 8)); REF_HIP_TRY(hipMalloc(&d_counts, 3 * 8)); REF_HIP_TRY(hipMalloc(&d_sel, 8));
+	Buf<NgmVariant> d_var;
+	Buf<char> d_seq;
+	Buf<uint8_t> d_status, d_regions, d_cf, d_ff, d_tmp;
+	Buf<uint64_t> d_len, d_roff, d_vcount, d_voff, d_sel;
+	Buf<unsigned long long> d_bad, d_counts;
+	Buf<uint32_t> d_vk, d_vp, d_vr;
+	NGM_MEM_TRY(d_var.alloc(n));
+	NGM_MEM_TRY(d_seq.alloc(std::max<size_t>(vcf.seq.size(), 1)));
+	REF_HIP_TRY(hipMemcpy(d_var.p, vcf.v.data(), n * sizeof(NgmVariant), hipMemcpyHostToDevice));
+	REF_HIP_TRY(hipMemcpy(d_seq.p, vcf.seq.data(), vcf.seq.size(), hipMemcpyHostToDevice));
+	NGM_MEM_TRY(d_status.alloc(n)); NGM_MEM_TRY(d_len.alloc(n)); NGM_MEM_TRY(d_roff.alloc(n));
+	NGM_MEM_TRY(d_bad.alloc(1)); NGM_MEM_TRY(d_counts.alloc(3)); NGM_MEM_TRY(d_sel.alloc(1));
 	const unsigned long long none = ~0ull;
-	REF_HIP_TRY(hipMemcpy(d_bad, &none, 8, hipMemcpyHostToDevice));
-	REF_HIP_TRY(hipMemset(d_counts, 0, 3 * 8));
+	REF_HIP_TRY(hipMemcpy(d_bad.p, &none, 8, hipMemcpyHostToDevice));
+	REF_HIP_TRY(hipMemset(d_counts.p, 0, 3 * 8));
 	const unsigned nb = (unsigned) ((n + 255) / 256);
-	hipLaunchKernelGGL(vcf_classify_kernel, dim3(nb), dim3(256), 0, 0, d_var, n, d_seq, r->d_genome, concat, k, d_status, d_len, d_bad);
-	hipLaunchKernelGGL(vcf_cut_kernel, dim3(nb), dim3(256), 0, 0, n, d_bad, d_status, d_len, d_counts);
+	hipLaunchKernelGGL(vcf_classify_kernel, dim3(nb), dim3(256), 0, 0, d_var.p, n, d_seq.p, r->d_genome.p, concat, k, d_status.p, d_len.p, d_bad.p);
+	hipLaunchKernelGGL(vcf_cut_kernel, dim3(nb), dim3(256), 0, 0, n, d_bad.p, d_status.p, d_len.p, d_counts.p);
 	REF_HIP_TRY(hipGetLastError());
 	unsigned long long counts[3], bad = 0;
-	REF_HIP_TRY(hipMemcpy(counts, d_counts, 3 * 8, hipMemcpyDeviceToHost));
-	REF_HIP_TRY(hipMemcpy(&bad, d_bad, 8, hipMemcpyDeviceToHost));
+	REF_HIP_TRY(hipMemcpy(counts, d_counts.p, 3 * 8, hipMemcpyDeviceToHost));
+	REF_HIP_TRY(hipMemcpy(&bad, d_bad.p, 8, hipMemcpyDeviceToHost));
 	if (bad != none) fprintf(stderr, "[PREPROCESS] SNP ref does not match reference at SNP %llu\n", (unsigned long long) vcf.v[bad].pos);
 	r->vcf_summary[1] = counts[0]; r->vcf_summary[2] = counts[1]; r->vcf_summary[3] = counts[2] + (bad != none ? 1 : 0);
 	size_t tb = 0;
-	REF_HIP_TRY(rocprim::exclusive_scan(nullptr, tb, d_len, d_roff, (uint64_t) 0, (size_t) n, rocprim::plus<uint64_t>()));
+	REF_HIP_TRY(rocprim::exclusive_scan(nullptr, tb, d_len.p, d_roff.p, (uint64_t) 0, (size_t) n, rocprim::plus<uint64_t>()));
 	tb += 256;
-	REF_HIP_TRY(hipMalloc(&d_tmp, tb));
-	REF_HIP_TRY(rocprim::exclusive_scan(d_tmp, tb, d_len, d_roff, (uint64_t) 0, (size_t) n, rocprim::plus<uint64_t>()));
+	NGM_MEM_TRY(d_tmp.alloc(tb));
+	REF_HIP_TRY(rocprim::exclusive_scan(d_tmp.p, tb, d_len.p, d_roff.p, (uint64_t) 0, (size_t) n, rocprim::plus<uint64_t>()));
 	uint64_t last_off = 0, last_len = 0;
-	REF_HIP_TRY(hipMemcpy(&last_off, d_roff + n - 1, 8, hipMemcpyDeviceToHost));
-	REF_HIP_TRY(hipMemcpy(&last_len, d_len + n - 1, 8, hipMemcpyDeviceToHost));
+	REF_HIP_TRY(hipMemcpy(&last_off, d_roff.p + n - 1, 8, hipMemcpyDeviceToHost));
+	REF_HIP_TRY(hipMemcpy(&last_len, d_len.p + n - 1, 8, hipMemcpyDeviceToHost));
 	const uint64_t total = last_off + last_len;
-	REF_HIP_TRY(hipMalloc(&d_regions, std::max<uint64_t>(total, 1)));
-	hipLaunchKernelGGL(vcf_fill_kernel, dim3(nb), dim3(256), 0, 0, d_var, n, d_seq, r->d_genome, concat, k, d_len, d_roff, d_regions);
+	NGM_MEM_TRY(d_regions.alloc(std::max<uint64_t>(total, 1)));
+	hipLaunchKernelGGL(vcf_fill_kernel, dim3(nb), dim3(256), 0, 0, d_var.p, n, d_seq.p, r->d_genome.p, concat, k, d_len.p, d_roff.p, d_regions.p);
 	REF_HIP_TRY(hipGetLastError());
 	const uint32_t mask = (1u << (2 * k)) - 1u;
 	const int bin_shift = r->prm.bin_size, skip = r->prm.kmer_skip;
@@ -543,9 +529,9 @@ int build_vcf_entries(ngm_ref *r, const WalkEnd &end, bool host_walk, VcfEntries
 		// the two walkers of the reference: the count pass restarts its state per region, the fill pass carries it on
 		std::vector<uint8_t> reg(total);
 		std::vector<uint64_t> len(n), roff(n);
-		REF_HIP_TRY(hipMemcpy(reg.data(), d_regions, total, hipMemcpyDeviceToHost));
-		REF_HIP_TRY(hipMemcpy(len.data(), d_len, n * 8, hipMemcpyDeviceToHost));
-		REF_HIP_TRY(hipMemcpy(roff.data(), d_roff, n * 8, hipMemcpyDeviceToHost));
+		REF_HIP_TRY(hipMemcpy(reg.data(), d_regions.p, total, hipMemcpyDeviceToHost));
+		REF_HIP_TRY(hipMemcpy(len.data(), d_len.p, n * 8, hipMemcpyDeviceToHost));
+		REF_HIP_TRY(hipMemcpy(roff.data(), d_roff.p, n * 8, hipMemcpyDeviceToHost));
 		std::vector<uint32_t> fk, fv, ck;
 		uint32_t fp = end.last_prefix, cpfx = 111111u;
 		int64_t fb = end.last_bin, cbin = -1;
@@ -570,39 +556,39 @@ int build_vcf_entries(ngm_ref *r, const WalkEnd &end, bool host_walk, VcfEntries
 			vcf_walk_region(reg.data() + roff[i], len[i], v.pos - ((uint64_t) k + v.ref_len + v.alt_len - 2), k, skip, mask, f);
 		}
 		out.visited = visited; out.nf = fk.size(); out.nc = ck.size();
-		REF_HIP_TRY(hipMalloc(&out.d_fkeys, std::max<uint64_t>(out.nf, 1) * 4)); REF_HIP_TRY(hipMalloc(&out.d_fvals, std::max<uint64_t>(out.nf, 1) * 4));
-		REF_HIP_TRY(hipMalloc(&out.d_ckeys, std::max<uint64_t>(out.nc, 1) * 4));
-		REF_HIP_TRY(hipMemcpy(out.d_fkeys, fk.data(), out.nf * 4, hipMemcpyHostToDevice));
-		REF_HIP_TRY(hipMemcpy(out.d_fvals, fv.data(), out.nf * 4, hipMemcpyHostToDevice));
-		REF_HIP_TRY(hipMemcpy(out.d_ckeys, ck.data(), out.nc * 4, hipMemcpyHostToDevice));
+		NGM_MEM_TRY(out.d_fkeys.alloc(std::max<uint64_t>(out.nf, 1))); NGM_MEM_TRY(out.d_fvals.alloc(std::max<uint64_t>(out.nf, 1)));
+		NGM_MEM_TRY(out.d_ckeys.alloc(std::max<uint64_t>(out.nc, 1)));
+		REF_HIP_TRY(hipMemcpy(out.d_fkeys.p, fk.data(), out.nf * 4, hipMemcpyHostToDevice));
+		REF_HIP_TRY(hipMemcpy(out.d_fvals.p, fv.data(), out.nf * 4, hipMemcpyHostToDevice));
+		REF_HIP_TRY(hipMemcpy(out.d_ckeys.p, ck.data(), out.nc * 4, hipMemcpyHostToDevice));
 		return 0;
 	}
-	REF_HIP_TRY(hipMalloc(&d_vcount, n * 8)); REF_HIP_TRY(hipMalloc(&d_voff, n * 8));
-	hipLaunchKernelGGL(vcf_walk_kernel<false>, dim3(nb), dim3(256), 0, 0, d_var, n, k, skip, d_len, d_roff, d_regions, d_vcount, nullptr, nullptr, nullptr, nullptr);
+	NGM_MEM_TRY(d_vcount.alloc(n)); NGM_MEM_TRY(d_voff.alloc(n));
+	hipLaunchKernelGGL(vcf_walk_kernel<false>, dim3(nb), dim3(256), 0, 0, d_var.p, n, k, skip, d_len.p, d_roff.p, d_regions.p, d_vcount.p, nullptr, nullptr, nullptr, nullptr);
 	REF_HIP_TRY(hipGetLastError());
-	REF_HIP_TRY(rocprim::exclusive_scan(d_tmp, tb, d_vcount, d_voff, (uint64_t) 0, (size_t) n, rocprim::plus<uint64_t>()));
-	REF_HIP_TRY(hipMemcpy(&last_off, d_voff + n - 1, 8, hipMemcpyDeviceToHost));
-	REF_HIP_TRY(hipMemcpy(&last_len, d_vcount + n - 1, 8, hipMemcpyDeviceToHost));
+	REF_HIP_TRY(rocprim::exclusive_scan(d_tmp.p, tb, d_vcount.p, d_voff.p, (uint64_t) 0, (size_t) n, rocprim::plus<uint64_t>()));
+	REF_HIP_TRY(hipMemcpy(&last_off, d_voff.p + n - 1, 8, hipMemcpyDeviceToHost));
+	REF_HIP_TRY(hipMemcpy(&last_len, d_vcount.p + n - 1, 8, hipMemcpyDeviceToHost));
 	const uint64_t m = last_off + last_len;
 	out.visited = m;
 	if (m == 0) return 0;
-	REF_HIP_TRY(hipMalloc(&d_vk, m * 4)); REF_HIP_TRY(hipMalloc(&d_vp, m * 4)); REF_HIP_TRY(hipMalloc(&d_vr, m * 4));
-	hipLaunchKernelGGL(vcf_walk_kernel<true>, dim3(nb), dim3(256), 0, 0, d_var, n, k, skip, d_len, d_roff, d_regions, nullptr, d_voff, d_vk, d_vp, d_vr);
-	REF_HIP_TRY(hipMalloc(&d_cf, m)); REF_HIP_TRY(hipMalloc(&d_ff, m));
+	NGM_MEM_TRY(d_vk.alloc(m)); NGM_MEM_TRY(d_vp.alloc(m)); NGM_MEM_TRY(d_vr.alloc(m));
+	hipLaunchKernelGGL(vcf_walk_kernel<true>, dim3(nb), dim3(256), 0, 0, d_var.p, n, k, skip, d_len.p, d_roff.p, d_regions.p, nullptr, d_voff.p, d_vk.p, d_vp.p, d_vr.p);
+	NGM_MEM_TRY(d_cf.alloc(m)); NGM_MEM_TRY(d_ff.alloc(m));
 	const unsigned mb = (unsigned) ((m + 255) / 256);
-	hipLaunchKernelGGL(vcf_store_flags_kernel, dim3(mb), dim3(256), 0, 0, d_vk, d_vp, d_vr, m, bin_shift, end.last_prefix, (long long) end.last_bin, d_cf, d_ff);
+	hipLaunchKernelGGL(vcf_store_flags_kernel, dim3(mb), dim3(256), 0, 0, d_vk.p, d_vp.p, d_vr.p, m, bin_shift, end.last_prefix, (long long) end.last_bin, d_cf.p, d_ff.p);
 	REF_HIP_TRY(hipGetLastError());
-	(void) hipFree(d_tmp); d_tmp = nullptr;
+	d_tmp.release();   // (early: the select's storage is sized anew)
 	tb = 0;
-	REF_HIP_TRY(rocprim::select(nullptr, tb, d_vk, d_ff, (uint32_t *) nullptr, d_sel, (size_t) m));
+	REF_HIP_TRY(rocprim::select(nullptr, tb, d_vk.p, d_ff.p, (uint32_t *) nullptr, d_sel.p, (size_t) m));
 	tb += 256;
-	REF_HIP_TRY(hipMalloc(&d_tmp, tb));
-	REF_HIP_TRY(hipMalloc(&out.d_fkeys, m * 4)); REF_HIP_TRY(hipMalloc(&out.d_fvals, m * 4)); REF_HIP_TRY(hipMalloc(&out.d_ckeys, m * 4));
-	REF_HIP_TRY(rocprim::select(d_tmp, tb, d_vk, d_ff, out.d_fkeys, d_sel, (size_t) m));
-	REF_HIP_TRY(rocprim::select(d_tmp, tb, d_vp, d_ff, out.d_fvals, d_sel, (size_t) m));
-	REF_HIP_TRY(hipMemcpy(&out.nf, d_sel, 8, hipMemcpyDeviceToHost));
-	REF_HIP_TRY(rocprim::select(d_tmp, tb, d_vk, d_cf, out.d_ckeys, d_sel, (size_t) m));
-	REF_HIP_TRY(hipMemcpy(&out.nc, d_sel, 8, hipMemcpyDeviceToHost));
+	NGM_MEM_TRY(d_tmp.alloc(tb));
+	NGM_MEM_TRY(out.d_fkeys.alloc(m)); NGM_MEM_TRY(out.d_fvals.alloc(m)); NGM_MEM_TRY(out.d_ckeys.alloc(m));
+	REF_HIP_TRY(rocprim::select(d_tmp.p, tb, d_vk.p, d_ff.p, out.d_fkeys.p, d_sel.p, (size_t) m));
+	REF_HIP_TRY(rocprim::select(d_tmp.p, tb, d_vp.p, d_ff.p, out.d_fvals.p, d_sel.p, (size_t) m));
+	REF_HIP_TRY(hipMemcpy(&out.nf, d_sel.p, 8, hipMemcpyDeviceToHost));
+	REF_HIP_TRY(rocprim::select(d_tmp.p, tb, d_vk.p, d_cf.p, out.d_ckeys.p, d_sel.p, (size_t) m));
+	REF_HIP_TRY(hipMemcpy(&out.nc, d_sel.p, 8, hipMemcpyDeviceToHost));
 	return 0;
 }
 
@@ -650,7 +636,7 @@ int build_buckets_kind(ngm_ref *r, int kind) {
 	const int k = r->prm.kmer;
 	const uint32_t n_kmers = 1u << (2 * k);
 	if (kind == 1) {
-		if (r->d_cbuckets) return 0;
+		if (r->d_cbuckets.p) return 0;
 		if ((k & 1) == 0) { ngm::pipeline_set_error("canonical buckets need an odd k-mer length"); return -22; }
 		const uint32_t n_pairs = n_kmers / 2;
 		const double mu = (double) r->n_entries / (double) n_pairs;
@@ -658,17 +644,17 @@ int build_buckets_kind(ngm_ref *r, int kind) {
 		while (lw < 6 && (double) ((1 << lw) - 1) < mu + 4.0 * sqrt(mu) + 0.5) ++lw;
 		while (lw > 2 && ((uint64_t) n_pairs << lw) + r->n_entries + 16 >= 0xFFFFFFFFull) --lw;
 		const uint64_t words = (uint64_t) n_pairs << lw;
-		uint32_t *d = nullptr;
-		REF_HIP_TRY(hipMalloc(&d, (words + r->n_entries + 16) * 4));
-		hipLaunchKernelGGL(fill_cbuckets_kernel, dim3((unsigned) ((words + 255) / 256)), dim3(256), 0, 0, n_pairs, k, lw, r->d_index, r->d_positions, d);
-		if (hipGetLastError() != hipSuccess || hipMemcpy(d + words, r->d_positions, (r->n_entries + 16) * 4, hipMemcpyDeviceToDevice) != hipSuccess ||
-				hipDeviceSynchronize() != hipSuccess) { (void) hipFree(d); ngm::pipeline_set_error("building the canonical buckets failed"); return -5; }
+		Buf<uint32_t> d;
+		NGM_MEM_TRY(d.alloc(words + r->n_entries + 16));
+		hipLaunchKernelGGL(fill_cbuckets_kernel, dim3((unsigned) ((words + 255) / 256)), dim3(256), 0, 0, n_pairs, k, lw, r->d_index.p, r->d_positions.p, d.p);
+		if (hipGetLastError() != hipSuccess || hipMemcpy(d.p + words, r->d_positions.p, (r->n_entries + 16) * 4, hipMemcpyDeviceToDevice) != hipSuccess ||
+				hipDeviceSynchronize() != hipSuccess) { ngm::pipeline_set_error("building the canonical buckets failed"); return -5; }
 		r->cbucket_log2_words = lw;
 		r->cbucket_pos_base = (uint32_t) words;
-		r->d_cbuckets = d;
+		r->d_cbuckets = std::move(d);
 		return 0;
 	}
-	if (r->d_buckets) return 0;
+	if (r->d_buckets.p) return 0;
 	// W - 1 >= mean + 4 standard deviations of a Poisson list length (real genomes have a heavy tail on top: those
 	// lists overflow into d_positions, which costs them one more request)
 	const double mu = (double) r->n_entries / (double) n_kmers;
@@ -678,21 +664,21 @@ int build_buckets_kind(ngm_ref *r, int kind) {
 	// list that did not fit alike; both must stay below 2^32 words
 	while (lw > 2 && (((uint64_t) n_kmers + 1) << lw) + r->n_entries + 16 >= 0xFFFFFFFFull) --lw;
 	const uint64_t words = ((uint64_t) n_kmers + 1) << lw;
-	uint32_t *d = nullptr;
-	REF_HIP_TRY(hipMalloc(&d, (words + r->n_entries + 16) * 4));
-	hipLaunchKernelGGL(fill_buckets_kernel, dim3((unsigned) ((words + 255) / 256)), dim3(256), 0, 0, n_kmers, k, lw, r->d_index, r->d_positions, d);
-	if (hipGetLastError() != hipSuccess || hipMemcpy(d + words, r->d_positions, (r->n_entries + 16) * 4, hipMemcpyDeviceToDevice) != hipSuccess ||
-			hipDeviceSynchronize() != hipSuccess) { (void) hipFree(d); ngm::pipeline_set_error("building the buckets failed"); return -5; }
+	Buf<uint32_t> d;
+	NGM_MEM_TRY(d.alloc(words + r->n_entries + 16));
+	hipLaunchKernelGGL(fill_buckets_kernel, dim3((unsigned) ((words + 255) / 256)), dim3(256), 0, 0, n_kmers, k, lw, r->d_index.p, r->d_positions.p, d.p);
+	if (hipGetLastError() != hipSuccess || hipMemcpy(d.p + words, r->d_positions.p, (r->n_entries + 16) * 4, hipMemcpyDeviceToDevice) != hipSuccess ||
+			hipDeviceSynchronize() != hipSuccess) { ngm::pipeline_set_error("building the buckets failed"); return -5; }
 	r->bucket_log2_words = lw;
 	r->bucket_pos_base = (uint32_t) words;
-	r->d_buckets = d;
+	r->d_buckets = std::move(d);
 	return 0;
 }
 
 int build_index(ngm_ref *r) {
 	const int k = r->prm.kmer;
 	const uint32_t n_kmers = 1u << (2 * k);
-	uint32_t *d_keys = nullptr, *d_vals = nullptr, *d_keys2 = nullptr, *d_starts = nullptr;
+	Buf<uint32_t> d_keys, d_vals, d_keys2, d_starts;
 	uint64_t n = 0;
 	WalkEnd end;
 	// NGM_HIP_TEST_LIMITS=host_walk=1: the host walk below, as taken when the GPU walk runs out of memory
@@ -700,10 +686,10 @@ int build_index(ngm_ref *r) {
 	if (!host_walk) {
 		// the walk on the GPU (CountKmerFreq decodes a contig with bufferLength = len and DecodeRefSequence emits len - 2 bases,
 		// 'x' / NUL after that, which encode() maps to 0: the last two bases of a contig act as 'A' -- handled in the kernels)
-		if (gpu_kmer_walk(r, &d_keys, &d_vals, &n, &end) != 0) { d_keys = d_vals = nullptr; n = 0; end = WalkEnd(); (void) hipGetLastError(); }  // e.g. out of memory on a shared GPU: the host walk needs no scratch
+		if (gpu_kmer_walk(r, d_keys, d_vals, &n, &end) != 0) { n = 0; end = WalkEnd(); (void) hipGetLastError(); }  // e.g. out of memory on a shared GPU: the host walk needs no scratch
 	}
-	const bool walked_on_host = !d_keys;
-	if (!d_keys) {
+	const bool walked_on_host = !d_keys.p;
+	if (walked_on_host) {
 		std::vector<uint32_t> keys, vals;
 		keys.reserve(r->n_bases / (r->prm.kmer_skip + 1) + 16);
 		vals.reserve(r->n_bases / (r->prm.kmer_skip + 1) + 16);
@@ -721,25 +707,23 @@ int build_index(ngm_ref *r) {
 		}
 		end.visited = w.visited; end.last_prefix = w.last_prefix; end.last_bin = w.last_bin;
 		n = keys.size();
-		REF_HIP_TRY(hipMalloc(&d_keys, std::max<uint64_t>(n, 1) * 4));
-		REF_HIP_TRY(hipMalloc(&d_vals, std::max<uint64_t>(n, 1) * 4));
-		REF_HIP_TRY(hipMemcpy(d_keys, keys.data(), n * 4, hipMemcpyHostToDevice));
-		REF_HIP_TRY(hipMemcpy(d_vals, vals.data(), n * 4, hipMemcpyHostToDevice));
+		NGM_MEM_TRY(d_keys.alloc(std::max<uint64_t>(n, 1)));
+		NGM_MEM_TRY(d_vals.alloc(std::max<uint64_t>(n, 1)));
+		REF_HIP_TRY(hipMemcpy(d_keys.p, keys.data(), n * 4, hipMemcpyHostToDevice));
+		REF_HIP_TRY(hipMemcpy(d_vals.p, vals.data(), n * 4, hipMemcpyHostToDevice));
 	}
 	VcfEntries ve;
 	if (r->vcf) {
 		// the variants' fill-pass entries go behind the genome's, so the stable sort keeps each list in the reference's order
-		if (int rc = build_vcf_entries(r, end, walked_on_host, ve)) { (void) hipFree(d_keys); (void) hipFree(d_vals); return rc; }
-		uint32_t *k2 = nullptr, *v2 = nullptr;
-		if (hipMalloc(&k2, std::max<uint64_t>(n + ve.nf, 1) * 4) != hipSuccess || hipMalloc(&v2, std::max<uint64_t>(n + ve.nf, 1) * 4) != hipSuccess) {
-			(void) hipFree(k2); (void) hipFree(d_keys); (void) hipFree(d_vals);
+		if (int rc = build_vcf_entries(r, end, walked_on_host, ve)) return rc;
+		Buf<uint32_t> k2, v2;
+		if (k2.alloc(std::max<uint64_t>(n + ve.nf, 1)) || v2.alloc(std::max<uint64_t>(n + ve.nf, 1))) {
 			ngm::pipeline_set_error("out of device memory adding the VCF's k-mers");
 			return -12;
 		}
-		REF_HIP_TRY(hipMemcpy(k2, d_keys, n * 4, hipMemcpyDeviceToDevice)); REF_HIP_TRY(hipMemcpy(v2, d_vals, n * 4, hipMemcpyDeviceToDevice));
-		REF_HIP_TRY(hipMemcpy(k2 + n, ve.d_fkeys, ve.nf * 4, hipMemcpyDeviceToDevice)); REF_HIP_TRY(hipMemcpy(v2 + n, ve.d_fvals, ve.nf * 4, hipMemcpyDeviceToDevice));
-		(void) hipFree(d_keys); (void) hipFree(d_vals);
-		d_keys = k2; d_vals = v2;
+		REF_HIP_TRY(hipMemcpy(k2.p, d_keys.p, n * 4, hipMemcpyDeviceToDevice)); REF_HIP_TRY(hipMemcpy(v2.p, d_vals.p, n * 4, hipMemcpyDeviceToDevice));
+		REF_HIP_TRY(hipMemcpy(k2.p + n, ve.d_fkeys.p, ve.nf * 4, hipMemcpyDeviceToDevice)); REF_HIP_TRY(hipMemcpy(v2.p + n, ve.d_fvals.p, ve.nf * 4, hipMemcpyDeviceToDevice));
+		d_keys = std::move(k2); d_vals = std::move(v2);   // (the genome's own lists go here)
 		const uint64_t genome_skips = end.visited - n;
 		r->vcf_skip_count = genome_skips + ve.visited - ve.nc;
 		r->vcf_skip_build = genome_skips + ve.visited - ve.nf;
@@ -749,84 +733,82 @@ int build_index(ngm_ref *r) {
 		n += ve.nf;
 	}
 	r->n_entries = n;
-	REF_HIP_TRY(hipMalloc(&d_keys2, std::max<uint64_t>(n, 1) * 4));
-	REF_HIP_TRY(hipMalloc(&r->d_positions, (std::max<uint64_t>(n, 1) + 16) * 4));  // the search reads 16-entry segments
-	REF_HIP_TRY(hipMemset(r->d_positions, 0, (std::max<uint64_t>(n, 1) + 16) * 4));
-	REF_HIP_TRY(hipMalloc(&d_starts, (size_t) n_kmers * 4));
-	REF_HIP_TRY(hipMalloc(&r->d_raw_counts, (size_t) n_kmers * 4));
-	REF_HIP_TRY(hipMalloc(&r->d_index, (size_t) n_kmers * sizeof(uint2)));
-	REF_HIP_TRY(hipMemset(d_starts, 0, (size_t) n_kmers * 4));
-	REF_HIP_TRY(hipMemset(r->d_raw_counts, 0, (size_t) n_kmers * 4));
+	NGM_MEM_TRY(d_keys2.alloc(std::max<uint64_t>(n, 1)));
+	NGM_MEM_TRY(r->d_positions.alloc(std::max<uint64_t>(n, 1) + 16));  // the search reads 16-entry segments
+	REF_HIP_TRY(hipMemset(r->d_positions.p, 0, (std::max<uint64_t>(n, 1) + 16) * 4));
+	NGM_MEM_TRY(d_starts.alloc(n_kmers));
+	NGM_MEM_TRY(r->d_raw_counts.alloc(n_kmers));
+	NGM_MEM_TRY(r->d_index.alloc(n_kmers));
+	REF_HIP_TRY(hipMemset(d_starts.p, 0, (size_t) n_kmers * 4));
+	REF_HIP_TRY(hipMemset(r->d_raw_counts.p, 0, (size_t) n_kmers * 4));
 	if (n > 0) {
 		// stable LSD radix sort on the 2k key bits: inside each k-mer group the entries keep their input order -- ascending genome
 		// positions, which is the order BuildPrefixTable appends them in (PrefixTable.cpp:729-748), followed with --vcf by the
 		// variant regions' entries in VCF order (not ascending, and a position may repeat: refindex.h)
 		size_t tmp_bytes = 0;
-		REF_HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_keys, d_keys2, d_vals, r->d_positions, n, 0, 2 * k));
-		void *d_tmp = nullptr;
-		REF_HIP_TRY(hipMalloc(&d_tmp, tmp_bytes));
-		REF_HIP_TRY(rocprim::radix_sort_pairs(d_tmp, tmp_bytes, d_keys, d_keys2, d_vals, r->d_positions, n, 0, 2 * k));
-		hipLaunchKernelGGL(mark_runs_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, 0, d_keys2, n, d_starts, r->d_raw_counts);
+		REF_HIP_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, d_keys.p, d_keys2.p, d_vals.p, r->d_positions.p, n, 0, 2 * k));
+		Buf<uint8_t> d_tmp;
+		NGM_MEM_TRY(d_tmp.alloc(tmp_bytes));
+		REF_HIP_TRY(rocprim::radix_sort_pairs(d_tmp.p, tmp_bytes, d_keys.p, d_keys2.p, d_vals.p, r->d_positions.p, n, 0, 2 * k));
+		hipLaunchKernelGGL(mark_runs_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, 0, d_keys2.p, n, d_starts.p, r->d_raw_counts.p);
 		REF_HIP_TRY(hipGetLastError());
 		REF_HIP_TRY(hipDeviceSynchronize());
-		(void) hipFree(d_tmp);
-	}
-	hipLaunchKernelGGL(finish_index_kernel, dim3((n_kmers + 255) / 256), dim3(256), 0, 0, n_kmers, k, d_starts, r->d_raw_counts, r->d_index);
+	}   // (the sort's storage goes here)
+	hipLaunchKernelGGL(finish_index_kernel, dim3((n_kmers + 255) / 256), dim3(256), 0, 0, n_kmers, k, d_starts.p, r->d_raw_counts.p, r->d_index.p);
 	if (r->vcf) {
 		// every list gets the count pass's number of slots (PrefixTable.cpp:360-374): its entries so far, then zeros
-		if (ve.nc) hipLaunchKernelGGL(vcf_slot_delta_kernel, dim3((unsigned) ((ve.nc + 255) / 256)), dim3(256), 0, 0, ve.d_ckeys, ve.nc, 1, r->d_raw_counts);
-		if (ve.nf) hipLaunchKernelGGL(vcf_slot_delta_kernel, dim3((unsigned) ((ve.nf + 255) / 256)), dim3(256), 0, 0, ve.d_fkeys, ve.nf, -1, r->d_raw_counts);
+		if (ve.nc) hipLaunchKernelGGL(vcf_slot_delta_kernel, dim3((unsigned) ((ve.nc + 255) / 256)), dim3(256), 0, 0, ve.d_ckeys.p, ve.nc, 1, r->d_raw_counts.p);
+		if (ve.nf) hipLaunchKernelGGL(vcf_slot_delta_kernel, dim3((unsigned) ((ve.nf + 255) / 256)), dim3(256), 0, 0, ve.d_fkeys.p, ve.nf, -1, r->d_raw_counts.p);
 		REF_HIP_TRY(hipGetLastError());
 		// new list starts: exclusive scan of the new lengths (in 64 bits, so that a table beyond 2^32 entries is caught)
 		uint64_t total = 0;
 		{
-			uint64_t *d_start64 = nullptr;
-			void *d_scan = nullptr;
+			Buf<uint64_t> d_start64;
+			Buf<uint8_t> d_scan;
 			size_t sb = 0;
-			auto widen = rocprim::make_transform_iterator(r->d_raw_counts, [] __host__ __device__ (uint32_t x) { return (uint64_t) x; });
-			REF_HIP_TRY(rocprim::exclusive_scan(nullptr, sb, widen, d_start64, (uint64_t) 0, (size_t) n_kmers, rocprim::plus<uint64_t>()));
-			REF_HIP_TRY(hipMalloc(&d_start64, (size_t) n_kmers * 8));
-			if (hipMalloc(&d_scan, sb + 256) != hipSuccess) { (void) hipFree(d_start64); ngm::pipeline_set_error("out of device memory (VCF list starts)"); return -12; }
-			const hipError_t e1 = rocprim::exclusive_scan(d_scan, sb, widen, d_start64, (uint64_t) 0, (size_t) n_kmers, rocprim::plus<uint64_t>());
+			auto widen = rocprim::make_transform_iterator(r->d_raw_counts.p, [] __host__ __device__ (uint32_t x) { return (uint64_t) x; });
+			REF_HIP_TRY(rocprim::exclusive_scan(nullptr, sb, widen, d_start64.p, (uint64_t) 0, (size_t) n_kmers, rocprim::plus<uint64_t>()));
+			NGM_MEM_TRY(d_start64.alloc(n_kmers));
+			if (d_scan.alloc(sb + 256)) { ngm::pipeline_set_error("out of device memory (VCF list starts)"); return -12; }
+			const hipError_t e1 = rocprim::exclusive_scan(d_scan.p, sb, widen, d_start64.p, (uint64_t) 0, (size_t) n_kmers, rocprim::plus<uint64_t>());
 			uint64_t last_start = 0;
 			uint32_t last_raw = 0;
-			const hipError_t e2 = hipMemcpy(&last_start, d_start64 + n_kmers - 1, 8, hipMemcpyDeviceToHost);
-			const hipError_t e3 = hipMemcpy(&last_raw, r->d_raw_counts + n_kmers - 1, 4, hipMemcpyDeviceToHost);
+			const hipError_t e2 = hipMemcpy(&last_start, d_start64.p + n_kmers - 1, 8, hipMemcpyDeviceToHost);
+			const hipError_t e3 = hipMemcpy(&last_raw, r->d_raw_counts.p + n_kmers - 1, 4, hipMemcpyDeviceToHost);
 			total = last_start + last_raw;
 			if (e1 == hipSuccess && e2 == hipSuccess && e3 == hipSuccess && total + 16 < 0xFFFFFFFFull)
-				hipLaunchKernelGGL(vcf_narrow_kernel, dim3((n_kmers + 255) / 256), dim3(256), 0, 0, n_kmers, d_start64, d_starts);
-			(void) hipFree(d_scan);
+				hipLaunchKernelGGL(vcf_narrow_kernel, dim3((n_kmers + 255) / 256), dim3(256), 0, 0, n_kmers, d_start64.p, d_starts.p);
+			d_scan.release();
 			const hipError_t e4 = hipDeviceSynchronize();
-			(void) hipFree(d_start64);
+			d_start64.release();
 			if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess) { ngm::pipeline_set_error("scanning the VCF list lengths failed"); return -5; }
 			if (total + 16 >= 0xFFFFFFFFull) { ngm::pipeline_set_error("k-mer table with the VCF's k-mers exceeds 2^32 entries"); return -27; }
 		}
-		uint32_t *d_final = nullptr;
-		unsigned int *d_over = nullptr;
-		REF_HIP_TRY(hipMalloc(&d_final, (total + 16) * 4));
-		REF_HIP_TRY(hipMemset(d_final, 0, (total + 16) * 4));
-		REF_HIP_TRY(hipMalloc(&d_over, 4));
-		REF_HIP_TRY(hipMemset(d_over, 0, 4));
-		if (n) hipLaunchKernelGGL(vcf_scatter_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, 0, d_keys2, r->d_positions, n, r->d_index, d_starts, r->d_raw_counts, d_final, d_over);
-		hipLaunchKernelGGL(vcf_index_kernel, dim3((n_kmers + 255) / 256), dim3(256), 0, 0, n_kmers, d_starts, r->d_raw_counts, r->d_index);
+		Buf<uint32_t> d_final;
+		Buf<unsigned int> d_over;
+		NGM_MEM_TRY(d_final.alloc(total + 16));
+		REF_HIP_TRY(hipMemset(d_final.p, 0, (total + 16) * 4));
+		NGM_MEM_TRY(d_over.alloc(1));
+		REF_HIP_TRY(hipMemset(d_over.p, 0, 4));
+		if (n) hipLaunchKernelGGL(vcf_scatter_kernel, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, 0, d_keys2.p, r->d_positions.p, n, r->d_index.p, d_starts.p, r->d_raw_counts.p, d_final.p, d_over.p);
+		hipLaunchKernelGGL(vcf_index_kernel, dim3((n_kmers + 255) / 256), dim3(256), 0, 0, n_kmers, d_starts.p, r->d_raw_counts.p, r->d_index.p);
 		REF_HIP_TRY(hipGetLastError());
 		unsigned int over = 0;
-		REF_HIP_TRY(hipMemcpy(&over, d_over, 4, hipMemcpyDeviceToHost));
-		(void) hipFree(d_over);
-		(void) hipFree(r->d_positions);
-		r->d_positions = d_final;
+		REF_HIP_TRY(hipMemcpy(&over, d_over.p, 4, hipMemcpyDeviceToHost));
+		d_over.release();
+		r->d_positions = std::move(d_final);   // (the table without the zero slots goes here)
 		r->n_entries = n = total;
 		// (the fill pass never stores more into a list than the count pass reserved: the two differ in the first two visited
 		// k-mers of a region only, where the count pass stores and the fill pass may skip)
 		if (over) { ngm::pipeline_set_error("VCF k-mers: the fill pass stored more entries than the count pass reserved (%u)", over); return -75; }
 	}
-	hipLaunchKernelGGL(apply_usage_rule_kernel, dim3((n_kmers + 255) / 256), dim3(256), 0, 0, n_kmers, k, r->d_raw_counts, r->d_index);
+	hipLaunchKernelGGL(apply_usage_rule_kernel, dim3((n_kmers + 255) / 256), dim3(256), 0, 0, n_kmers, k, r->d_raw_counts.p, r->d_index.p);
 	REF_HIP_TRY(hipGetLastError());
 	REF_HIP_TRY(hipDeviceSynchronize());
-	(void) hipFree(d_keys); (void) hipFree(d_vals); (void) hipFree(d_keys2); (void) hipFree(d_starts);
+	d_keys.release(); d_vals.release(); d_keys2.release(); d_starts.release();   // (before the statistics' host array)
 
 	std::vector<uint32_t> raw(n_kmers);
-	REF_HIP_TRY(hipMemcpy(raw.data(), r->d_raw_counts, (size_t) n_kmers * 4, hipMemcpyDeviceToHost));
+	REF_HIP_TRY(hipMemcpy(raw.data(), r->d_raw_counts.p, (size_t) n_kmers * 4, hipMemcpyDeviceToHost));
 	index_stats(r, raw.data(), (uint32_t) raw.size());
 	return 0;   // the bucket layouts are built when the first mapper asks for one (ngm_ref_ensure_buckets): a bisulfite run needs none
 }
@@ -854,15 +836,16 @@ void index_stats(ngm_ref *r, const uint32_t *raw, uint32_t n_kmers) {
 int upload_staged(void *dst, const void *src, size_t bytes) {
 	constexpr size_t kPiece = (size_t) 32 << 20;
 	if (bytes <= kPiece) { REF_HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice)); return 0; }
-	void *stage[2] = {nullptr, nullptr};
+	ngm::PinnedBuf<char> stage[2];
 	hipEvent_t done[2] = {nullptr, nullptr};
 	hipStream_t st = nullptr;
 	int rc = 0;
-	auto cleanup = [&] { for (int i = 0; i < 2; ++i) { if (stage[i]) (void) hipHostFree(stage[i]); if (done[i]) (void) hipEventDestroy(done[i]); } if (st) (void) hipStreamDestroy(st); };
-	if (hipHostMalloc(&stage[0], kPiece, hipHostMallocDefault) != hipSuccess || hipHostMalloc(&stage[1], kPiece, hipHostMallocDefault) != hipSuccess ||
+	auto cleanup = [&] { for (hipEvent_t e : done) if (e) (void) hipEventDestroy(e); if (st) (void) hipStreamDestroy(st); };   // (the two buffers free themselves)
+	if (stage[0].alloc(kPiece) || stage[1].alloc(kPiece) ||
 			hipEventCreateWithFlags(&done[0], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&done[1], hipEventDisableTiming) != hipSuccess ||
 			hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) {
 		cleanup();
+		stage[0].release(); stage[1].release();   // (early: the plain copy stages through page-locked memory of the runtime's own)
 		REF_HIP_TRY(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));   // (no page-locked memory left: the plain copy)
 		return 0;
 	}
@@ -872,7 +855,7 @@ int upload_staged(void *dst, const void *src, size_t bytes) {
 		const size_t nb = std::min(kPiece, bytes - off);
 		if (off >= 2 * kPiece && hipEventSynchronize(done[turn]) != hipSuccess) { rc = -5; break; }
 		const char *from = (const char *) src + off;
-		char *to = (char *) stage[turn];
+		char *to = stage[turn].p;
 		const int parts = (int) ((nb + (1u << 20) - 1) >> 20);
 		pool.parallel_for(parts, [&](int lo, int hi) { const size_t a = (size_t) lo << 20, b = std::min(nb, (size_t) hi << 20); memcpy(to + a, from + a, b - a); }, 1);
 		if (hipMemcpyAsync((char *) dst + off, to, nb, hipMemcpyHostToDevice, st) != hipSuccess || hipEventRecord(done[turn], st) != hipSuccess) rc = -5;
@@ -908,8 +891,8 @@ int upload_genome(ngm_ref *r) {
 			}
 		}, 1);
 	}
-	REF_HIP_TRY(hipMalloc(&r->d_genome, r->genome_words * 4));
-	return upload_staged(r->d_genome, packed.data(), r->genome_words * 4);
+	NGM_MEM_TRY(r->d_genome.alloc(r->genome_words));
+	return upload_staged(r->d_genome.p, packed.data(), r->genome_words * 4);
 }
 
 int finish_ref(ngm_ref *r) {
@@ -1119,14 +1102,14 @@ ngm_ref *ngm_ref_create_from_cache(int device, const ngm_ref_params *p, const ch
 	if (upload_genome(r) != 0) { ngm_ref_destroy(r); return nullptr; }
 	lap("sequence packed and copied");
 	const size_t pos_alloc = ((size_t) table_len + 16) * 4;
-	if (hipMalloc((void **) &r->d_index, (size_t) n_kmers * 8) != hipSuccess || hipMalloc((void **) &r->d_raw_counts, (size_t) n_kmers * 4) != hipSuccess ||
-			hipMalloc((void **) &r->d_positions, pos_alloc) != hipSuccess || hipMemset((char *) r->d_positions + pos_bytes, 0, pos_alloc - pos_bytes) != hipSuccess) {
+	if (r->d_index.alloc(n_kmers) || r->d_raw_counts.alloc(n_kmers) ||
+			r->d_positions.alloc((size_t) table_len + 16) || hipMemset((char *) r->d_positions.p + pos_bytes, 0, pos_alloc - pos_bytes) != hipSuccess) {
 		ngm::pipeline_set_error("out of device memory loading the index cache");
 		ngm_ref_destroy(r);
 		return nullptr;
 	}
-	if (upload_staged(r->d_index, idx.data(), (size_t) n_kmers * 8) != 0 || upload_staged(r->d_raw_counts, raw.data(), (size_t) n_kmers * 4) != 0 ||
-			upload_staged(r->d_positions, pos, pos_bytes) != 0) { ngm_ref_destroy(r); return nullptr; }
+	if (upload_staged(r->d_index.p, idx.data(), (size_t) n_kmers * 8) != 0 || upload_staged(r->d_raw_counts.p, raw.data(), (size_t) n_kmers * 4) != 0 ||
+			upload_staged(r->d_positions.p, pos, pos_bytes) != 0) { ngm_ref_destroy(r); return nullptr; }
 	lap("k-mer table copied");
 	index_stats(r, raw.data(), n_kmers);
 	r->from_cache = true;
@@ -1212,12 +1195,6 @@ int ngm_ref_vcf_skip_counts(const ngm_ref *r, uint64_t out[2]) {
 void ngm_ref_destroy(ngm_ref *r) {
 	if (!r) return;
 	(void) hipSetDevice(r->device);
-	if (r->d_genome) (void) hipFree(r->d_genome);
-	if (r->d_index) (void) hipFree(r->d_index);
-	if (r->d_raw_counts) (void) hipFree(r->d_raw_counts);
-	if (r->d_positions) (void) hipFree(r->d_positions);
-	if (r->d_buckets) (void) hipFree(r->d_buckets);
-	if (r->d_cbuckets) (void) hipFree(r->d_cbuckets);
 	delete r;
 }
 
@@ -1263,11 +1240,11 @@ int ngm_ref_index_copy(const ngm_ref *r, uint32_t *counts, uint32_t *raw_counts,
 	const uint32_t n_kmers = 1u << (2 * r->prm.kmer);
 	if (counts) {
 		std::vector<uint2> idx(n_kmers);
-		REF_HIP_TRY(hipMemcpy(idx.data(), r->d_index, (size_t) n_kmers * sizeof(uint2), hipMemcpyDeviceToHost));
+		REF_HIP_TRY(hipMemcpy(idx.data(), r->d_index.p, (size_t) n_kmers * sizeof(uint2), hipMemcpyDeviceToHost));
 		for (uint32_t i = 0; i < n_kmers; ++i) counts[i] = idx[i].y;
 	}
-	if (raw_counts) REF_HIP_TRY(hipMemcpy(raw_counts, r->d_raw_counts, (size_t) n_kmers * 4, hipMemcpyDeviceToHost));
-	if (positions && r->n_entries) REF_HIP_TRY(hipMemcpy(positions, r->d_positions, r->n_entries * 4, hipMemcpyDeviceToHost));
+	if (raw_counts) REF_HIP_TRY(hipMemcpy(raw_counts, r->d_raw_counts.p, (size_t) n_kmers * 4, hipMemcpyDeviceToHost));
+	if (positions && r->n_entries) REF_HIP_TRY(hipMemcpy(positions, r->d_positions.p, r->n_entries * 4, hipMemcpyDeviceToHost));
 	return 0;
 }
 
@@ -1330,10 +1307,10 @@ int ngm_ref_write_ngm_cache(const ngm_ref *r, const char *fasta_path) {
 		cf.put(&cookie, 4, 1); cf.put(&kk, 4, 1); cf.put(&skip, 4, 1); cf.put(&units, 4, 1); cf.put(&index_size, 4, 1);
 		std::vector<uint32_t> raw(n_kmers);
 		std::vector<uint2> idx(n_kmers);
-		REF_HIP_TRY(hipMemcpy(raw.data(), r->d_raw_counts, (size_t) n_kmers * 4, hipMemcpyDeviceToHost));
-		REF_HIP_TRY(hipMemcpy(idx.data(), r->d_index, (size_t) n_kmers * 8, hipMemcpyDeviceToHost));
+		REF_HIP_TRY(hipMemcpy(raw.data(), r->d_raw_counts.p, (size_t) n_kmers * 4, hipMemcpyDeviceToHost));
+		REF_HIP_TRY(hipMemcpy(idx.data(), r->d_index.p, (size_t) n_kmers * 8, hipMemcpyDeviceToHost));
 		std::vector<uint32_t> pos(r->n_entries + 1, 0);
-		if (r->n_entries) REF_HIP_TRY(hipMemcpy(pos.data(), r->d_positions, r->n_entries * 4, hipMemcpyDeviceToHost));
+		if (r->n_entries) REF_HIP_TRY(hipMemcpy(pos.data(), r->d_positions.p, r->n_entries * 4, hipMemcpyDeviceToHost));
 		const uint32_t table_len = (uint32_t) r->n_entries;
 		cf.put(&table_len, 4, 1);
 		// Index { uint m_TabIndex; char m_RevCompIndex; } packed to 5 bytes (PrefixTable.h:18-61)

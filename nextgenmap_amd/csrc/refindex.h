@@ -43,6 +43,7 @@
 #include <vector>
 
 #include "../../include/ngm_pipeline.h"
+#include "device_mem.h"
 
 namespace ngm {
 // std::vector whose resize() leaves new elements uninitialised: the multi-GB host arrays of the reference are filled by all pool
@@ -73,12 +74,12 @@ struct ngm_ref {
 	int auto_max_kfreq = 100;
 	bool from_cache = false;          // loaded from NextGenMap's cache files instead of being built
 	// device
-	uint32_t *d_genome = nullptr;
+	ngm::Buf<uint32_t> d_genome;
 	uint64_t genome_words = 0;
-	uint2 *d_index = nullptr;
-	uint32_t *d_raw_counts = nullptr;
-	uint32_t *d_positions = nullptr;
-	uint32_t *d_buckets = nullptr;
+	ngm::Buf<uint2> d_index;
+	ngm::Buf<uint32_t> d_raw_counts;
+	ngm::Buf<uint32_t> d_positions;
+	ngm::Buf<uint32_t> d_buckets;
 	int bucket_log2_words = 2;        // W = 1 << bucket_log2_words dwords per k-mer bucket
 	uint32_t bucket_pos_base = 0;     // word offset of the position table copy that follows the buckets in d_buckets
 	double overflow_hit_share = 0.0;  // share of all index entries that live in lists longer than W-1
@@ -91,7 +92,7 @@ struct ngm_ref {
 	// W = 4..64 dwords from the mean length of both lists (GRCh38 size: 30.8 -> 64 dwords = two 128-byte lines, the second one
 	// only read for the ~45 % of the pairs with more than 31 positions).  Same allocation scheme: a copy of the position table
 	// follows the buckets.
-	uint32_t *d_cbuckets = nullptr;
+	ngm::Buf<uint32_t> d_cbuckets;
 	int cbucket_log2_words = 2;
 	uint32_t cbucket_pos_base = 0;
 	// --vcf (PrefixTable.cpp:223-228, :500-574): the variants of the VCF in file order, applied by build_index; and what came of them

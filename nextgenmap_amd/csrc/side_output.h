@@ -200,13 +200,13 @@ struct LineStream {
 	// flagged slots; *last_depth: the depth behind the chunk.  The chunk's text starts empty and next_slot moves behind the chunk.
 	template <typename Launch>
 	int scan_and_select(Base &b, int32_t *depth, int32_t carry, size_t n, Launch flag_launch, uint32_t *m, int32_t *last_depth) {
-		size_t tb = tmp.n;
+		size_t tb = tmp.cap;
 		NGM_HIP_TRY(hipEventRecord(b.ev[0], b.st));
 		NGM_HIP_TRY(rocprim::inclusive_scan(tmp.p, tb, depth, depth, carry, n, rocprim::plus<int32_t>(), b.st));
 		NGM_HIP_TRY(hipEventRecord(b.ev[1], b.st));
 		flag_launch();
 		NGM_HIP_TRY(hipGetLastError());
-		tb = tmp.n;
+		tb = tmp.cap;
 		NGM_HIP_TRY(rocprim::select(tmp.p, tb, rocprim::counting_iterator<uint32_t>(0), flag.p, idx.p, d_m.p, n, b.st));
 		NGM_HIP_TRY(hipEventRecord(b.ev[2], b.st));
 		NGM_HIP_TRY(hipMemcpyAsync(m, d_m.p, 4, hipMemcpyDeviceToHost, b.st));
@@ -233,7 +233,7 @@ struct LineStream {
 		flag_launch();
 		NGM_HIP_TRY(hipGetLastError());
 		NGM_HIP_TRY(hipEventRecord(b.ev[1], b.st));
-		size_t tb = tmp.n;
+		size_t tb = tmp.cap;
 		NGM_HIP_TRY(rocprim::select(tmp.p, tb, rocprim::counting_iterator<uint32_t>(0), flag.p, idx.p, d_m.p, n, b.st));
 		NGM_HIP_TRY(hipEventRecord(b.ev[2], b.st));
 		NGM_HIP_TRY(hipMemcpyAsync(m, d_m.p, 4, hipMemcpyDeviceToHost, b.st));

@@ -76,10 +76,10 @@ extern "C" ngm_snp *ngm_snp_create(const ngm_snp_params *p) {
 }
 
 extern "C" ngm_snp *ngm_snp_create_for_ref(const ngm_ref *r, const ngm_snp_params *p) {
-	if (!r || !p || !r->d_genome) { ngm::pipeline_set_error("ngm_snp_create_for_ref: bad arguments"); return nullptr; }
+	if (!r || !p || !r->d_genome.p) { ngm::pipeline_set_error("ngm_snp_create_for_ref: bad arguments"); return nullptr; }
 	side::RefView ref;
 	if (!ref.from_ref("ngm_snp_create_for_ref", *r)) return nullptr;
-	return create(p, r->device, ref, r->d_genome);   // (the reference outlives the run's caller)
+	return create(p, r->device, ref, r->d_genome.p);   // (the reference outlives the run's caller)
 }
 
 extern "C" void ngm_snp_destroy(ngm_snp *c) { side::destroy(c); }

@@ -32,7 +32,7 @@ struct ngm_stats_comm {
 	int device = 0, rank = 0, world = 1;
 	ncclComm_t comm = nullptr;
 	hipStream_t st = nullptr;
-	int64_t *d_buf = nullptr;
+	ngm::Buf<int64_t> d_buf;
 };
 
 namespace {
@@ -98,7 +98,7 @@ ngm_stats_comm *ngm_stats_comm_create(int device, int rank, int world, const cha
 	c->device = device; c->rank = rank; c->world = world;
 	const ncclResult_t e = R.CommInitRank(&c->comm, world, id, rank);
 	if (e != ncclSuccess) { ngm::pipeline_set_error("ncclCommInitRank (rank %d of %d, device %d): %s", rank, world, device, nccl_err(e)); delete c; return nullptr; }
-	if (hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking) != hipSuccess || hipMalloc(&c->d_buf, 8 * sizeof(int64_t)) != hipSuccess) {
+	if (hipStreamCreateWithFlags(&c->st, hipStreamNonBlocking) != hipSuccess || c->d_buf.alloc(8)) {
 		ngm::pipeline_set_error("out of device memory (stats all-reduce)");
 		ngm_stats_comm_destroy(c);
 		return nullptr;
@@ -110,10 +110,10 @@ int ngm_stats_allreduce(ngm_stats_comm *c, int64_t v[8]) {
 	if (!c || !c->comm || !v) return -22;
 	Rccl &R = rccl();
 	if (hipSetDevice(c->device) != hipSuccess) return -5;
-	if (hipMemcpyAsync(c->d_buf, v, 8 * sizeof(int64_t), hipMemcpyHostToDevice, c->st) != hipSuccess) { ngm::pipeline_set_error("stats all-reduce: upload failed"); return -5; }
-	const ncclResult_t e = R.AllReduce(c->d_buf, c->d_buf, 8, ncclInt64, ncclSum, c->comm, c->st);
+	if (hipMemcpyAsync(c->d_buf.p, v, 8 * sizeof(int64_t), hipMemcpyHostToDevice, c->st) != hipSuccess) { ngm::pipeline_set_error("stats all-reduce: upload failed"); return -5; }
+	const ncclResult_t e = R.AllReduce(c->d_buf.p, c->d_buf.p, 8, ncclInt64, ncclSum, c->comm, c->st);
 	if (e != ncclSuccess) { ngm::pipeline_set_error("ncclAllReduce: %s", nccl_err(e)); return -5; }
-	if (hipMemcpyAsync(v, c->d_buf, 8 * sizeof(int64_t), hipMemcpyDeviceToHost, c->st) != hipSuccess || hipStreamSynchronize(c->st) != hipSuccess) {
+	if (hipMemcpyAsync(v, c->d_buf.p, 8 * sizeof(int64_t), hipMemcpyDeviceToHost, c->st) != hipSuccess || hipStreamSynchronize(c->st) != hipSuccess) {
 		ngm::pipeline_set_error("stats all-reduce: download failed");
 		return -5;
 	}
@@ -124,7 +124,6 @@ void ngm_stats_comm_destroy(ngm_stats_comm *c) {
 	if (!c) return;
 	(void) hipSetDevice(c->device);
 	if (c->st) { (void) hipStreamSynchronize(c->st); (void) hipStreamDestroy(c->st); }
-	if (c->d_buf) (void) hipFree(c->d_buf);
 	if (c->comm && rccl().CommDestroy) (void) rccl().CommDestroy(c->comm);
 	delete c;
 }

@@ -193,12 +193,22 @@ def _lib():
         lib.ngm_methyl_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.ngm_mapper_set_methyl.argtypes = [C.c_void_p, C.c_void_p]
         lib.ngm_mapper_set_count.argtypes = [C.c_void_p, C.c_void_p]
+        lib.ngm_debug_live_memory.argtypes = [C.c_void_p]
         _bound = True
     return lib
 
 
 def _err():
     return NgmHipError(_lib().ngm_pipeline_last_error().decode())
+
+
+def live_memory():
+    """what the library holds in this process (ngm_debug_live_memory): device bytes live, pinned host bytes live, device allocations so
+    far, pinned allocations so far"""
+    out = np.zeros(4, np.uint64)
+    if _lib().ngm_debug_live_memory(out.ctypes.data) < 0:
+        raise _err()
+    return dict(zip(("device_bytes", "pinned_bytes", "device_allocations", "pinned_allocations"), (int(x) for x in out)))
 
 
 class Bgzf:
