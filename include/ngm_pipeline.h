@@ -581,6 +581,30 @@ int ngm_debug_select_top1(int device, int n_reads, const uint32_t *base, const u
 int ngm_debug_align_finish(void *engine /* ngm_hip_ctx * */, int mode, int n, const char *const *ref, const char *const *qry, void *out /* ngm_hip_align_out[n] */,
 		uint64_t *n_fallback);
 
+/* test hook: ngm_hip_batch_align (include/ngm_hip.h) of a LINEAR engine the way the mapper's align stage of a default run builds its strings: pack,
+ * DP + traceback, compact_runs_kernel, cigar_strings_kernel<false> (csrc/cigar_device.h) -- through the launch code the align stage runs -- then
+ * the downloads.  dir: the pairs' direction bytes (alt_scoring / alt_cigar engines) or NULL; capacity: bytes of the string stream, 0 = the
+ * mapper's n * 96 + 4096.  out[i] is taken from the device's stream where the kernel built the strings (built_by[i] = 1), and made by the
+ * host's builder from the compacted runs otherwise (built_by[i] = 0: a string beyond the kernel's row, a read symbol outside ACGTN, a full
+ * stream) -- as the mapper does.  *cursor: the stream cursor's final value (all bytes asked for, beyond capacity when the stream was full).
+ * Returns n (0 for n <= 0), or a negative error code (ngm_hip_last_error of the engine); -22, before anything is taken, for an engine of the
+ * affine personality.  tests/test_gpu_linear_strings.py compares it with the CPU oracle. */
+int ngm_debug_linear_strings(void *engine /* ngm_hip_ctx * */, int mode, int n, const char *const *ref, const char *const *qry, const char *dir, uint64_t capacity,
+		void *out /* ngm_hip_align_out[n] */, uint8_t *built_by, uint64_t *cursor);
+
+/* test hook: gather_pairs_kernel (csrc/gather_device.h) through the launch code of the score and align stages, for a mapper's q, corridor,
+ * reference and engine.  reads: n_reads rows of qry_max_len bytes, uploaded and measured as a batch's are (by the candidate search);
+ * pair p = (pair_read[p] < n_reads, pair_loc[p], pair_sv[p]: bit 0 = reverse strand); alt_dir: 0 off, 1 single-end, 2 paired (the table bit
+ * of the read classes); align_stage: 0 = the score stage's window geometry, ((q + c) | 1) + 1, 1 = the align stage's, (q + c) | 2.
+ * dims = {RW, FW}: read and window words per pair; with words, lens and blk_rows all NULL nothing else is done.  words: the packed
+ * workspace as it stands, ceil(n_pairs / 64) * (RW + FW) * 64 dwords (block b, word m, slot s at (b * (RW + FW) + m) * 64 + s; window words
+ * from m = RW); lens[n_pairs]; blk_rows[ceil(n_pairs / 64)].  A word the kernel did not write reads as 0xFFFFFFFF.  The call disturbs the
+ * mapper's batch state like a map call does: its uploaded reads (batch_reads), the per-read and candidate arrays of the last search (a whole
+ * candidate search runs, only to measure the reads) and the search's paired flag (set to single-end).  Returns 0, or a negative error code;
+ * -22 before anything is taken for a pair whose read does not exist.  tests/test_gpu_gather.py compares it with tests/ngm_host_model.py. */
+int ngm_debug_gather_pairs(ngm_mapper *m, int n_reads, const char *reads, int n_pairs, const uint32_t *pair_read, const uint32_t *pair_loc, const uint32_t *pair_sv,
+		int alt_dir, int align_stage, int dims[2], uint32_t *words, uint16_t *lens, uint16_t *blk_rows);
+
 /* test hook: expand_pairs_kernel (csrc/gather_device.h) over host arrays: out[base[i] + k] = i for k < count[i]; out has n_cand entries, the
  * ones no read owns are left as 0xFFFFFFFF. */
 int ngm_debug_expand_pairs(int device, int n_reads, const uint32_t *base, const uint32_t *count, uint64_t n_cand, uint32_t *out);

@@ -21,7 +21,11 @@
 namespace ngm {
 
 __host__ __device__ constexpr int dir_words(int C) { return (2 * C + 31) / 32; }
-__host__ __device__ constexpr int run_stride(int q, int c) { return (q + c + 8 + 7) & ~7; }
+// u16 per pair in the traceback's run scratch: room for the longest path through the band -- every step a run of its own, at most q rows
+// and q + c window columns (alternating 1-base insertions and deletions, which scores with gaps far cheaper than a mismatch do produce).
+// (q + c + 8 until the linear string builder was pinned: the tracebacks drop the runs beyond the stride, and such an alignment came back
+// without its first runs and still valid.)
+__host__ __device__ constexpr int run_stride(int q, int c) { return (2 * q + c + 8 + 7) & ~7; }
 
 enum { kDirStop = 0, kDirDiag = 1, kDirUp = 2, kDirLeft = 3 };
 // run ops emitted by the traceback: 0 = forced mismatch column (band border in end-to-end mode, the

@@ -50,6 +50,10 @@ struct ngm_hip_ctx {
 namespace ngm {
 // workspace for n pairs (packed batch, lens, blk_rows); returns 0 or a negative error
 int engine_reserve(ngm_hip_ctx *ctx, int n);
+// the host-pointer entry points' way into that workspace: the `dir` bytes of n pairs staged for the next pack (null: all pairs use the
+// FWD table), and pack_pairs_kernel over n flat rows of q + c window bytes / q read bytes in device memory
+int engine_stage_dirs(ngm_hip_ctx *ctx, int n, const char *dir);
+int engine_pack(ngm_hip_ctx *ctx, int n, const void *d_ref, const void *d_qry, hipStream_t st);
 // DP over ctx->packed / ctx->lens / ctx->blk_rows (filled by pack_pairs_kernel or gather_pairs_kernel)
 int engine_score_packed(ngm_hip_ctx *ctx, int mode, int n, float *d_scores, hipStream_t st);
 // fin (affine personality only): behind the DP, affine_finish_kernel builds the strings from the trace matrix in one launch instead of the

@@ -67,6 +67,23 @@ void host_window(const ngm_ref *r, uint64_t offset, int buffer_len, int want, ch
 	}
 }
 
+// The two window geometries of a mapper (gather_device.h): the score stage's refMaxLen (ScoreBuffer.h:112), the align stage's
+// (AlignmentBuffer.h:67: (qry_max_len + corridor) | 1 + 1)
+ngm::WindowGeom window_geom(const ngm_mapper *m, bool align_stage) {
+	const int q = m->prm.qry_max_len, c = m->prm.corridor;
+	return ngm::WindowGeom{m->ref->n_bases - 1, align_stage ? ((q + c) | 2) : (((q + c) | 1) + 1), c >> 1};
+}
+
+// The gather's launch on the mapper's stream, shared by score_candidates, align and the test hook ngm_debug_gather_pairs: n_pairs pairs
+// (pair_read, pair_loc, pair_sv in device memory) of the batch's reads into the engine's packed workspace (reserved by the caller)
+int launch_gather(ngm_mapper *m, const ngm::WindowGeom &G, const uint32_t *pair_read, const uint32_t *pair_loc, const uint32_t *pair_sv, int n_pairs, int alt_dir) {
+	ngm_hip_ctx *eng = m->eng;
+	hipLaunchKernelGGL(ngm::gather_pairs_kernel, dim3((n_pairs + ngm::kSlots - 1) / ngm::kSlots), dim3(256), 0, m->st, m->batch_reads, m->d_read_len.p, m->prm.qry_max_len,
+			m->ref->d_genome.p, G, pair_read, pair_loc, pair_sv, n_pairs, eng->RW, eng->FW, eng->packed.p, eng->lens.p, eng->blk_rows.p, alt_dir);
+	MAP_HIP_TRY(hipGetLastError());
+	return 0;
+}
+
 }  // namespace
 
 namespace ngm {
@@ -74,15 +91,9 @@ namespace ngm {
 // candidate; events ev[2] (behind the gather) and ev[3] (behind the score kernels).  The caller has reserved d_pair_read / d_scores and the
 // engine's buffers for np candidates.
 int score_candidates(ngm_mapper *m, int n, uint64_t np, int alt_dir) {
-	const ngm_ref *r = m->ref;
 	ngm_hip_ctx *eng = m->eng;
-	const int q = m->prm.qry_max_len, c = m->prm.corridor;
 	hipLaunchKernelGGL(ngm::expand_pairs_kernel, dim3((n + 255) / 256), dim3(256), 0, m->st, n, m->d_cand_base.p, m->d_cand_count.p, m->d_pair_read.p);
-	const int nb = (int) ((np + ngm::kSlots - 1) / ngm::kSlots);
-	ngm::WindowGeom Gs{r->n_bases - 1, ((q + c) | 1) + 1, c >> 1};  // refMaxLen of ScoreBuffer.h:112
-	hipLaunchKernelGGL(ngm::gather_pairs_kernel, dim3(nb), dim3(256), 0, m->st, m->batch_reads, m->d_read_len.p, q, r->d_genome.p, Gs,
-			m->d_pair_read.p, m->d_out_loc.p, m->d_out_sv.p, (int) np, eng->RW, eng->FW, eng->packed.p, eng->lens.p, eng->blk_rows.p, alt_dir);
-	MAP_HIP_TRY(hipGetLastError());
+	if (int rc = launch_gather(m, window_geom(m, false), m->d_pair_read.p, m->d_out_loc.p, m->d_out_sv.p, (int) np, alt_dir)) return rc;
 	MAP_HIP_TRY(hipEventRecord(m->ev[2], m->st));
 	if (int rc = ngm::engine_score_packed(eng, m->prm.mode, (int) np, m->d_scores.p, m->st)) { ngm::pipeline_set_error("%s", ngm_hip_last_error(eng)); return rc; }
 	MAP_HIP_TRY(hipEventRecord(m->ev[3], m->st));
@@ -121,6 +132,46 @@ static int launch_pair_select(hipStream_t st, size_t npairs, const uint32_t *can
 			(const uint32_t *) huge_list, (const uint32_t *) huge_count, cand_base, cand_count, scores, loc, read_len, min_d, max_d, cutoff,
 			out + npairs, tops, tied_n, (uint32_t) npairs, (uint32_t *) nullptr, (uint32_t *) nullptr, (const uint32_t *) (list + npairs));
 	MAP_HIP_TRY(hipGetLastError());
+	return 0;
+}
+
+// The align stage's launches behind the gather (or the pack) wherever cigar_strings_kernel builds the strings -- every configuration but the affine
+// personality's one finishing kernel -- on `st`, shared by align and the test hook ngm_debug_linear_strings: DP + traceback over the engine's packed
+// workspace (engine_align_packed; with the engine's event [2] between the two), the runs compacted into runs_c with their total at *run_total, and
+// with `S` CIGAR / MD / NM / identity per alignment, the strings in S->bytes with their total at *S->cursor.  ev_dp / ev_last: recorded behind the
+// traceback / behind the last kernel when not null.  Buffers are the caller's: records 8 n, runs n * rs, runs_c n * rs, the two counters.
+struct AlignStrings {
+	ngm::CigarDevOut *out; char *bytes; unsigned long long capacity, *cursor;
+	const uint16_t *read_len; const uint32_t *a_read;   // affine personality only: per read, and the read of alignment j
+	int variant, hard_clip, silent_clip, alt_cigar;
+};
+static int launch_compact_runs(ngm_hip_ctx *eng, hipStream_t st, int n, int32_t *records, uint16_t *runs, int rs, uint16_t *runs_c, unsigned long long *run_total, bool traceback_first) {
+	MAP_HIP_TRY(hipMemsetAsync(run_total, 0, 8, st));
+	if (traceback_first) if (int rc = ngm::engine_affine_traceback_packed(eng, n, records, runs, rs, st)) { ngm::pipeline_set_error("%s", ngm_hip_last_error(eng)); return rc; }
+	hipLaunchKernelGGL(ngm::compact_runs_kernel, dim3((n + 255) / 256), dim3(256), 0, st, n, records, runs, rs, runs_c, run_total);
+	MAP_HIP_TRY(hipGetLastError());
+	return 0;
+}
+static int launch_align_strings(ngm_hip_ctx *eng, hipStream_t st, int mode, int n, int32_t *records, uint16_t *runs, int rs, uint16_t *runs_c, unsigned long long *run_total,
+		const AlignStrings *S, hipEvent_t ev_dp, hipEvent_t ev_last) {
+	const bool was_prof = eng->profiling;
+	eng->profiling = true;  // brackets DP vs traceback with eng->ev[2]
+	const int rc = ngm::engine_align_packed(eng, mode, n, records, runs, rs, st);
+	eng->profiling = was_prof;
+	if (rc) { ngm::pipeline_set_error("%s", ngm_hip_last_error(eng)); return rc; }
+	if (ev_dp) MAP_HIP_TRY(hipEventRecord(ev_dp, st));
+	if (int rc2 = launch_compact_runs(eng, st, n, records, runs, rs, runs_c, run_total, false)) return rc2;
+	// CIGAR / MD / NM / identity on the GPU (cigar_device.h)
+	if (S) {
+		MAP_HIP_TRY(hipMemsetAsync(S->cursor, 0, 8, st));
+		const int variant_cpu = S->variant == NGM_VARIANT_OCL_CPU ? 1 : 0;
+		if (eng->prm.personality == NGM_PERSONALITY_AFFINE) hipLaunchKernelGGL(ngm::cigar_strings_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, st, n, records, runs_c, eng->packed.p, eng->RW, eng->FW,
+				S->read_len, S->a_read, variant_cpu, S->hard_clip, S->silent_clip, S->out, S->bytes, S->capacity, S->cursor, 0);
+		else hipLaunchKernelGGL(ngm::cigar_strings_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, st, n, records, runs_c, eng->packed.p, eng->RW, eng->FW,
+				S->read_len, S->a_read, variant_cpu, S->hard_clip, S->silent_clip, S->out, S->bytes, S->capacity, S->cursor, S->alt_cigar);
+		MAP_HIP_TRY(hipGetLastError());
+	}
+	if (ev_last) MAP_HIP_TRY(hipEventRecord(ev_last, st));
 	return 0;
 }
 
@@ -322,15 +373,9 @@ void compact_winners(MapBatch &b) {
 // kernel has left alignments to the host (trace matrix and end cells are still there)
 int compact_runs(MapBatch &b, int rs, bool traceback_first) {
 	ngm_mapper *m = b.m;
-	ngm_hip_ctx *eng = m->eng;
 	const int na = b.na;
 	MAP_OOM_TRY(m->d_runs_c.reserve((size_t) na * rs), "out of device memory (runs)");
-	MAP_HIP_TRY(hipMemsetAsync(m->d_total.p, 0, 8, m->st));
-	if (traceback_first) if (int rc = ngm::engine_affine_traceback_packed(eng, na, m->d_records.p, m->d_runs.p, rs, m->st)) { ngm::pipeline_set_error("%s", ngm_hip_last_error(eng)); return rc; }
-	hipLaunchKernelGGL(ngm::compact_runs_kernel, dim3((na + 255) / 256), dim3(256), 0, m->st, na, m->d_records.p, m->d_runs.p, rs,
-			m->d_runs_c.p, m->d_total.p);
-	MAP_HIP_TRY(hipGetLastError());
-	return 0;
+	return launch_compact_runs(m->eng, m->st, na, m->d_records.p, m->d_runs.p, rs, m->d_runs_c.p, m->d_total.p, traceback_first);
 }
 // ... the compacted runs on the host (behind the synchronisation that brought their total)
 int fetch_runs(MapBatch &b, unsigned long long n_runs_total) {
@@ -352,7 +397,6 @@ int fetch_strings(MapBatch &b, unsigned long long n_str_total) {
 // ---- alignment stage: one pair per read that has a winner (AlignmentBuffer::DoRun) --------------------
 int align(MapBatch &b) {
 	ngm_mapper *m = b.m;
-	const ngm_ref *r = m->ref;
 	ngm_hip_ctx *eng = m->eng;
 	const int q = b.q, c = b.c, mode = m->prm.mode, topn = b.topn, alt_cigar = b.alt_cigar, alt_dir = b.alt_dir;
 	compact_winners(b);
@@ -360,7 +404,8 @@ int align(MapBatch &b) {
 	const int rs = ngm::run_stride(q, c);
 	MAP_OOM_TRY(m->p_rec.reserve((size_t) na * 8 + 8), "out of pinned host memory");
 	int32_t *h_rec = b.h_rec = m->p_rec.p;
-	const int align_buf_len = b.align_buf_len = (q + c) | 2;  // AlignmentBuffer.h:67: (qry_max_len + corridor) | 1 + 1
+	const ngm::WindowGeom Ga = window_geom(m, true);
+	b.align_buf_len = Ga.buffer_len;
 	static const bool dev_strings = !getenv("NGM_HIP_HOST_CIGAR");
 	b.dev_strings = dev_strings;
 	GpuStage stage_align(m, 1, false);
@@ -377,16 +422,13 @@ int align(MapBatch &b) {
 		const bool finish = affine && dev_strings && topn == 1 && !tail_split;
 		const unsigned long long scap = (unsigned long long) na * 96ull + 4096ull;
 		MAP_OOM_TRY(dev_strings && (m->d_cigout.reserve(na) || m->d_str.reserve(scap) || m->p_cigout.reserve(na)), "out of memory (CIGAR strings)");
+		MAP_OOM_TRY(!finish && m->d_runs_c.reserve((size_t) na * rs), "out of device memory (runs)");
 		if (finish) MAP_HIP_TRY(hipMemsetAsync(m->d_total.p + 8, 0, 16, m->st));   // the stage's one memset: stream cursor + fall-back counter
 		MAP_HIP_TRY(hipStreamSynchronize(m->st));   // (the uploads travel outside the stage lock)
 		stage_align.acquire();
 		MAP_HIP_TRY(hipEventRecord(m->ev[5], m->st));
-		ngm::WindowGeom Ga{r->n_bases - 1, align_buf_len, c >> 1};
-		hipLaunchKernelGGL(ngm::gather_pairs_kernel, dim3((na + ngm::kSlots - 1) / ngm::kSlots), dim3(256), 0, m->st, m->batch_reads, m->d_read_len.p, q,
-				r->d_genome.p, Ga, m->d_a_read.p, m->d_a_loc.p, m->d_a_sv.p, na, eng->RW, eng->FW, eng->packed.p, eng->lens.p, eng->blk_rows.p, alt_dir);
-		MAP_HIP_TRY(hipGetLastError());
+		if (int rc = launch_gather(m, Ga, m->d_a_read.p, m->d_a_loc.p, m->d_a_sv.p, na, alt_dir)) return rc;
 		MAP_HIP_TRY(hipEventRecord(m->ev[6], m->st));
-		const bool was_prof = eng->profiling;
 		// affine, strings on the GPU, one alignment per read: DP, then ONE finishing kernel from the trace matrix to the strings
 		// (affine_finish_kernel, cigar_device.h).  NGM_HIP_ALIGN_TAIL_SPLIT=1 keeps the three kernels traceback / compact_runs / cigar_strings
 		// and their downloads (tests); they also serve every other mode, and the alignments the finishing kernel leaves to the host.
@@ -394,6 +436,7 @@ int align(MapBatch &b) {
 		if (finish) {
 			unsigned long long ctr[2] = {0, 0};   // [0] bytes of the string stream, [1] alignments left to the host
 			const ngm::AlignFinish fin{m->d_cigout.p, m->d_str.p, scap, m->d_total.p + 8};
+			const bool was_prof = eng->profiling;
 			eng->profiling = true;  // brackets DP vs finishing kernel with eng->ev[2]
 			if (int rc = ngm::engine_align_packed(eng, mode, na, m->d_records.p, m->d_runs.p, rs, m->st, &fin)) { eng->profiling = was_prof; ngm::pipeline_set_error("%s", ngm_hip_last_error(eng)); return rc; }
 			eng->profiling = was_prof;
@@ -415,23 +458,11 @@ int align(MapBatch &b) {
 				if (int rc = fetch_runs(b, n_runs_total)) return rc;
 			}
 		} else {
-			eng->profiling = true;  // brackets DP vs traceback with eng->ev[2]
-			if (int rc = ngm::engine_align_packed(eng, mode, na, m->d_records.p, m->d_runs.p, rs, m->st)) { eng->profiling = was_prof; ngm::pipeline_set_error("%s", ngm_hip_last_error(eng)); return rc; }
-			eng->profiling = was_prof;
-			MAP_HIP_TRY(hipEventRecord(m->ev[7], m->st));
-			if (int rc = compact_runs(b, rs, false)) return rc;
-			if (!dev_strings) { MAP_HIP_TRY(hipEventRecord(m->ev[8], m->st)); }   // (behind the stage's last kernel)
-			// CIGAR / MD / NM / identity on the GPU (cigar_device.h); NGM_HIP_HOST_CIGAR=1 keeps the host builders (tests)
+			// DP + traceback, the runs compacted, and CIGAR / MD / NM / identity on the GPU (cigar_device.h); NGM_HIP_HOST_CIGAR=1 keeps the
+			// host builders (tests).  ev[7] behind the traceback, ev[8] behind the stage's last kernel.
+			const AlignStrings str{m->d_cigout.p, m->d_str.p, scap, m->d_total.p + 8, m->d_read_len.p, m->d_a_read.p, m->prm.variant, m->prm.hard_clip, m->prm.silent_clip, alt_cigar};
+			if (int rc = launch_align_strings(eng, m->st, mode, na, m->d_records.p, m->d_runs.p, rs, m->d_runs_c.p, m->d_total.p, dev_strings ? &str : nullptr, m->ev[7], m->ev[8])) return rc;
 			if (dev_strings) {
-				MAP_HIP_TRY(hipMemsetAsync(m->d_total.p + 8, 0, 8, m->st));
-				if (affine) hipLaunchKernelGGL(ngm::cigar_strings_kernel<true>, dim3((na + 255) / 256), dim3(256), 0, m->st, na, m->d_records.p, m->d_runs_c.p, eng->packed.p, eng->RW, eng->FW,
-						m->d_read_len.p, m->d_a_read.p, m->prm.variant == NGM_VARIANT_OCL_CPU ? 1 : 0, m->prm.hard_clip, m->prm.silent_clip, m->d_cigout.p, m->d_str.p, scap,
-						(unsigned long long *) (m->d_total.p + 8), 0);
-				else hipLaunchKernelGGL(ngm::cigar_strings_kernel<false>, dim3((na + 255) / 256), dim3(256), 0, m->st, na, m->d_records.p, m->d_runs_c.p, eng->packed.p, eng->RW, eng->FW,
-						m->d_read_len.p, m->d_a_read.p, m->prm.variant == NGM_VARIANT_OCL_CPU ? 1 : 0, m->prm.hard_clip, m->prm.silent_clip, m->d_cigout.p, m->d_str.p, scap,
-						(unsigned long long *) (m->d_total.p + 8), alt_cigar);
-				MAP_HIP_TRY(hipGetLastError());
-				MAP_HIP_TRY(hipEventRecord(m->ev[8], m->st));
 				MAP_HIP_TRY(hipMemcpyAsync(m->p_cigout.p, m->d_cigout.p, (size_t) na * sizeof(ngm::CigarDevOut), hipMemcpyDeviceToHost, m->st));
 				MAP_HIP_TRY(hipMemcpyAsync(&n_str_total, m->d_total.p + 8, 8, hipMemcpyDeviceToHost, m->st));
 			}
@@ -948,6 +979,110 @@ int ngm_debug_pair_select(int device, int n_pairs, const uint32_t *base, const u
 	MAP_HIP_TRY(hipMemcpy(counts, d_tied_n.p, 16, hipMemcpyDeviceToHost));
 	MAP_HIP_TRY(hipMemcpy(entries, d_out.p, (2 * npairs + 2) * sizeof(ngm::PairOut), hipMemcpyDeviceToHost));
 	MAP_HIP_TRY(hipMemcpy(tops, d_top.p, (npairs + 1) * sizeof(ngm::PairTop), hipMemcpyDeviceToHost));
+	return 0;
+}
+
+int ngm_debug_linear_strings(void *engine, int mode, int n, const char *const *ref, const char *const *qry, const char *dir, uint64_t capacity, void *out_records,
+		uint8_t *built_by, uint64_t *cursor) {
+	ngm_hip_ctx *ctx = (ngm_hip_ctx *) engine;
+	ngm_hip_align_out *out = (ngm_hip_align_out *) out_records;
+	if (!ctx || !out || !built_by || !cursor) return -22;
+	*cursor = 0;
+	if (n <= 0) return 0;
+	if (ctx->prm.personality != NGM_PERSONALITY_LINEAR) { ctx->error = "ngm_debug_linear_strings: linear-gap personality only"; return -22; }
+	const int am = mode & NGM_MODE_ALIGN_MASK;
+	if (am != NGM_MODE_LOCAL && am != NGM_MODE_END_TO_END) { ctx->error = "ngm_debug_linear_strings: unsupported alignment mode"; return -22; }
+	DevGuard g(ctx->device);
+	auto fail = [&](int rc) { ctx->error = ngm_pipeline_last_error(); return rc; };   // (what the shared launch code reports)
+	const size_t rl = ctx->rl, q = ctx->q;
+	const int rs = ngm::run_stride(ctx->q, ctx->c);
+	const unsigned long long scap = capacity ? capacity : (unsigned long long) n * 96ull + 4096ull;   // 0: the align stage's
+	ngm::DevBuf<ngm::CigarDevOut> d_out;
+	ngm::DevBuf<char> d_str;
+	ngm::DevBuf<uint16_t> d_runs_c;
+	ngm::DevBuf<unsigned long long> d_ctr;   // [0] runs, [1] the byte stream's cursor
+	if (ctx->h_ref.reserve((size_t) n * rl) || ctx->h_qry.reserve((size_t) n * q) || ctx->d_ref.reserve((size_t) n * rl) || ctx->d_qry.reserve((size_t) n * q) ||
+			ctx->d_records.reserve((size_t) n * 8) || ctx->d_runs.reserve((size_t) n * rs) || ctx->h_records.reserve((size_t) n * 8) || d_out.reserve(n) || d_str.reserve(scap) ||
+			d_runs_c.reserve((size_t) n * rs) || d_ctr.reserve(2)) { ctx->error = "out of memory (ngm_debug_linear_strings)"; return -12; }
+	if (int rc = ngm::engine_stage_dirs(ctx, n, dir)) return rc;
+	for (int i = 0; i < n; ++i) {
+		memcpy(ctx->h_ref.p + (size_t) i * rl, ref[i], rl);
+		memcpy(ctx->h_qry.p + (size_t) i * q, qry[i], q);
+	}
+	hipStream_t st = ctx->stream;
+	if (hipMemcpyAsync(ctx->d_ref.p, ctx->h_ref.p, (size_t) n * rl, hipMemcpyHostToDevice, st) != hipSuccess ||
+			hipMemcpyAsync(ctx->d_qry.p, ctx->h_qry.p, (size_t) n * q, hipMemcpyHostToDevice, st) != hipSuccess) { ctx->error = "ngm_debug_linear_strings: upload failed"; return -5; }
+	if (int rc = ngm::engine_reserve(ctx, n)) return rc;
+	if (int rc = ngm::engine_pack(ctx, n, ctx->d_ref.p, ctx->d_qry.p, st)) return rc;
+	const AlignStrings str{d_out.p, d_str.p, scap, d_ctr.p + 1, nullptr, nullptr, ctx->prm.variant, ctx->prm.hard_clip, ctx->prm.silent_clip, ctx->prm.alt_cigar};
+	if (int rc = launch_align_strings(ctx, st, mode, n, ctx->d_records.p, ctx->d_runs.p, rs, d_runs_c.p, d_ctr.p, &str, nullptr, nullptr)) return fail(rc);
+	std::vector<ngm::CigarDevOut> h_out((size_t) n);
+	unsigned long long ctr[2] = {0, 0};
+	auto download = [&]() -> int {
+		MAP_HIP_TRY(hipMemcpyAsync(h_out.data(), d_out.p, (size_t) n * sizeof(ngm::CigarDevOut), hipMemcpyDeviceToHost, st));
+		MAP_HIP_TRY(hipMemcpyAsync(ctr, d_ctr.p, 16, hipMemcpyDeviceToHost, st));
+		MAP_HIP_TRY(hipMemcpyAsync(ctx->h_records.p, ctx->d_records.p, (size_t) n * 8 * 4, hipMemcpyDeviceToHost, st));
+		MAP_HIP_TRY(hipStreamSynchronize(st));
+		return 0;
+	};
+	if (int rc = download()) return fail(rc);
+	if (ctr[0] > (unsigned long long) n * rs) { ctx->error = "ngm_debug_linear_strings: more runs than the scratch holds"; return -75; }
+	const unsigned long long used = std::min(ctr[1], scap);
+	std::vector<uint16_t> h_runs((size_t) ctr[0] + 1);
+	std::vector<char> h_str((size_t) used + 1);
+	auto fetch = [&]() -> int {
+		if (ctr[0]) MAP_HIP_TRY(hipMemcpy(h_runs.data(), d_runs_c.p, (size_t) ctr[0] * 2, hipMemcpyDeviceToHost));
+		if (used) MAP_HIP_TRY(hipMemcpy(h_str.data(), d_str.p, (size_t) used, hipMemcpyDeviceToHost));
+		return 0;
+	};
+	if (int rc = fetch()) return fail(rc);
+	*cursor = ctr[1];
+	const ngm::CigarParams cp{ctx->prm.match_bonus, -ctx->prm.mismatch_penalty, ctx->prm.variant, ctx->prm.hard_clip, ctx->prm.silent_clip, ctx->prm.alt_cigar};
+	for (int i = 0; i < n; ++i) {   // as finish_hits: the device's strings where it built them, the host's builder on the compacted runs otherwise
+		const ngm::CigarDevOut &dv = h_out[(size_t) i];
+		built_by[i] = (dv.flags & 1) ? 1 : 0;
+		if (!(dv.flags & 1)) {
+			const int32_t *rec = ctx->h_records.p + (size_t) i * 8;
+			if ((uint64_t) (uint32_t) rec[6] + (uint64_t) (rec[0] ? rec[4] : 0) > ctr[0]) { ctx->error = "ngm_debug_linear_strings: runs beyond their total"; return -75; }
+			ngm::build_cigar_md(cp, rec, &h_runs[(size_t) (uint32_t) rec[6]], ref[i], qry[i], &out[i], (cp.alt && dir && dir[i]) ? 1 : 0);
+			continue;
+		}
+		if ((unsigned long long) dv.cig_off + dv.cig_len > used || (unsigned long long) dv.md_off + dv.md_len > used) { ctx->error = "ngm_debug_linear_strings: a string beyond the stream"; return -75; }
+		memcpy(out[i].cigar, h_str.data() + dv.cig_off, dv.cig_len); out[i].cigar[dv.cig_len] = 0;
+		memcpy(out[i].md, h_str.data() + dv.md_off, dv.md_len); out[i].md[dv.md_len] = 0;
+		out[i].position_offset = dv.position_offset; out[i].qstart = dv.qstart; out[i].qend = dv.qend;
+		out[i].score_token = dv.score_token; out[i].identity = dv.identity; out[i].nm = dv.nm;
+	}
+	return n;
+}
+
+int ngm_debug_gather_pairs(ngm_mapper *m, int n_reads, const char *reads, int n_pairs, const uint32_t *pair_read, const uint32_t *pair_loc, const uint32_t *pair_sv,
+		int alt_dir, int align_stage, int dims[2], uint32_t *words, uint16_t *lens, uint16_t *blk_rows) {
+	if (!m || !dims) return -22;
+	dims[0] = m->eng->RW; dims[1] = m->eng->FW;
+	if (!words && !lens && !blk_rows) return 0;   // (the sizes only)
+	if (n_reads <= 0 || n_pairs <= 0 || !reads || !pair_read || !pair_loc || !pair_sv || !words || !lens || !blk_rows || alt_dir < 0 || alt_dir > 2) return -22;
+	for (int p = 0; p < n_pairs; ++p) if (pair_read[p] >= (uint32_t) n_reads) { ngm::pipeline_set_error("ngm_debug_gather_pairs: pair %d names read %u of %d", p, pair_read[p], n_reads); return -22; }
+	DevGuard g(m->ref->device);
+	ngm_hip_ctx *eng = m->eng;
+	const size_t nb = ((size_t) n_pairs + ngm::kSlots - 1) / ngm::kSlots, n_words = nb * (size_t) (eng->RW + eng->FW) * ngm::kSlots;
+	ngm::DevBuf<uint32_t> d_pr, d_pl, d_ps;
+	MAP_OOM_TRY(d_pr.reserve(n_pairs) || d_pl.reserve(n_pairs) || d_ps.reserve(n_pairs), "out of device memory (ngm_debug_gather_pairs)");
+	if (int rc = ngm::engine_reserve(eng, n_pairs)) { ngm::pipeline_set_error("%s", ngm_hip_last_error(eng)); return rc; }
+	// the rows and their lengths as a batch's: uploaded, and searched -- the candidate search measures the reads (its candidates are not used)
+	if (int rc = upload_reads(m, n_reads, reads)) return rc;
+	m->cs_paired = false;
+	if (int rc = run_cs(m, n_reads)) return rc;
+	MAP_HIP_TRY(hipMemcpyAsync(d_pr.p, pair_read, (size_t) n_pairs * 4, hipMemcpyHostToDevice, m->st));
+	MAP_HIP_TRY(hipMemcpyAsync(d_pl.p, pair_loc, (size_t) n_pairs * 4, hipMemcpyHostToDevice, m->st));
+	MAP_HIP_TRY(hipMemcpyAsync(d_ps.p, pair_sv, (size_t) n_pairs * 4, hipMemcpyHostToDevice, m->st));
+	MAP_HIP_TRY(hipMemsetAsync(eng->packed.p, 0xFF, n_words * 4, m->st));   // (a word the kernel leaves out reads as eight classes 15)
+	MAP_HIP_TRY(hipMemsetAsync(eng->blk_rows.p, 0xFF, nb * 2, m->st));
+	if (int rc = launch_gather(m, window_geom(m, align_stage != 0), d_pr.p, d_pl.p, d_ps.p, n_pairs, alt_dir)) return rc;
+	MAP_HIP_TRY(hipMemcpyAsync(words, eng->packed.p, n_words * 4, hipMemcpyDeviceToHost, m->st));
+	MAP_HIP_TRY(hipMemcpyAsync(lens, eng->lens.p, (size_t) n_pairs * 2, hipMemcpyDeviceToHost, m->st));
+	MAP_HIP_TRY(hipMemcpyAsync(blk_rows, eng->blk_rows.p, nb * 2, hipMemcpyDeviceToHost, m->st));
+	MAP_HIP_TRY(hipStreamSynchronize(m->st));
 	return 0;
 }
 

@@ -273,7 +273,9 @@ struct ScopedDevice {
 	~ScopedDevice() { if (prev >= 0) (void) hipSetDevice(prev); }
 };
 
-int launch_pack(ngm_hip_ctx *ctx, int n, const void *d_ref, const void *d_qry, hipStream_t st) {
+}  // namespace
+namespace ngm {
+int engine_pack(ngm_hip_ctx *ctx, int n, const void *d_ref, const void *d_qry, hipStream_t st) {
 	const int nb = n_blocks_of(n);
 	const size_t lds = (size_t) ngm::kSlots * (ctx->rl + ctx->q);
 	hipLaunchKernelGGL(ngm::pack_pairs_kernel, dim3(nb), dim3(256), lds, st, (const uint8_t *) d_ref,
@@ -284,7 +286,7 @@ int launch_pack(ngm_hip_ctx *ctx, int n, const void *d_ref, const void *d_qry, h
 }
 
 // the `dir` bytes of a host-pointer call -> device (null: all pairs use the FWD table)
-int stage_dirs(ngm_hip_ctx *ctx, int n, const char *dir) {
+int engine_stage_dirs(ngm_hip_ctx *ctx, int n, const char *dir) {
 	ctx->pair_dir = nullptr;
 	if ((!ctx->K.alt && !ctx->prm.alt_cigar) || !dir) return 0;
 	if (ctx->d_pair_dir.reserve(n)) { set_error(ctx, "out of memory staging %d pairs", n); return -12; }
@@ -293,7 +295,7 @@ int stage_dirs(ngm_hip_ctx *ctx, int n, const char *dir) {
 	return 0;
 }
 
-}  // namespace
+}  // namespace ngm
 
 extern "C" {
 
@@ -415,7 +417,7 @@ int ngm_hip_score_device(ngm_hip_ctx *ctx, int mode, int n, const void *d_ref, c
 	const int nb = n_blocks_of(n);
 	ctx->ev_valid[0] = ctx->ev_valid[1] = ctx->ev_valid[2] = false;
 	if (ctx->profiling) HIP_TRY(ctx, hipEventRecord(ctx->ev[0], st));
-	if (int r = launch_pack(ctx, n, d_ref, d_qry, st)) return r;
+	if (int r = ngm::engine_pack(ctx, n, d_ref, d_qry, st)) return r;
 	if (ctx->profiling) HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));
 	if (int r = ngm::engine_score_packed(ctx, mode, n, d_scores, st)) return r;
 	if (ctx->profiling) { HIP_TRY(ctx, hipEventRecord(ctx->ev[2], st)); ctx->ev_valid[0] = ctx->ev_valid[1] = true; }
@@ -427,7 +429,7 @@ int ngm_hip_batch_score(ngm_hip_ctx *ctx, int mode, int n, const char *const *re
 	if (!ctx) return -22;
 	if (n <= 0) return 0;  // SWOcl.cpp:39-42
 	ScopedDevice sd(ctx->device);
-	if (int r0 = stage_dirs(ctx, n, dir)) return r0;
+	if (int r0 = ngm::engine_stage_dirs(ctx, n, dir)) return r0;
 	const size_t rl = ctx->rl, q = ctx->q;
 	if (ctx->h_ref.reserve((size_t) n * rl) || ctx->h_qry.reserve((size_t) n * q) || ctx->h_scores.reserve(n) ||
 			ctx->d_ref.reserve((size_t) n * rl) || ctx->d_qry.reserve((size_t) n * q) || ctx->d_scores.reserve(n)) {
@@ -470,7 +472,7 @@ int ngm_hip_align_device(ngm_hip_ctx *ctx, int mode, int n, const void *d_ref, c
 	const int nb = n_blocks_of(n);
 	ctx->ev_valid[0] = ctx->ev_valid[1] = ctx->ev_valid[2] = false;
 	if (ctx->profiling) HIP_TRY(ctx, hipEventRecord(ctx->ev[0], st));
-	if (int r = launch_pack(ctx, n, d_ref, d_qry, st)) return r;
+	if (int r = ngm::engine_pack(ctx, n, d_ref, d_qry, st)) return r;
 	if (ctx->profiling) HIP_TRY(ctx, hipEventRecord(ctx->ev[1], st));
 	if (int r = ngm::engine_align_packed(ctx, mode, n, d_records, d_runs, run_stride, st)) return r;
 	if (ctx->profiling) { HIP_TRY(ctx, hipEventRecord(ctx->ev[3], st)); ctx->ev_valid[0] = ctx->ev_valid[1] = ctx->ev_valid[2] = true; }
@@ -482,7 +484,7 @@ int ngm_hip_batch_align(ngm_hip_ctx *ctx, int mode, int n, const char *const *re
 	if (!ctx) return -22;
 	if (n <= 0) return 0;  // SWOclCigar.cpp:109-112
 	ScopedDevice sd(ctx->device);
-	if (int r0 = stage_dirs(ctx, n, dir)) return r0;
+	if (int r0 = ngm::engine_stage_dirs(ctx, n, dir)) return r0;
 	const size_t rl = ctx->rl, q = ctx->q;
 	const int rs = ngm::run_stride(ctx->q, ctx->c);
 	if (ctx->h_ref.reserve((size_t) n * rl) || ctx->h_qry.reserve((size_t) n * q) || ctx->d_ref.reserve((size_t) n * rl) ||
@@ -556,7 +558,7 @@ int ngm_debug_align_finish(void *engine, int mode, int n, const char *const *ref
 	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_qry.p, ctx->h_qry.p, (size_t) n * q, hipMemcpyHostToDevice, ctx->stream));
 	HIP_TRY(ctx, hipMemsetAsync(d_ctr.p, 0, 16, ctx->stream));
 	if (int r = engine_reserve(ctx, n)) return r;
-	if (int r = launch_pack(ctx, n, ctx->d_ref.p, ctx->d_qry.p, ctx->stream)) return r;
+	if (int r = ngm::engine_pack(ctx, n, ctx->d_ref.p, ctx->d_qry.p, ctx->stream)) return r;
 	const ngm::AlignFinish fin{d_out.p, d_str.p, scap, d_ctr.p};
 	if (int r = ngm::engine_align_packed(ctx, mode, n, ctx->d_records.p, ctx->d_runs.p, rs, ctx->stream, &fin)) return r;
 	HIP_TRY(ctx, hipMemcpyAsync(h_out.data(), d_out.p, (size_t) n * sizeof(ngm::CigarDevOut), hipMemcpyDeviceToHost, ctx->stream));

@@ -77,6 +77,7 @@ def load_library():
     lib.ngm_hip_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
     lib.ngm_hip_set_profiling.argtypes = [C.c_void_p, C.c_int]
     lib.ngm_debug_align_finish.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+    lib.ngm_debug_linear_strings.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
     _lib = lib
     return lib
 
@@ -145,10 +146,13 @@ class Engine:
         assert r == n
         return out
 
-    def BatchAlign(self, mode, ref, qry, dirs=None, finish=False):
+    def BatchAlign(self, mode, ref, qry, dirs=None, finish=False, device_strings=False, capacity=0):
         """-> list of dicts(cigar, md, position_offset, qstart, qend, score_token, identity, nm).
         finish (affine personality): the mapper's align stage instead of the drop-in's -- DP, then the one finishing kernel from the
-        trace matrix to the strings; self.last_fallback = the alignments that kernel left to the old traceback and the host."""
+        trace matrix to the strings; self.last_fallback = the alignments that kernel left to the old traceback and the host.
+        device_strings (linear personality): the align stage of a default run -- DP + traceback, compact_runs_kernel, then
+        cigar_strings_kernel into a byte stream of `capacity` bytes (0: the mapper's n * 96 + 4096); self.last_built_by = uint8[n], 1 where
+        the kernel built the strings and 0 where the host's builder did, self.last_cursor = the stream cursor's final value."""
         n, ref, qry, rp, qp = self._ptr_lists(ref, qry)
         stride = 4 * max(1, self.q)  # AlignmentBuffer.cpp:106-109
         cig = np.zeros((n, stride), dtype=np.uint8)
@@ -164,6 +168,10 @@ class Engine:
             fb = C.c_uint64(0)
             r = self._check(self.lib.ngm_debug_align_finish(self.h, mode, n, rp, qp, outs, C.byref(fb)), n)
             self.last_fallback = int(fb.value)
+        elif device_strings:
+            by, cur = np.zeros(max(n, 1), np.uint8), C.c_uint64(0)
+            r = self._check(self.lib.ngm_debug_linear_strings(self.h, mode, n, rp, qp, None if d is None else d.ctypes.data, int(capacity), outs, by.ctypes.data, C.byref(cur)), n)
+            self.last_built_by, self.last_cursor = by[:n], int(cur.value)
         else:
             r = self._check(self.lib.ngm_hip_batch_align(self.h, mode, n, rp, qp, outs, None if d is None else d.ctypes.data), n)
         assert r == n

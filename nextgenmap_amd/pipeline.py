@@ -121,6 +121,7 @@ def _lib():
         lib.ngm_mapper_argos_counters.argtypes = [C.c_void_p, C.c_void_p]
         lib.ngm_mapper_argos_path_counters.argtypes = [C.c_void_p, C.c_void_p]
         lib.ngm_debug_argos_order.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        lib.ngm_debug_gather_pairs.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
         lib.ngm_debug_sam_records.restype = C.c_longlong
         lib.ngm_debug_sam_records.argtypes = ([C.c_int, C.POINTER(SamOptions)] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t] + [C.c_void_p] * 5 +
                                               [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p])
@@ -855,6 +856,24 @@ class Mapper:
         if self.lib.ngm_mapper_cs_fetch(self.h, loc.ctypes.data, strand.ctypes.data, votes.ctypes.data) < 0:
             raise _err()
         return offs, mx, loc[:tot], strand[:tot], votes[:tot]
+
+    def debug_gather_pairs(self, rows, pair_read, pair_loc, pair_sv, alt_dir=0, align_stage=False):
+        """ngm_debug_gather_pairs: gather_pairs_kernel as the score stage (align_stage: the align stage) launches it, for pairs (read index,
+        location, bit 0 of pair_sv = reverse strand) over `rows`.  -> (words uint32 [blocks, RW + FW, 64], lens uint16 [pairs], blk_rows
+        uint16 [blocks], RW, FW)"""
+        rows = np.ascontiguousarray(rows, dtype=np.uint8)
+        pr, pl, ps = (np.ascontiguousarray(a, dtype=np.uint32) for a in (pair_read, pair_loc, pair_sv))
+        n = len(pr)
+        assert rows.shape[1] == self.q and len(pl) == n and len(ps) == n
+        dims = np.zeros(2, np.int32)
+        if self.lib.ngm_debug_gather_pairs(self.h, 0, None, 0, None, None, None, 0, 0, dims.ctypes.data, None, None, None) < 0:
+            raise _err()
+        rw, fw, nb = int(dims[0]), int(dims[1]), (n + 63) // 64
+        words, lens, blk_rows = np.zeros((nb, rw + fw, 64), np.uint32), np.zeros(max(n, 1), np.uint16), np.zeros(max(nb, 1), np.uint16)
+        if self.lib.ngm_debug_gather_pairs(self.h, rows.shape[0], rows.ctypes.data, n, pr.ctypes.data, pl.ctypes.data, ps.ctypes.data, int(alt_dir), int(bool(align_stage)),
+                                           dims.ctypes.data, words.ctypes.data, lens.ctypes.data, blk_rows.ctypes.data) < 0:
+            raise _err()
+        return words, lens[:n], blk_rows[:nb], rw, fw
 
     def map_pe_raw(self, rows, d_rows=None, out=None):
         """Paired-end: rows 2i and 2i+1 are mates.  Same outputs as map_se_raw."""

@@ -107,3 +107,57 @@ def convert(geom, pos):
     if starts[u] - pos < 1000:
         return None
     return u - 1, pos - starts[u - 1]
+
+
+# ---- the gather of (read, window) pairs into the DP kernels' packed layout (gather_pairs_kernel, csrc/gather_device.h) ----------------
+READ_CLASS = np.full(256, 5, np.uint8)   # reads hold A C G T N (IParser.h:59-121): anything else counts as N
+WIN_CLASS = np.full(256, 5, np.uint8)    # what DecodeRefSequence leaves in a window: the genome's A C G T N, 'x', NUL
+for _k, _ch in enumerate(b"ACGT"):
+    READ_CLASS[_ch] = WIN_CLASS[_ch] = _k
+READ_CLASS[0] = WIN_CLASS[0] = 6
+WIN_CLASS[ord("x")] = 4
+
+
+def pack8(k):
+    """class codes [..., 8] -> one dword: nibble 2j = base j, nibble 2j + 1 = base j + 4"""
+    k = np.asarray(k, np.uint32)
+    w = np.zeros(k.shape[:-1], np.uint32)
+    for j in range(8):
+        w |= k[..., j] << np.uint32(4 * (2 * j if j < 4 else 2 * (j - 4) + 1))
+    return w
+
+
+def gather_pairs_model(genome, n_bases, rows, pair_read, pair_loc, pair_sv, q, c, rw, fw, alt_dir=0, align_stage=False):
+    """-> (words uint32 [blocks, rw + fw, 64], lens uint16 [pairs], blk_rows uint16 [blocks]): per pair the read (reverse-complemented for
+    a pair on the reverse strand, MappedRead::computeReverseSeq) and its window (DecodeRefSequence at loc - c / 2 with the stage's buffer
+    length; all N where that fails -- a loc below c / 2 wraps), as symbol classes, eight per word, rows interleaved over the 64 slots of a
+    block.  Bit 3 of the read classes: the pair uses the reverse score table (alt_dir 1: reverse strand; 2: second mates flip).  Lanes
+    beyond the last pair hold class 6 everywhere."""
+    rows = np.asarray(rows, np.uint8)
+    n = len(pair_read)
+    nb = (n + 63) // 64
+    buffer_len = ((q + c) | 2) if align_stage else (((q + c) | 1) + 1)
+    read_len = np.array([int(np.flatnonzero(r == 0)[0]) if (r == 0).any() else q for r in rows])
+    cls = np.full((nb * 64, 8 * (rw + fw)), 6, np.uint32)
+    lens = np.zeros(n, np.uint16)
+    blk_rows = np.zeros(nb, np.uint16)
+    for p in range(n):
+        ridx, rev = int(pair_read[p]), bool(int(pair_sv[p]) & 1)
+        L = int(read_len[ridx])
+        read = revcomp_row(rows[ridx], L) if rev else rows[ridx]
+        second = alt_dir == 2 and (ridx & 1)
+        dbit = 8 if alt_dir and ((not second) if rev else second) else 0
+        rc = np.full(8 * rw, 6, np.uint32)
+        rc[:L] = READ_CLASS[read[:L]]
+        cls[p, :8 * rw] = rc | dbit
+        offset = (int(pair_loc[p]) - (c >> 1)) % (1 << 64)
+        ok, win = decode_ref(genome, n_bases, offset, buffer_len)
+        wc = np.full(8 * fw, 5 if not ok else 6, np.uint32)
+        if ok:
+            k = min(buffer_len, 8 * fw)
+            wc[:k] = WIN_CLASS[win[:k]]
+        cls[p, 8 * rw:] = wc
+        lens[p] = L
+        blk_rows[p // 64] = max(blk_rows[p // 64], L)
+    words = pack8(cls.reshape(nb, 64, rw + fw, 8)).transpose(0, 2, 1)
+    return np.ascontiguousarray(words), lens, blk_rows

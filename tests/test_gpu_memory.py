@@ -187,3 +187,36 @@ def test_debug_entries_free_what_they_take(world):
     text, counters = P.debug_sam_records(**marshal(batch, False))
     assert text.count(b"\n") == 2 and counters[0] == 2
     assert _bytes(P.live_memory()) == _bytes(base)
+    # the two hooks that work on an engine's / a mapper's own workspace: what they take besides comes back with the call, the rest with the object
+    import nextgenmap_amd as N
+    from nextgenmap_amd import engine as E
+    from pairgen import make_pairs
+    pref, pqry = make_pairs(70, Q, CORRIDOR, seed=3, read_len=READ_LEN)
+    eng = N.Engine(Q, CORRIDOR)
+    assert len(eng.BatchAlign(0, pref, pqry, device_strings=True)) == 70 and int(eng.last_built_by.sum()) > 35
+    held = _bytes(P.live_memory())
+    eng.BatchAlign(0, pref, pqry, device_strings=True)
+    assert _bytes(P.live_memory()) == held
+    eng.close()
+    assert _bytes(P.live_memory()) == _bytes(base)
+    aff = N.Engine(Q, CORRIDOR, personality=E.PERSONALITY_AFFINE, gap_read=33, gap_ref=33, gap_extend=3)
+    held = _bytes(P.live_memory())
+    with pytest.raises(E.NgmHipError):          # (an affine engine: refused before anything is taken)
+        aff.BatchAlign(0, pref, pqry, device_strings=True)
+    assert _bytes(P.live_memory()) == held
+    aff.close()
+    assert _bytes(P.live_memory()) == _bytes(base)
+    ref = P.Reference.from_contigs([world["genome"]])
+    mp = P.Mapper(ref, Q, CORRIDOR)
+    pr, pl, ps = np.arange(70, dtype=np.uint32) % N_READS, np.arange(1000, 1070, dtype=np.uint32), np.arange(70, dtype=np.uint32) & 1
+    words, lens, _, rw, fw = mp.debug_gather_pairs(world["rows"], pr, pl, ps)
+    assert words.shape == (2, rw + fw, 64) and list(lens) == [READ_LEN] * 70
+    mp.debug_gather_pairs(world["rows"], pr, pl, ps)   # (the mapper's own buffers are final from the second batch on, as in test_steady_state_allocates_nothing)
+    held = _bytes(P.live_memory())
+    mp.debug_gather_pairs(world["rows"], pr, pl, ps, align_stage=True)
+    assert _bytes(P.live_memory()) == held
+    with pytest.raises(P.NgmHipError):          # (a pair of a read that is not there: refused before anything is taken)
+        mp.debug_gather_pairs(world["rows"], pr + N_READS, pl, ps)
+    assert _bytes(P.live_memory()) == held
+    mp.close(); ref.close()
+    assert _bytes(P.live_memory()) == _bytes(base)
